@@ -5,12 +5,15 @@ backbone -> transformer -> keypoint heads + fused PostProcess -> batched PnP -> 
 (+ one RCCL all-gather of the per-image pose records when N > 1).  Default workload is
 BASELINE config 2: ResNet50-s8 + 6/6 transformer, 11 queries, bf16, bs=64 per GPU, EPnP only.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
-Prints ONE JSON line (rank 0).  The dominant kernel's launches are bracketed with HIP events
-on the launch stream during the timed region (spe_model_profile_*) for the roofline object.
+Prints ONE JSON line (rank 0).  A plain run sets up, warms up, times the K steps and prints the
+headline fields.  --full adds everything else: a per-launch profiled step, the dominant kernel's
+launches bracketed with HIP events on the launch stream during the timed region
+(spe_model_profile_*) for the roofline object, the host_input and parity_mode lines, the accuracy
+against the exact-f32 mode, the north star and the CPU baseline.
 """
 import argparse
 import glob
@@ -83,6 +86,13 @@ def parse():
     p.add_argument("--gpus", type=int, default=1)
     p.add_argument("--steps", type=int, default=20)
     p.add_argument("--warmup", type=int, default=3)
+    p.add_argument("--full", action="store_true",
+                   help="besides the headline line's timed steps, also run everything else the benchmark measures: "
+                        "the per-launch profiled step + roofline, host_input, parity_mode, accuracy against exact "
+                        "f32, north_star and the CPU baseline (each still has its own --no-* switch)")
+    p.add_argument("--dump-outputs", dest="dump_outputs", default=None, metavar="DIR",
+                   help="after the timed steps, write what the last timed step returned (this rank's forward "
+                        "outputs, poses, scores) as DIR/<name>.npy, float32 or float64, at most 64 MB in all")
     p.add_argument("--model", default="detr", choices=["detr", "rtdetr_r18", "rtdetr_r50"],
                    help="detr: the REV DETR keypoint model (BASELINE configs); rtdetr_*: the UNC RT-DETR sigma model "
                         "(SURVEY 8f.4) at its speed config (256x256, 30 queries, 3 decoder layers, sigma-weighted "
@@ -118,7 +128,7 @@ def parse():
                    help="skip the host_input object (the same step fed from pinned host memory: 8-bit crops "
                         "copied H2D every step on a copy stream, REV/engine.py:92)")
     p.add_argument("--north-star", action="store_true",
-                   help="also time the north-star shape at N = 1 (default only for N > 1): global batch 256 over the "
+                   help="with --full: also time the north-star shape at N = 1 (default only for N > 1): global batch 256 over the "
                         "ranks, RANSAC-P3P + LM, bf16 and the parity dtype, accuracy against exact f32")
     p.add_argument("--no-north-star", action="store_true", help="skip the north_star object for N > 1")
     p.add_argument("--no-accuracy", action="store_true",
@@ -665,6 +675,71 @@ def stub_worker(args):
     return 0
 
 
+def time_plain(pipe, args, world, dev):
+    """The headline figure alone (a run without --full): warm-up, then EXACTLY args.steps timed steps
+    between barriers + synchronize, as in time_mode but with no profiled step and no event brackets;
+    elapsed = max over ranks.  Returns the timing and the last step's outputs."""
+    import torch
+    import torch.distributed as dist
+    from spe import dist as sd
+
+    def step():
+        out = pipe.run()
+        if world > 1:
+            sd.exchange_pose_records(out["poses"], out["s_t"], out["s_q"],
+                                     stream=out.get("stream") or torch.cuda.current_stream())
+        return out
+
+    for _ in range(max(args.warmup, 1)):
+        step()
+    if world > 1:
+        dist.barrier()
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for _ in range(args.steps):
+        out = step()
+    torch.cuda.synchronize()
+    t1 = time.perf_counter()
+    if world > 1:
+        dist.barrier()
+    elapsed = torch.tensor([t1 - t0], dtype=torch.float64, device=dev)
+    if world > 1:
+        dist.all_reduce(elapsed, op=dist.ReduceOp.MAX)
+    return {"elapsed": float(elapsed.item()), "out": out}
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out, path, limit=DUMP_LIMIT_BYTES):
+    """--dump-outputs: every tensor a caller of the timed step receives (out["forward"], out["poses"],
+    out["assess"], the SPEED scores s_t / s_q) as path/<group>_<key>.npy -- float64 tensors as float64,
+    everything else (bf16, integer status) as float32.  Over `limit` bytes in all, an array above its
+    equal share is cut to a fixed, seeded sample of its flattened elements (sorted indices)."""
+    import numpy as np
+    import torch
+    named = {}
+    for group in ("forward", "poses", "assess"):
+        for k, v in (out.get(group) or {}).items():
+            if isinstance(v, torch.Tensor):
+                named[f"{group}_{k}"] = v
+    for k in ("s_t", "s_q"):
+        if isinstance(out.get(k), torch.Tensor):
+            named[k] = out[k]
+    arrays = {k: v.detach().to(torch.float64 if v.dtype == torch.float64 else torch.float32).cpu().numpy()
+              for k, v in named.items()}
+    if sum(a.nbytes for a in arrays.values()) > limit:
+        share = limit // len(arrays)
+        for k in sorted(arrays):
+            a = arrays[k]
+            if a.nbytes > share:
+                idx = np.sort(np.random.default_rng(0).choice(a.size, share // a.itemsize, replace=False))
+                arrays[k] = a.reshape(-1)[idx]
+    os.makedirs(path, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(path, k + ".npy"), a)
+
+
 def time_mode(pipe, model, args, world, dev, dtype, attn_dtype, cfg, B, launch_table=None):
     """Warm-up, one per-launch-profiled step (dominant kernel class), then EXACTLY args.steps timed
     steps between barriers + synchronize, the dominant class's launches bracketed by HIP events on
@@ -1003,12 +1078,17 @@ def main():
     torch.cuda.synchronize()
 
     host = None
-    host_ok = (rcfg is None and not args.raw_frames and not args.no_host_input
+    host_ok = (args.full and rcfg is None and not args.raw_frames and not args.no_host_input
                and getattr(solver, "mode", None) != _lib_mode_ceres())
     if host_ok and not args.host_input_last:
         host = host_input_line(args, model, solver, cfg, world, rank, dev, overlap, B)
-    tm = time_mode(pipe, model, args, world, dev, args.dtype, args.attn_dtype, cfg, B, args.launch_table)
+    if args.full or args.launch_table:
+        tm = time_mode(pipe, model, args, world, dev, args.dtype, args.attn_dtype, cfg, B, args.launch_table)
+    else:
+        tm = time_plain(pipe, args, world, dev)
     out = tm["out"]
+    if args.dump_outputs and rank == 0:
+        dump_outputs(out, args.dump_outputs)
     score = float((out["s_t"] + out["s_q"]).mean().item())
     status = out["poses"]["status"].cpu()
 
@@ -1022,9 +1102,11 @@ def main():
     # ---- parity mode: the same weights, batch and pipeline in the fast parity dtype, timed the
     # same way (its own steps between barriers), with its accuracy against the exact-f32 mode
     parity = None
-    want_parity = (rcfg is None and not args.raw_frames and not args.no_parity and args.parity_dtype != args.dtype)
+    want_parity = (args.full and rcfg is None and not args.raw_frames and not args.no_parity
+                   and args.parity_dtype != args.dtype)
     ref = None
-    if rcfg is None and not args.raw_frames and not args.no_accuracy and (args.dtype != "fp32" or want_parity):
+    if (args.full and rcfg is None and not args.raw_frames and not args.no_accuracy
+            and (args.dtype != "fp32" or want_parity)):
         ref = Fp32Reference(cfg, w, data, solver, dev)
     acc = (accuracy_vs_fp32(model, ref, out, world, args.solver, args.config)
            if (ref is not None and args.dtype != "fp32") else None)
@@ -1052,7 +1134,7 @@ def main():
 
     # ---- the north-star shape (global bs 256, RANSAC-P3P + LM) for multi-GPU runs
     ns = None
-    if (rcfg is None and not args.raw_frames and not args.no_north_star and (world > 1 or args.north_star)
+    if (args.full and rcfg is None and not args.raw_frames and not args.no_north_star and (world > 1 or args.north_star)
             and (cfg.input_size, cfg.num_queries, cfg.enc_layers) == (416, 11, 6)):
         ns = north_star_line(args, cfg, w, world, rank, dev, overlap)
 
@@ -1079,14 +1161,14 @@ def main():
                    "parallelism": f"dp{world} (image sharding)"},
         "weights_sha256_16": weights_checksum(w),
         "weights_source": wsource,
-        "roofline": tm["roofline"],
-        "kernel_time_ms_per_step": tm["kernel_time_ms_per_step"],
+        **({"roofline": tm["roofline"], "kernel_time_ms_per_step": tm["kernel_time_ms_per_step"]}
+           if "roofline" in tm else {}),
         "speed_score_mean_random_weights": score,
         "solver_status_counts": {str(s): int((status == s).sum()) for s in range(5)},
     })
     if "assess" in out:
         result["self_assessment_reliable"] = int(out["assess"]["reliable"].sum().item())
-    if not args.raw_frames and "points_px" in out["forward"] and "probs" in out["forward"]:
+    if args.full and not args.raw_frames and "points_px" in out["forward"] and "probs" in out["forward"]:
         e = keypoint_error_px(out["forward"]["points_px"], out["forward"]["probs"], data)
         result["keypoints_vs_gt_px"] = {"median": float(np.median(e)), "p90": float(np.percentile(e, 90)),
                                         "fg_queries": int(e.size), "weights": args.weights}
@@ -1103,7 +1185,7 @@ def main():
         result["parity_mode"] = parity
     if ns is not None:
         result["north_star"] = ns
-    if world == 1 and not args.no_cpu_baseline:
+    if args.full and world == 1 and not args.no_cpu_baseline:
         result["cpu_baseline"] = (cpu_baseline(cfg, args.cpu_seconds, args.solver) if rcfg is None
                                   else cpu_baseline_rtdetr(rcfg, args.cpu_seconds))
     print(json.dumps(result))

@@ -3,8 +3,8 @@ compare two such dumps bit for bit.  Used to show that a kernel change which kee
 its accumulation order (a different DMA pipeline, a different launch form) leaves the accuracy-
 contract mode's results -- and so every validated bench line -- unchanged.
 
-  python scripts/lab/bitwise_forward.py dump gpurun_out/a.npz      (SPE_LIB_PATH selects the library)
-  python scripts/lab/bitwise_forward.py compare gpurun_out/a.npz gpurun_out/b.npz
+  python scripts/lab/bitwise_forward.py dump bench_out/a.npz      (SPE_LIB_PATH selects the library)
+  python scripts/lab/bitwise_forward.py compare bench_out/a.npz bench_out/b.npz
 """
 import argparse
 import os

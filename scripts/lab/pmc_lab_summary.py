@@ -1,5 +1,5 @@
 """Per-kernel PMC summary of scripts/lab/pmc_lab.sh output: clock, busy fractions, per-dispatch
-VALU / MFMA figures.  usage: python scripts/lab/pmc_lab_summary.py gpurun_out/pmc_lab"""
+VALU / MFMA figures.  usage: python scripts/lab/pmc_lab_summary.py bench_out/pmc_lab"""
 import collections
 import csv
 import glob

@@ -3,7 +3,7 @@ for every launch class, the algorithmic flops and bytes, the HIP-event time, ach
 and HBM GB/s, and the fraction of the binding gfx950 peak (MI355X_MICROARCH.md: 2500 TFLOP/s
 dense bf16, 8000 GB/s HBM).
 
-usage: python scripts/launch_summary.py gpurun_out/<tag>_launch_table.json [--out profiles/<tag>_class_roofline.json]
+usage: python scripts/launch_summary.py bench_out/<tag>_launch_table.json [--out profiles/<tag>_class_roofline.json]
 """
 import argparse
 import json

@@ -3,7 +3,7 @@
 Run the bench serialised on one stream with its launch table, once per counter (scripts/gpu_pmc_kinds.sh):
     rocprofv3 --kernel-trace --pmc FETCH_SIZE -- python3 bench.py --no-overlap --steps 1 ... --launch-table lt.json
 then
-    python scripts/pmc_kinds.py gpurun_out/pmc_kinds --table lt.json --out profiles/r4_pmc_kinds.json
+    python scripts/pmc_kinds.py bench_out/pmc_kinds --table lt.json --out profiles/r4_pmc_kinds.json
 
 The launch table lists the step's model launches in issue order (kind, algorithmic bytes); the
 rocprofv3 dispatches of the LAST step are aligned to it backwards: every GEMM / conv / LayerNorm /

@@ -1,6 +1,6 @@
 """Summarise rocprofv3 --pmc CSVs (scripts/gpu_pmc.sh output) per (kernel, grid size).
 
-usage: python scripts/pmc_summary.py gpurun_out/pmc_<tag> [--min-us 20] [--json out.json]
+usage: python scripts/pmc_summary.py bench_out/pmc_<tag> [--min-us 20] [--json out.json]
 FETCH_SIZE is doubled (gfx950 reports half of the bytes of 16-B/lane streaming reads,
 MI355X_MICROARCH.md "HBM"); SQ cycle counters are quad-cycles.
 """

@@ -1,7 +1,7 @@
 """Turn a FETCH_SIZE / WRITE_SIZE rocprofv3 PMC run (scripts/gpu_pmc.sh) into the per-launch
 HBM traffic figure bench.py reports as roofline.traffic.
 
-usage: python scripts/pmc_traffic.py gpurun_out/pmc_<tag> --kernel attn16_kernel --kind attn.enc \
+usage: python scripts/pmc_traffic.py bench_out/pmc_<tag> --kernel attn16_kernel --kind attn.enc \
            [--grid 2883584] [--out profiles/pmc_attn.enc.json]
 
 Corrections (MI355X_MICROARCH.md, "HBM"): FETCH_SIZE and WRITE_SIZE are in KiB; on gfx950

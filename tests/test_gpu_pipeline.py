@@ -341,3 +341,65 @@ def test_pipeline_host_input_matches_device_resident(gpu_device, small_model, st
             assert torch.equal(o["poses"][f], r["poses"][f]), f
         assert torch.equal(o["s_t"], r["s_t"]) and torch.equal(o["s_q"], r["s_q"])
     assert host.h2d_bytes == B * cfg.input_size ** 2 + B * 4 * 4 + B * 7 * 8
+
+
+def test_bench_plain_run_times_steps_and_dumps_outputs(gpu_device, tmp_path):
+    """`bench.py --gpus 1 --steps K --warmup W --dump-outputs DIR` on a small shape: one result line
+    with the headline fields, K timed steps, ms_per_step consistent with value, none of the objects
+    that belong to --full, and the last step's outputs as float32 / float64 .npy files of the
+    batch's shape."""
+    import json
+    import os
+    import subprocess
+    import sys
+    repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = dict(os.environ)
+    for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT", "SPE_BENCH_STUB"):
+        env.pop(k, None)
+    d = tmp_path / "out"
+    r = subprocess.run([sys.executable, os.path.join(repo, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
+                        "--batch", "4", "--size", "128", "--layers", "2", "--weights", "random", "--dump-outputs", str(d)],
+                       env=env, capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1, r.stdout
+    res = json.loads(lines[0])
+    assert res["steps"] == 3 and res["unit"] == "images/s" and res["higher_is_better"] is True and res["dtype"] == "bf16"
+    assert res["ms_per_step"] > 0 and res["value"] == pytest.approx(4 * 1e3 / res["ms_per_step"], rel=1e-9)
+    for k in ("roofline", "kernel_time_ms_per_step", "host_input", "parity_mode", "accuracy_vs_fp32", "north_star",
+              "cpu_baseline", "keypoints_vs_gt_px"):
+        assert k not in res, k
+    files = {p.name[:-4]: np.load(p) for p in d.iterdir()}
+    assert {"forward_probs", "forward_points_px", "poses_quat", "poses_tvec", "poses_status", "s_t", "s_q"} <= set(files)
+    assert all(a.dtype in (np.float32, np.float64) for a in files.values())
+    assert files["forward_probs"].shape == (4, 11, 12) and files["forward_points_px"].shape == (4, 11, 2)
+    assert files["poses_quat"].shape == (4, 4) and files["poses_status"].shape == (4,)
+    assert np.isfinite(files["forward_probs"]).all() and np.isfinite(files["forward_points_px"]).all()
+    assert sum(a.nbytes for a in files.values()) <= 64 << 20
+
+
+def test_bench_plain_timing_covers_exactly_the_timed_steps(gpu_device, monkeypatch):
+    """bench.time_plain runs `warmup` steps outside the clock and exactly `steps` inside it: with a
+    clock that counts the pipeline's run() calls, the elapsed time is `steps` and the pipeline ran
+    warmup + steps times; the returned outputs are the last step's."""
+    import importlib.util
+    import os
+    import types
+    repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    spec = importlib.util.spec_from_file_location("bench_mod", os.path.join(repo, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+
+    class CountingPipe:
+        calls = 0
+
+        def run(self):
+            self.calls += 1
+            return {"call": self.calls}
+
+    pipe = CountingPipe()
+    monkeypatch.setattr(bench, "time", types.SimpleNamespace(perf_counter=lambda: float(pipe.calls)))
+    for steps, warmup in ((5, 2), (1, 3)):
+        pipe.calls = 0
+        tm = bench.time_plain(pipe, argparse.Namespace(steps=steps, warmup=warmup), 1, gpu_device)
+        assert tm["elapsed"] == steps and pipe.calls == warmup + steps and tm["out"]["call"] == warmup + steps
