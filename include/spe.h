@@ -196,6 +196,23 @@ int spe_forward_stages_u8(spe_model* m, void* stream, const uint8_t* crops, int 
 int spe_preprocess(void* stream, const uint8_t* frames, int batch, int height, int width, int channels,
                    const double* bbox_xxyy, int size, float* images, float* clip_bbox, int32_t* status);
 
+/* Submission input pipeline on the device (SpeedSubmission.__getitem__, REV/datasets/speed.py:92-160,
+ * the dataset of gen_submission_single.py / gen_submission_multi.py): generate_clip_bbox (:92-108)
+ * gives the integer square x1 = int(xc - s/2), y1 = int(yc - s/2), side = int(s), s = 1.2 x the
+ * box's longer side (fp64, truncation towards zero), which is NOT clipped to the frame; the crop
+ * (:126-144) is a side x side zero canvas holding the in-frame part of that square ("pad instead
+ * of squeeze", 2020-12-14), then A.Resize(S, S, cv2.INTER_CUBIC), F.to_tensor and Normalize as in
+ * spe_preprocess.  frames / bbox_xxyy as for spe_preprocess.  images (nullable): fp32 [B,3,S,S];
+ * crops_u8 (nullable): uint8 [B,S,S,channels], the resized crop before to_tensor -- the input of
+ * spe_forward_stages_u8; at least one of the two is required (else SPE_E_ARG).  clip_bbox: fp32
+ * [B,4] = (x1, y1, x1 + side, y1 + side), PostProcess's box; it may be negative or extend past the
+ * frame.  status (nullable): [B] 0 ok, 1 when side <= 0 or the square shares no pixel with the
+ * frame (zeros written; parity unpinned: the reference raises or, through numpy's negative-slice
+ * wrap-around, returns a black crop, depending on the side the square lies on).  (ABI 9 addition) */
+int spe_preprocess_submission(void* stream, const uint8_t* frames, int batch, int height, int width, int channels,
+                              const double* bbox_xxyy, int size, float* images, uint8_t* crops_u8, float* clip_bbox,
+                              int32_t* status);
+
 /* Baseline-JPEG decode of grayscale frames on the device: the decode half of
  * `Image.open(img_path).convert('RGB')` in SpeedTrain.__getitem__ (REV/datasets/speed.py:209-210;
  * Pillow / libjpeg-turbo, islow IDCT), which the reference runs in DataLoader worker processes

@@ -18,6 +18,10 @@
 // resampled once and normalised into the three channels.  Arithmetic follows the restatement
 // in oracle/preprocess_ref.py operation for operation (this file is built with
 // -ffp-contract=off; divisions are IEEE), so the u8 crops match it bit for bit.
+//
+// preprocess_submission_kernel below is the same stage of SpeedSubmission (:92-160), the dataset
+// of the gen_submission scripts: an integer square padded with zeros instead of clipped
+// (restated in tests/submission_ref.py).
 #include "spe_common.h"
 #include "spe_kernels.h"
 
@@ -110,7 +114,116 @@ __global__ __launch_bounds__(256) void preprocess_kernel(const uint8_t* __restri
   }
 }
 
+// SpeedSubmission's crop (REV/datasets/speed.py:92-160, the 2020-12-14 "pad instead of squeeze"
+// rule): generate_clip_bbox (:92-108) gives an integer square that is never clipped to the frame,
+//   x1 = int(xc - s / 2), y1 = int(yc - s / 2), side = int(s), s = 1.2 x max side  (fp64; int()
+//   truncates towards zero, like the C cast below)
+// and __getitem__ (:113-160) copies the in-frame part of that box into a side x side zero canvas,
+// which A.Resize then resamples.  The canvas is never built here: canvas pixel (cx, cy) is frame
+// pixel (x1 + cx, y1 + cy) inside the frame and 0 outside it, and the taps are clamped to the
+// canvas (its replicated border), not to the frame.
+struct PadBox { int x1, y1, side; bool empty; };
+
+SPE_DEV PadBox pad_box(const double* bb, int W, int H) {
+  const double x1 = bb[0], y1 = bb[1], x2 = bb[2], y2 = bb[3];
+  const double scale = fmax(x2 - x1, y2 - y1) * 1.2;
+  const double xc = (x1 + x2) / 2, yc = (y1 + y2) / 2, hs = scale / 2;
+  // beyond +-1e9 the reference cannot allocate its canvas; clamped so the casts and x1 + side stay in int
+  const double lim = 1e9;
+  PadBox b;
+  b.x1 = (int)fmin(fmax(xc - hs, -lim), lim);
+  b.y1 = (int)fmin(fmax(yc - hs, -lim), lim);
+  b.side = (int)fmin(fmax(scale, -lim), lim);
+  // status 1 (parity unpinned): no canvas, or a canvas that shares no pixel with the frame -- the
+  // reference raises or, through numpy's negative-slice wrap-around, returns a black crop
+  b.empty = b.side <= 0 || max(b.x1, 0) >= min(b.x1 + b.side, W) || max(b.y1, 0) >= min(b.y1 + b.side, H);
+  return b;
+}
+
+template <int C>
+__global__ __launch_bounds__(256) void preprocess_submission_kernel(
+    const uint8_t* __restrict__ frames, int H, int W, const double* __restrict__ bbox, int S,
+    float* __restrict__ images, uint8_t* __restrict__ crops, float* __restrict__ clip_out,
+    int32_t* __restrict__ status) {
+  const int b = blockIdx.z, oy = blockIdx.y, ox = blockIdx.x * 256 + threadIdx.x;
+  const PadBox bx = pad_box(bbox + 4 * b, W, H);
+  if (oy == 0 && blockIdx.x == 0 && threadIdx.x < 4) {
+    const int t = threadIdx.x;
+    clip_out[4 * b + t] = (float)((t & 1 ? bx.y1 : bx.x1) + (t & 2 ? bx.side : 0));
+    if (t == 0 && status) status[b] = bx.empty ? 1 : 0;
+  }
+  if (ox >= S) return;
+  const size_t plane = (size_t)S * S, pix = (size_t)oy * S + ox;
+  float* out = images ? images + (size_t)b * 3 * plane + pix : nullptr;
+  uint8_t* cr = crops ? crops + ((size_t)b * plane + pix) * C : nullptr;
+  if (bx.empty) {
+    if (out) { out[0] = 0.f; out[plane] = 0.f; out[2 * plane] = 0.f; }
+    if (cr) {
+#pragma unroll
+      for (int c = 0; c < C; ++c) cr[c] = 0;
+    }
+    return;
+  }
+  int xs, ys, cx[4], cy[4];
+  cubic_taps(ox, S, bx.side, xs, cx);
+  cubic_taps(oy, S, bx.side, ys, cy);
+  // every load is from a frame pixel (the index clamped into the frame); a tap outside the
+  // frame contributes the canvas's 0 through its zeroed coefficient
+  int col[4];
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    const int x = bx.x1 + min(max(xs + k, 0), bx.side - 1);
+    if (x < 0 || x >= W) cx[k] = 0;
+    col[k] = min(max(x, 0), W - 1);
+  }
+  const uint8_t* fr = frames + (size_t)b * H * W * C;
+  int v[C];
+#pragma unroll
+  for (int c = 0; c < C; ++c) v[c] = 0;
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    const int y = bx.y1 + min(max(ys + j, 0), bx.side - 1);
+    const int wy = (y < 0 || y >= H) ? 0 : cy[j];
+    const uint8_t* rp = fr + (size_t)min(max(y, 0), H - 1) * W * C;
+#pragma unroll
+    for (int c = 0; c < C; ++c) {
+      int hsum = 0;                                // HResizeCubic: int sum of u8 x short
+#pragma unroll
+      for (int k = 0; k < 4; ++k) hsum += (int)rp[col[k] * C + c] * cx[k];
+      v[c] += hsum * wy;                           // VResizeCubic
+    }
+  }
+  const float mean[3] = {0.485f, 0.456f, 0.406f}, stdv[3] = {0.229f, 0.224f, 0.225f};
+  int u8[C];
+#pragma unroll
+  for (int c = 0; c < C; ++c) {
+    u8[c] = min(max((v[c] + (1 << 21)) >> 22, 0), 255);          // FixedPtCast<int, uchar, 22>
+    if (cr) cr[c] = (uint8_t)u8[c];
+  }
+  if (out) {
+#pragma unroll
+    for (int ch = 0; ch < 3; ++ch)
+      out[ch * plane] = ((float)u8[C == 1 ? 0 : ch] / 255.f - mean[ch]) / stdv[ch];
+  }
+}
+
 }  // namespace
+
+int spe_launch_preprocess_submission(const uint8_t* frames, int B, int H, int W, int C, const double* bbox, int S,
+                                     float* images, uint8_t* crops_u8, float* clip_bbox, int32_t* status,
+                                     hipStream_t s) {
+  if (B <= 0) return 0;
+  if (!frames || !bbox || (!images && !crops_u8) || !clip_bbox || H <= 0 || W <= 0 || S <= 0 || (C != 1 && C != 3))
+    return -5;
+  const dim3 grid((S + 255) / 256, S, B);
+  if (C == 1)
+    hipLaunchKernelGGL(preprocess_submission_kernel<1>, grid, dim3(256), 0, s, frames, H, W, bbox, S, images, crops_u8,
+                       clip_bbox, status);
+  else
+    hipLaunchKernelGGL(preprocess_submission_kernel<3>, grid, dim3(256), 0, s, frames, H, W, bbox, S, images, crops_u8,
+                       clip_bbox, status);
+  return (int)hipGetLastError();
+}
 
 int spe_launch_preprocess(const uint8_t* frames, int B, int H, int W, int C, const double* bbox, int S,
                           float* images, float* clip_bbox, int32_t* status, hipStream_t s) {

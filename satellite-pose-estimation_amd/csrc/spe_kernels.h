@@ -238,6 +238,10 @@ int spe_ffn_splits(int M, int F);  // split count spe_launch_ffn_ln would use fo
 
 int spe_launch_preprocess(const uint8_t* frames, int B, int H, int W, int C, const double* bbox, int S,
                           float* images, float* clip_bbox, int32_t* status, hipStream_t s);
+// SpeedSubmission's pad-to-square crop (REV/datasets/speed.py:92-160); images / crops_u8 nullable, not both
+int spe_launch_preprocess_submission(const uint8_t* frames, int B, int H, int W, int C, const double* bbox, int S,
+                                     float* images, uint8_t* crops_u8, float* clip_bbox, int32_t* status,
+                                     hipStream_t s);
 // The model input: the ImageNet-normalised fp32 batch [B][3][S][S] (f32), or the 8-bit crops
 // [B][S][S][ch] (u8, ch = 1 grayscale -- SPEED's frames, Image.convert('RGB') replicating them --
 // or 3 RGB) that to_tensor + Normalize (REV/datasets/speed.py:25-41) turn into it: the pack kernels

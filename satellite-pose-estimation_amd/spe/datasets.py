@@ -10,6 +10,8 @@ csrc/preprocess.hip) and returns the model input and the clip boxes PostProcess 
 Huffman, dequantisation and libjpeg's islow IDCT, bit-exact with Pillow), so a batch can start
 from the JPEG files' bytes in HBM.  The reference's validation-time img_trunc(p=0.2)
 augmentation (:232) is a defect and is not reproduced.
+`SpeedSubmissionTransform` is the same stage of SpeedSubmission (:44-160), the gen_submission
+scripts' dataset: an integer square that is padded with zeros instead of clipped to the frame.
 """
 from __future__ import annotations
 
@@ -59,6 +61,56 @@ class SpeedValTransform:
         _lib.check(_lib.lib().spe_preprocess(_lib.stream_ptr(stream), _lib.ptr(frames), B, H, W, C, _lib.ptr(bb), S,
                                              _lib.ptr(out["images"]), _lib.ptr(out["clip_bbox"]),
                                              _lib.ptr(out["status"])), "spe_preprocess")
+        return out
+
+
+def generate_clip_bbox_submission(bbox):
+    """SpeedSubmission.generate_clip_bbox (REV/datasets/speed.py:92-108) on the host: the integer
+    square [x1, y1, x1 + side, y1 + side] with x1 = int(xc - s/2), y1 = int(yc - s/2), side = int(s),
+    s = 1.2 x the longer box side (fp64; int() truncates towards zero).  Not clipped to the frame:
+    it may be negative or extend past it.  Returns an int64 array."""
+    x1, y1, x2, y2 = (float(v) for v in bbox)
+    scale = max(x2 - x1, y2 - y1) * 1.2
+    xc, yc, h = (x1 + x2) / 2, (y1 + y2) / 2, scale / 2
+    x1, y1, side = int(xc - h), int(yc - h), int(scale)
+    return np.asarray([x1, y1, x1 + side, y1 + side], dtype=np.int64)
+
+
+class SpeedSubmissionTransform:
+    """SpeedSubmission.__getitem__ after the decode (REV/datasets/speed.py:113-160), the dataset of
+    the reference's gen_submission scripts, for a batch of frames in HBM with one HIP launch
+    (spe_preprocess_submission, csrc/preprocess.hip): the integer square of
+    generate_clip_bbox_submission, a side x side zero canvas with the in-frame part of the square
+    copied in (pad, where the validation transform clips), the 8-bit cubic resize and
+    to_tensor + Normalize.  Same call shape as SpeedValTransform; `crops=True` also returns the
+    resized uint8 crops [B,S,S] (grayscale frames) or [B,S,S,3], the model's u8 input, and
+    `images=False` leaves the fp32 batch out.  status 1 (zeros written, parity unpinned): side <= 0
+    or a square that shares no pixel with the frame."""
+
+    def __init__(self, size: int = 416):
+        self.size = int(size)
+
+    def __call__(self, frames: torch.Tensor, bbox_xxyy, out=None, stream=None, crops: bool = False,
+                 images: bool = True):
+        if frames.dtype != torch.uint8 or frames.dim() not in (3, 4) or not frames.is_cuda:
+            raise ValueError("frames must be a device uint8 tensor [B,H,W] or [B,H,W,3]")
+        frames = frames.contiguous()
+        B, H, W = frames.shape[:3]
+        C = 1 if frames.dim() == 3 else frames.shape[3]
+        dev = frames.device
+        bb = torch.as_tensor(bbox_xxyy, dtype=torch.float64).to(dev).contiguous().view(B, 4)
+        S = self.size
+        if out is None:
+            out = {"clip_bbox": torch.empty(B, 4, device=dev),
+                   "status": torch.empty(B, dtype=torch.int32, device=dev)}
+            if images:
+                out["images"] = torch.empty(B, 3, S, S, device=dev)
+            if crops:
+                out["crops"] = torch.empty((B, S, S) if C == 1 else (B, S, S, C), dtype=torch.uint8, device=dev)
+        _lib.check(_lib.lib().spe_preprocess_submission(
+            _lib.stream_ptr(stream), _lib.ptr(frames), B, H, W, C, _lib.ptr(bb), S, _lib.ptr(out.get("images")),
+            _lib.ptr(out.get("crops")), _lib.ptr(out["clip_bbox"]), _lib.ptr(out.get("status"))),
+            "spe_preprocess_submission")
         return out
 
 

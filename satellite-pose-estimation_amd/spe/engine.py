@@ -6,9 +6,15 @@ The criterion (Hungarian matcher + losses, REV/engine.py:99-112) runs on the dev
 (spe.models.SetCriterion) when given; its losses are logged like the reference's
 MetricLogger: per-batch values averaged over batches, weighted ("loss", "loss_ce", ...) and
 "<k>_unscaled", plus "class_error".
+
+generate_submission() is the reference's gen_submission loop (REV/gen_submission_single.py:113-187,
+gen_submission_multi.py:123-186) from the JPEG files' bytes to the {filename: pose} log.
 """
 from __future__ import annotations
 
+import io
+
+import numpy as np
 import torch
 
 from . import _lib
@@ -75,3 +81,79 @@ def evaluate(model, criterion, postprocessors, data_loader, gt_file, solver, dev
     stats = {k: s / max(n, 1) for k, (s, n) in meters.items()}
     stats["speed_eval_pose"] = evaluator.stats
     return stats, evaluator
+
+
+def _host_decode(data, height, width, filename):
+    """Image.open(path).convert('RGB') (REV/datasets/speed.py:116) of one file on the host."""
+    from PIL import Image
+    rgb = np.asarray(Image.open(io.BytesIO(data)).convert("RGB"))
+    if rgb.shape[:2] != (height, width):
+        raise ValueError(f"{filename}: a {rgb.shape[1]}x{rgb.shape[0]} frame in a batch of {width}x{height} frames")
+    return rgb
+
+
+def _batch_frames(files, names, decoder, device):
+    """JPEG bytes of one batch -> device frames uint8 [B,H,W], or [B,H,W,3] when a frame is not gray.
+    The device decoder takes the baseline grayscale files (SPEED's format); a file it refuses
+    (status != 0: colour, progressive, oversized) is decoded with Pillow and its frame uploaded."""
+    from .datasets import JpegDecoder
+    dec = decoder(*JpegDecoder.pack(files, device))
+    frames = dec["frames"]
+    refused = np.nonzero(dec["status"].cpu().numpy())[0]
+    if len(refused) == 0:
+        return frames
+    H, W = frames.shape[1:3]
+    host = {int(i): _host_decode(files[i], H, W, names[i]) for i in refused}
+    gray = all((f[..., 0] == f[..., 1]).all() and (f[..., 0] == f[..., 2]).all() for f in host.values())
+    if not gray:
+        frames = frames[..., None].expand(-1, -1, -1, 3).contiguous()
+    for i, f in host.items():
+        frames[i] = torch.from_numpy(np.array(f[..., 0] if gray else f)).to(device)
+    return frames
+
+
+@torch.no_grad()
+def generate_submission(models, postprocessors, anns, read_file, solver, device, batch_size, input_size,
+                        decoder=None, transform=None):
+    """The reference's gen_submission loop (REV/gen_submission_single.py:113-187; with a list of
+    models, gen_prediction + gen_submission of gen_submission_multi.py:123-186) over SpeedSubmission
+    (REV/datasets/speed.py:44-160), from the files' bytes on.
+
+    anns: the detector's {filename: [[x1, y1, x2, y2, score], ...]} mapping (load_anns, :59-82); the
+    first box of each file is used, in the mapping's order.  read_file(filename) -> the JPEG file's
+    bytes.  Per batch (the last may be short, drop_last=False): JpegDecoder, SpeedSubmissionTransform
+    (u8 crops), the model(s) with the fused PostProcess, one batched solve -- solver.solve_batch, or
+    solver.solve_batch_multi for a list of models (Multi_Mean_PoseSolver) -- and one D2H copy of the
+    pose records.  Returns {filename: {"quat_pr", "tvec_pr"}}, rounded to 6 decimals like the
+    reference; a failed solve (the reference's IndexError / cv2.error) or a status-1 crop gives the
+    zero pose.  `postprocessors` is accepted for the reference's signature: PostProcess runs fused
+    in the model's forward.  decoder / transform default to JpegDecoder() (SPEED's 1920x1200 frames)
+    and SpeedSubmissionTransform(input_size); every frame of a run has the decoder's size."""
+    from .datasets import JpegDecoder, SpeedSubmissionTransform
+    multi = isinstance(models, (list, tuple))
+    if multi and not hasattr(solver, "solve_batch_multi"):
+        raise ValueError("a list of models needs an ensemble solver (Multi_Mean_PoseSolver)")
+    decoder = decoder if decoder is not None else JpegDecoder()
+    transform = transform if transform is not None else SpeedSubmissionTransform(input_size)
+    names = list(anns)
+    log = {}
+    for i0 in range(0, len(names), int(batch_size)):
+        batch = names[i0:i0 + int(batch_size)]
+        bbox = np.asarray([anns[f][0][:4] for f in batch], np.float64)
+        frames = _batch_frames([read_file(f) for f in batch], batch, decoder, device)
+        t = transform(frames, bbox, crops=True, images=False)
+        if multi:
+            outs = [m(t["crops"], clip_bbox=t["clip_bbox"]) for m in models]
+            poses = solver.solve_batch_multi([o["points_px"] for o in outs], [o["probs"] for o in outs])
+        else:
+            o = models(t["crops"], clip_bbox=t["clip_bbox"])
+            poses = solver.solve_batch(o["points_px"], o["probs"], o.get("sigmas"))
+        # failed images carry the zero pose, as in SpeedEval.update_batch: every solver status but OK
+        # and RANSAC_FALLBACK, and here a status-1 crop too
+        st = poses["status"]
+        failed = ((st != _lib.SPE_PNP_OK) & (st != _lib.SPE_PNP_RANSAC_FALLBACK)) | (t["status"] != 0)
+        rec = torch.cat([poses["quat"].double(), poses["tvec"].double(), failed.double()[:, None]], 1).cpu().numpy()
+        for f, r in zip(batch, rec):
+            quat, tvec = (np.zeros(4), np.zeros(3)) if r[7] else (r[0:4], r[4:7])
+            log[f] = {"quat_pr": np.around(quat, decimals=6).tolist(), "tvec_pr": np.around(tvec, decimals=6).tolist()}
+    return log
