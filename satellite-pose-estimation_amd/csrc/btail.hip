@@ -186,7 +186,7 @@ int spe_btail_perm(int k) {
 }
 
 bool spe_btail_enabled() {
-  static const int on = [] { const char* e = getenv("SPE_BTAIL"); return e ? atoi(e) : 1; }();
+  static const int on = spe_env_int("SPE_BTAIL", 1);
   return on != 0;
 }
 

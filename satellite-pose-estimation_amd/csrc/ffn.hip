@@ -596,12 +596,12 @@ int spe_launch_ffn_ln(const FfnArgs& a0, hipStream_t s) {
     a.partial = nullptr;
     // 48 rows per wave (MB = 3, 493 VGPR+AGPR, no spills) measured 9 % faster than 32 (kbench,
     // B = 64 encoder FFN: 0.48 vs 0.53 ms); 64 rows spill.  SPE_FFN_MB overrides for A/B runs.
-    static const int mb = [] { const char* e = getenv("SPE_FFN_MB"); return e ? atoi(e) : 3; }();
-    static const int nst = [] { const char* e = getenv("SPE_FFN_NST"); return e ? atoi(e) : 4; }();
-    static const int pipe = [] { const char* e = getenv("SPE_FFN_PIPE"); return e ? atoi(e) : 1; }();
+    static const int mb = spe_env_int("SPE_FFN_MB", 3);
+    static const int nst = spe_env_int("SPE_FFN_NST", 4);
+    static const int pipe = spe_env_int("SPE_FFN_PIPE", 1);
     // SPE_FFN_SCHED: 0 = compiler-scheduled pipe loop, 3 / 6 / 9 = pinned schedule with that
     // many reads ahead (default 6)
-    static const int sched = [] { const char* e = getenv("SPE_FFN_SCHED"); return e ? atoi(e) : 6; }();
+    static const int sched = spe_env_int("SPE_FFN_SCHED", 6);
     auto main_kernel = [&](int grid) {
       if (sched == 3) hipLaunchKernelGGL((ffn_pipe_kernel<3, true, 3>), dim3(grid), dim3(NT), 0, s, a);
       else if (sched == 9) hipLaunchKernelGGL((ffn_pipe_kernel<3, true, 9>), dim3(grid), dim3(NT), 0, s, a);
@@ -614,7 +614,7 @@ int spe_launch_ffn_ln(const FfnArgs& a0, hipStream_t s) {
       // rounds take 192-row tiles and the rest goes to a second launch of 128-row tiles: the
       // last round then costs ~0.85 of a 192-row round (B = 64 encoder FFN: 0.445 -> 0.427 ms
       // unpinned).  SPE_FFN_TAIL=0 disables it for A/B runs.
-      static const int tail = [] { const char* e = getenv("SPE_FFN_TAIL"); return e ? atoi(e) : 1; }();
+      static const int tail = spe_env_int("SPE_FFN_TAIL", 1);
       const int tiles = (a.M + 191) / 192, ncu = spe_cu_count();
       const int full = ncu > 0 ? tiles / ncu * ncu : 0, rest = a.M - full * 192;
       if (tail && full > 0 && rest > 0 && (rest + 127) / 128 <= ncu) {

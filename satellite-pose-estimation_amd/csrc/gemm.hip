@@ -687,7 +687,7 @@ int launch_x6_geo(const GemmArgs& g, int mode, hipStream_t s) {
 // tile geometry: SPE_X6_TILE = 128 (default: 3-9 % faster than 256 across the bench shapes,
 // scripts/x6_bench.py) or 256
 int launch_x6(const GemmArgs& g, int mode, hipStream_t s) {
-  static const int tile = [] { const char* e = getenv("SPE_X6_TILE"); return e ? atoi(e) : 128; }();
+  static const int tile = spe_env_int("SPE_X6_TILE", 128);
   return tile == 128 ? launch_x6_geo<128>(g, mode, s) : launch_x6_geo<256>(g, mode, s);
 }
 
@@ -947,7 +947,7 @@ __global__ __launch_bounds__(D6_NT, 2) void gemm_x6d_conv_pl_n64(GemmArgs g) { g
 
 // 1 = not a problem for the DMA kernel
 int launch_x6d(const GemmArgs& g, int mode, hipStream_t s) {
-  static const int en = [] { const char* e = getenv("SPE_X6_DMA"); return e ? atoi(e) : 1; }();
+  static const int en = spe_env_int("SPE_X6_DMA", 1);
   if (!en || !g.B6 || (mode != GEMM_LINEAR && mode != GEMM_CONV) || (g.lda & 3)) return 1;
   const bool pl = mode == GEMM_CONV && (g.Cin & 31);      // per-lane tap decode (stem)
   if (pl ? ((g.Cin & 3) || (g.K & 3) || g.K != g.Cin * g.KH * g.KW) : (g.K & 31)) return 1;
@@ -960,7 +960,7 @@ int launch_x6d(const GemmArgs& g, int mode, hipStream_t s) {
     return 1;
   }
   // N <= 64: the 128 x 64 tile (SPE_X6_N64=0 keeps 128 x 128)
-  static const int n64 = [] { const char* e = getenv("SPE_X6_N64"); return e ? atoi(e) : 1; }();
+  static const int n64 = spe_env_int("SPE_X6_N64", 1);
   const bool narrow = n64 && g.N <= 64;
   const int bn = narrow ? 64 : 128;
   const int tiles = ((g.M + D6_BM - 1) / D6_BM) * ((g.N + bn - 1) / bn);

@@ -697,7 +697,7 @@ int launch_bn(const GemmArgs& g, int mode, hipStream_t s) {
   // SPE_GEMM2_PIN=0: residual-free convs on the compiler-scheduled loop (A/B knob).  The other
   // convs and linear problems stage with global_load_lds (buffer-load staging without the pinned
   // schedule measured neutral, 4806 vs 4786 img/s, and was removed)
-  static const int pin = [] { const char* e = getenv("SPE_GEMM2_PIN"); return e ? atoi(e) : 1; }();
+  static const int pin = spe_env_int("SPE_GEMM2_PIN", 1);
   constexpr long long LIM = (1ll << 31) - (1 << 20);          // 32-bit buffer offsets
   const bool bfits = (long long)g.N * g.ldb * 2 < LIM;
   if (mode == GEMM_CONV) {
@@ -740,7 +740,7 @@ int launch_st1(const GemmArgs& g, hipStream_t s) {
 // (0.129 -> 0.138) and stays on the two-stage kernel.  SPE_GEMM_ST1_K overrides the K bound
 // (0 disables) for A/B runs.
 int st1_max_k() {
-  static const int v = [] { const char* e = getenv("SPE_GEMM_ST1_K"); return e ? atoi(e) : 256; }();
+  static const int v = spe_env_int("SPE_GEMM_ST1_K", 256);
   return v;
 }
 bool use_st1(const GemmArgs& g, int mode) {

@@ -307,7 +307,7 @@ int spe_cu_count() {
 namespace {
 
 bool sgemm_enabled() {
-  static const bool on = [] { const char* e = getenv("SPE_SGEMM"); return !e || atoi(e) != 0; }();
+  static const bool on = spe_env_int("SPE_SGEMM", 1) != 0;
   return on;
 }
 
@@ -342,7 +342,7 @@ int launch_kbn(const GemmArgs& g, hipStream_t s) {
 int spe_launch_sgemm(const GemmArgs& g, int mode, hipStream_t s) {
   if (mode == GEMM_CONV && sgemm_enabled()) {
     // the pair-packed stem (see CP): 7x8 window, 4 channels, pre-bordered input, N = 64
-    static const int on = [] { const char* e = getenv("SPE_SG_STEM"); return e ? atoi(e) : 1; }();
+    static const int on = spe_env_int("SPE_SG_STEM", 1);
     if (on && g.Cin == 4 && g.KH == 7 && g.KW == 8 && g.pad == 0 && g.K == 224 && g.ldb == 256 && g.N == 64 &&
         !g.R && !g.ln_g && g.vt_T == 0 && g.act <= ACT_RELU && !g.res_post && !g.out_f32 && g.ldc % 4 == 0 &&
         (g.Ho - 1) * g.stride + 8 <= g.H && (g.Wo - 1) * g.stride + 8 <= g.W)

@@ -140,7 +140,7 @@ __global__ __launch_bounds__(NT, 1) void lnproj_kernel(GemmArgs g, int row_tiles
 
 // bf16, K = N = 256, residual + LayerNorm, no activation (SPE_LNPROJ=0 disables it)
 bool spe_lnproj_applies(const GemmArgs& g) {
-  static const int on = [] { const char* e = getenv("SPE_LNPROJ"); return e ? atoi(e) : 1; }();
+  static const int on = spe_env_int("SPE_LNPROJ", 1);
   return on && g.M > 0 && g.K == D && g.N == D && g.ln_g && g.ln_b && g.R && !g.act && !g.res_post && !g.out_f32 &&
          !g.out_f16 && g.vt_T == 0 && g.r_period == 0 && !g.P && g.lda % 8 == 0 && g.ldb >= D && g.ldc % 4 == 0 &&
          g.ldr % 4 == 0;

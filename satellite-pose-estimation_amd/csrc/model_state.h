@@ -1,4 +1,4 @@
-// Internal state of a spe_model (shared by registry.cpp and forward.cpp).
+// Internal state of a spe_model (shared by registry.cpp, forward.cpp, launch.cpp and rtdetr_model.cpp).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -8,6 +8,7 @@
 #include <vector>
 
 #include "../../include/spe.h"
+#include "spe_common.h"
 #include "spe_kernels.h"
 
 struct Conv {              // conv / linear packed as [N][Kpad] in T, bias fp32
@@ -178,7 +179,7 @@ int64_t spe_rtdetr_workspace(const spe_model* m, int B);
 // Q > 12 keeps the projected K / V^T and the exact-f32 attention.  SPE_XATTN_H3=0: that path for
 // every Q (A/B runs).
 inline bool spe_use_xattn(const spe_model* m) {
-  static const bool h3 = [] { const char* e = getenv("SPE_XATTN_H3"); return e ? atoi(e) != 0 : true; }();
+  static const bool h3 = spe_env_int("SPE_XATTN_H3", 1) != 0;
   const auto& c = m->cfg;
   return (c.dtype == SPE_DTYPE_BF16_ || (h3 && m->h3 && 8 * c.num_queries <= 96)) && c.hidden_dim == 256 &&
          c.nheads == 8 && c.dim_feedforward % 32 == 0 && c.enc_layers > 0;

@@ -1,0 +1,147 @@
+// C entry points of the native runtime outside the model's forward pass (include/spe.h): the set
+// criterion, ensemble fusion, pre- and post-processing, the batched solver, its self-assessment and the
+// SPEED score.  No allocation or synchronisation happens inside spe_pnp_batch / spe_speed_score once the
+// per-stream scratch has its size, so a caller may capture them into a hipGraph.
+#include <hip/hip_runtime.h>
+
+#include <map>
+#include <mutex>
+#include <tuple>
+
+#include "launch.h"
+#include "model_state.h"
+#include "spe_pnp.h"
+
+#define fail spe_fail
+
+// Device scratch of the solver's RANSAC hypothesis records and the criterion's per-image partial
+// sums: one buffer per (device, stream, kind), grown on demand and kept for the process lifetime,
+// so steady-state calls allocate nothing (a first call with a larger batch allocates and must
+// therefore happen outside graph capture).  Keying by stream is what makes concurrent calls safe:
+// calls on one stream are ordered by the stream, calls on different streams never share records.
+// A stream handle that is destroyed while its work is pending and then reissued by the runtime
+// would inherit the buffer; callers keep solver streams alive for as long as they use them.
+static void* stream_scratch(hipStream_t stream, int kind, size_t bytes) {
+  static std::mutex mu;
+  static std::map<std::tuple<int, hipStream_t, int>, std::pair<void*, size_t>> bufs;
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess) return nullptr;
+  std::lock_guard<std::mutex> g(mu);
+  auto& e = bufs[std::make_tuple(dev, stream, kind)];
+  if (e.second < bytes) {
+    // the old buffer may still be read by work queued on this stream: free it in stream order
+    if (e.first) {
+      if (hipStreamSynchronize(stream) != hipSuccess) return nullptr;
+      (void)hipFree(e.first);
+    }
+    e.first = nullptr;
+    e.second = 0;
+    if (hipMalloc(&e.first, bytes) != hipSuccess) return nullptr;
+    e.second = bytes;
+  }
+  return e.first;
+}
+enum { SCRATCH_CRITERION = 0, SCRATCH_HYP = 1 };
+
+extern "C" {
+
+int spe_criterion(void* stream, const float* logits, const float* points, const int32_t* tgt_labels,
+                  const float* tgt_points, int layers, int batch, int num_queries, int num_classes, int num_targets,
+                  float cost_class, float cost_pts, float eos_coef, double num_points, int32_t* match, double* losses) {
+  if (!logits || !points || !tgt_labels || !tgt_points || !match || !losses || layers < 1 || batch < 0 ||
+      num_queries < 1 || num_queries > 64 || num_targets < 1 || num_targets > 32 || num_targets > num_queries ||
+      num_classes < 2 || num_classes > 32 || !(num_points > 0))
+    return fail(SPE_E_ARG, "bad argument");
+  CritArgs a{logits, points, tgt_labels, tgt_points, layers, batch, num_queries, num_classes, num_targets,
+             cost_class, cost_pts, eos_coef, num_points, match, nullptr, losses};
+  if (batch > 0) {
+    a.partial = (double*)stream_scratch((hipStream_t)stream, SCRATCH_CRITERION, (size_t)layers * batch * 5 * sizeof(double));
+    if (!a.partial) return fail(SPE_E_LAUNCH, "criterion scratch allocation failed");
+  }
+  CK(spe_launch_criterion(a, (hipStream_t)stream));
+  return 0;
+}
+
+int spe_ensemble_fuse(void* stream, const float* points_px, const float* probs, int models, int batch,
+                      int num_queries, int num_classes, float* fused_points, float* fused_probs) {
+  if (!points_px || !probs || !fused_points || !fused_probs || models < 1 || batch < 0 || num_queries < 1 ||
+      num_classes < 2 || num_classes > 17 || (int64_t)models * num_queries > 256)
+    return fail(SPE_E_ARG, "bad argument");
+  EnsembleArgs a{points_px, probs, models, batch, num_queries, num_classes, fused_points, fused_probs};
+  CK(spe_launch_ensemble_fuse(a, (hipStream_t)stream));
+  return 0;
+}
+
+int spe_preprocess(void* stream, const uint8_t* frames, int batch, int height, int width, int channels,
+                   const double* bbox_xxyy, int size, float* images, float* clip_bbox, int32_t* status) {
+  if (!frames || !bbox_xxyy || !images || !clip_bbox || batch < 0 || height <= 0 || width <= 0 || size <= 0 ||
+      (channels != 1 && channels != 3))
+    return fail(SPE_E_ARG, "bad argument");
+  CK(spe_launch_preprocess(frames, batch, height, width, channels, bbox_xxyy, size, images, clip_bbox, status,
+                           (hipStream_t)stream));
+  return 0;
+}
+
+int spe_preprocess_submission(void* stream, const uint8_t* frames, int batch, int height, int width, int channels,
+                              const double* bbox_xxyy, int size, float* images, uint8_t* crops_u8, float* clip_bbox,
+                              int32_t* status) {
+  if (!frames || !bbox_xxyy || (!images && !crops_u8) || !clip_bbox || batch < 0 || height <= 0 || width <= 0 ||
+      size <= 0 || (channels != 1 && channels != 3))
+    return fail(SPE_E_ARG, "bad argument");
+  CK(spe_launch_preprocess_submission(frames, batch, height, width, channels, bbox_xxyy, size, images, crops_u8,
+                                      clip_bbox, status, (hipStream_t)stream));
+  return 0;
+}
+
+int spe_postprocess(void* stream, const float* logits, const float* points, const float* clip_bbox, int B, int Q,
+                    float* probs, float* points_px) {
+  if (!logits || !points || !clip_bbox || !probs || !points_px || B < 0 || Q <= 0) return fail(SPE_E_ARG, "bad argument");
+  CK(spe_launch_postprocess(logits, points, clip_bbox, B, Q, probs, points_px, (hipStream_t)stream));
+  return 0;
+}
+
+int spe_pnp_batch(void* stream, const float* points_px, const float* probs, const float* sigmas, int B, int Q, int C,
+                  const double* K, const double* world, int mode, float repro, int ransac_iters, double confidence,
+                  float* quat, double* tvec, double* rvec, int32_t* status, int32_t* n_corr, int32_t* corr_label,
+                  uint32_t* inlier_mask, const float* repro_per_image) {
+  if (!points_px || !probs || !K || !world || !quat || !tvec || B < 0 || Q <= 0 || Q > 64 || C < 2 || C > 17)
+    return fail(SPE_E_ARG, "bad argument");
+  if (mode < SPE_PNP_EPNP || mode > SPE_PNP_EPNP_CERES) return fail(SPE_E_ARG, "bad solver mode");
+  if (ransac_iters < 1 || ransac_iters > 255 || !(confidence > 0 && confidence < 1))
+    return fail(SPE_E_ARG, "ransac_iters must be in [1,255], confidence in (0,1)");
+  PnpArgs a{};
+  a.points = points_px; a.probs = probs; a.sigmas = sigmas;
+  a.B = B; a.Q = Q; a.C = C; a.K = K; a.world = world; a.mode = mode; a.repro = repro;
+  a.repro_img = repro_per_image;
+  a.ransac_iters = ransac_iters; a.confidence = confidence;
+  a.quat = quat; a.tvec = tvec; a.rvec = rvec; a.status = status; a.n_corr = n_corr;
+  a.corr_label = corr_label; a.inlier_mask = inlier_mask;
+  if (mode == SPE_PNP_EPNP_RANSAC_SIGMA && B > 0) {
+    a.hyp = (HypRec*)stream_scratch((hipStream_t)stream, SCRATCH_HYP, (size_t)B * ransac_iters * sizeof(HypRec));
+    a.hyp_stride = ransac_iters;
+    if (!a.hyp) return fail(SPE_E_LAUNCH, "hypothesis scratch allocation failed");
+  }
+  CK(spe_launch_pnp(a, (hipStream_t)stream));
+  return 0;
+}
+
+int spe_self_assess(void* stream, const float* probs, const float* sigmas, const int32_t* status,
+                    const int32_t* corr_label, const uint32_t* inlier_mask, int B, int Q, int C, float score_th,
+                    float sigma_th, int min_inliers, float* mean_sigma, int32_t* n_confident, uint8_t* reliable) {
+  if (!probs || !sigmas || !status || !corr_label || !inlier_mask || !mean_sigma || !n_confident || !reliable || B < 0 ||
+      Q <= 0 || Q > 64 || C < 2 || C > 17 || min_inliers < 0)
+    return fail(SPE_E_ARG, "bad argument");
+  SelfAssessArgs a{probs, sigmas, status, corr_label, inlier_mask, B, Q, C, score_th, sigma_th, min_inliers,
+                   mean_sigma, n_confident, reliable};
+  CK(spe_launch_self_assess(a, (hipStream_t)stream));
+  return 0;
+}
+
+int spe_speed_score(void* stream, const float* quat, const double* tvec, const double* q_gt, const double* t_gt, int B,
+                    double* s_t, double* s_q) {
+  if (!quat || !tvec || !q_gt || !t_gt || !s_t || !s_q || B < 0) return fail(SPE_E_ARG, "bad argument");
+  CK(spe_launch_score(quat, tvec, q_gt, t_gt, B, s_t, s_q, (hipStream_t)stream));
+  return 0;
+}
+
+}  // extern "C"

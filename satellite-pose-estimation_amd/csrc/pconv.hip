@@ -308,7 +308,7 @@ int launch_pc(const GemmArgs& g, const PcGeom& geo, hipStream_t s) {
 
 // 1 = not a problem for this kernel (the caller takes gemm2 / gemm)
 int spe_launch_pconv(const GemmArgs& g, hipStream_t s) {
-  static const int en = [] { const char* e = getenv("SPE_PCONV"); return e ? atoi(e) : 1; }();
+  static const int en = spe_env_int("SPE_PCONV", 1);
   if (!en) return 1;
   if (g.KH != 3 || g.KW != 3 || g.stride != 1 || g.pad != 1 || g.Ho != g.H || g.Wo != g.W) return 1;
   if (g.Cin % 64 || g.N % 64 || g.R || g.act > ACT_RELU || g.res_post || g.out_f32 || g.vt_T > 0 || g.ln_g) return 1;

@@ -362,7 +362,7 @@ float* upload_transposed(spe_model* m, const std::string& k, int out, int in) {
 }
 
 bool spe_use_neckfold(const spe_model* m) {
-  static const int on = [] { const char* e = getenv("SPE_NECK_FOLD"); return e ? atoi(e) : 1; }();
+  static const int on = spe_env_int("SPE_NECK_FOLD", 1);
   return on && (m->cfg.dtype == SPE_DTYPE_BF16_ || m->x3);
 }
 
@@ -440,7 +440,7 @@ int build_device(spe_model* m) {
   const auto& c = m->cfg;
   const int d = c.hidden_dim, ff = c.dim_feedforward, Q = c.num_queries;
   const std::string b = "backbone.0.body";
-  static const int stem_pairs = [] { const char* e = getenv("SPE_STEM_PAIRS"); return e ? atoi(e) : 1; }();
+  static const int stem_pairs = spe_env_int("SPE_STEM_PAIRS", 1);
   if (m->esz == 2 && stem_pairs) {
     // bf16: the pair-packed stem (SPE_STEM_PAIRS=0: the 8-channel tap-major stem, A/B knob).  The 7x7/s2/p3 conv over 3 channels runs as a 7x8/s2 conv
     // over the zero-bordered 4-channel input (spe_launch_pack_input_pad4): k = (kh*8 + kw)*4 + ci,

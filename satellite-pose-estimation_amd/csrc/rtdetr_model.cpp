@@ -273,16 +273,6 @@ RtWs rt_plan(const spe_model* m, int B) {
   return w;
 }
 
-#define CK(x)                                                                         \
-  do {                                                                                \
-    int _r = (x);                                                                     \
-    if (_r != 0) {                                                                    \
-      char _b[256];                                                                   \
-      snprintf(_b, sizeof _b, "%s failed (%d) at %s:%d", #x, _r, __FILE__, __LINE__);  \
-      return fail(_r < 0 ? SPE_E_LAUNCH : _r, _b);                                    \
-    }                                                                                 \
-  } while (0)
-
 }  // namespace
 
 int spe_rtdetr_build_device(spe_model* m) {
@@ -444,10 +434,6 @@ int spe_rtdetr_forward(spe_model* m, void* stream, const float* images, int B, v
   const int BQ = B * Q, h = c.csp_hidden;
   char* ws = (char*)workspace;
   auto P = [&](size_t o) { return (void*)(ws + o); };
-  auto ln = [&](const char* kind, const void* x, const float* g, const float* b, void* y, float* y32, int M) {
-    return run_other(m, kind, 0.0, (double)M * d * 2 * E, s,
-                     [&] { return spe_launch_layernorm(x, g, b, y, y32, M, d, dt, s); });
-  };
 
   // conv as an implicit GEMM, or a plain GEMM over NHWC rows when it is 1x1 / stride 1; the
   // residual R (same row layout as the output) is added before the activation
@@ -537,14 +523,14 @@ int spe_rtdetr_forward(spe_model* m, void* stream, const float* images, int B, v
     GemmArgs go = linear_args(r.ao, P(w.aao), d, M, P(w.atmp), d);
     go.R = P(w.aout); go.ldr = d;
     CK(run_gemm(m, "rt.aifi.o", go, GEMM_LINEAR, s));
-    CK(ln("rt.ln", P(w.atmp), r.an1g, r.an1b, P(w.aout), nullptr, M));
+    CK(run_layernorm(m, "rt.ln", P(w.atmp), r.an1g, r.an1b, P(w.aout), nullptr, M, d, dt, s));
     GemmArgs g1 = linear_args(r.al1, P(w.aout), d, M, P(w.affn), c.enc_ff);
     g1.act = ACT_GELU;
     CK(run_gemm(m, "rt.aifi.ffn", g1, GEMM_LINEAR, s));
     GemmArgs g2 = linear_args(r.al2, P(w.affn), c.enc_ff, M, P(w.atmp), d);
     g2.R = P(w.aout); g2.ldr = d;
     CK(run_gemm(m, "rt.aifi.ffn", g2, GEMM_LINEAR, s));
-    CK(ln("rt.ln", P(w.atmp), r.an2g, r.an2b, P(w.aout), nullptr, M));
+    CK(run_layernorm(m, "rt.ln", P(w.atmp), r.an2g, r.an2b, P(w.aout), nullptr, M, d, dt, s));
   }
   // CSPRepLayer over a [rows][512] concat: conv1 / conv2 (1x1 + BN + SiLU), RepVGG 3x3 + SiLU + x2,
   // conv3 (1x1 + BN + SiLU) when hidden != 256
@@ -608,7 +594,7 @@ int spe_rtdetr_forward(spe_model* m, void* stream, const float* images, int B, v
       CK(run_gemm(m, "rt.dec.enc_out", gf, GEMM_LINEAR, s));
     } else {
       CK(run_gemm(m, "rt.dec.enc_out", g, GEMM_LINEAR, s));
-      CK(ln("rt.ln", P(w.omem), r.eo_g, r.eo_b, P(w.omem), nullptr, ML));
+      CK(run_layernorm(m, "rt.ln", P(w.omem), r.eo_g, r.eo_b, P(w.omem), nullptr, ML, d, dt, s));
     }
   }
   {
@@ -688,7 +674,7 @@ int spe_rtdetr_forward(spe_model* m, void* stream, const float* images, int B, v
     GemmArgs go = linear_args(e.so, P(w.dao), d, BQ, P(w.dtmp), d);
     go.R = P(tgt); go.ldr = d;
     CK(run_gemm(m, "rt.gemm.dec", go, GEMM_LINEAR, s));
-    CK(ln("rt.ln", P(w.dtmp), e.n1g, e.n1b, P(w.t1d), nullptr, BQ));
+    CK(run_layernorm(m, "rt.ln", P(w.dtmp), e.n1g, e.n1b, P(w.t1d), nullptr, BQ, d, dt, s));
     // multi-scale deformable cross-attention, query = tgt + qpos
     GemmArgs gs = linear_args(e.soaw, P(w.t1d), d, BQ, P(w.soaw), e.soaw.N);
     gs.P = P(w.qpos); gs.ldp = d; gs.prow = BQ; gs.out_f32 = 1;
@@ -707,7 +693,7 @@ int spe_rtdetr_forward(spe_model* m, void* stream, const float* images, int B, v
     GemmArgs gc = linear_args(e.oproj, P(w.dcr), d, BQ, P(w.dtmp), d);
     gc.R = P(w.t1d); gc.ldr = d;
     CK(run_gemm(m, "rt.gemm.dec", gc, GEMM_LINEAR, s));
-    CK(ln("rt.ln", P(w.dtmp), e.n2g, e.n2b, P(w.t2d), nullptr, BQ));
+    CK(run_layernorm(m, "rt.ln", P(w.dtmp), e.n2g, e.n2b, P(w.t2d), nullptr, BQ, d, dt, s));
     // FFN (ReLU) + norm3
     GemmArgs g1 = linear_args(e.l1, P(w.t2d), d, BQ, P(w.dffn), c.dec_ff);
     g1.act = ACT_RELU;
@@ -716,7 +702,7 @@ int spe_rtdetr_forward(spe_model* m, void* stream, const float* images, int B, v
     g2.R = P(w.t2d); g2.ldr = d;
     CK(run_gemm(m, "rt.gemm.dec", g2, GEMM_LINEAR, s));
     tgt = (tgt == w.tgt) ? w.t1d : w.tgt;          // t1d is free again once the FFN residual is read
-    CK(ln("rt.ln", P(w.dtmp), e.n3g, e.n3b, P(tgt), (float*)P(w.hs), BQ));
+    CK(run_layernorm(m, "rt.ln", P(w.dtmp), e.n3g, e.n3b, P(tgt), (float*)P(w.hs), BQ, d, dt, s));
     // heads: score, refined points sigmoid(box MLP + inverse_sigmoid(ref)), sigma (+ PostProcess)
     RtHeadArgs ha{};
     ha.pt_add = ref; ha.pt_add_invsig = 1;

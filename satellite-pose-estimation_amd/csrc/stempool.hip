@@ -197,7 +197,7 @@ bool geom(int S, SpGeom& p) {
 }  // namespace
 
 bool spe_stempool_enabled() {
-  static const int on = [] { const char* e = getenv("SPE_STEMPOOL"); return e ? atoi(e) : 1; }();
+  static const int on = spe_env_int("SPE_STEMPOOL", 1);
   return on != 0;
 }
 

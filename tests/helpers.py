@@ -41,3 +41,95 @@ def solver_stress_set(B, seed=0, Q=11, C=12, noise=2.0, outlier_frac=0.1, degene
             p[idx] += rng.uniform(-400, 400, (nout, 2))
         pts[b] = p.astype(np.float32)
     return pts, probs, qs, ts, sig
+
+
+# ---- launch tables (tests/test_gpu_launch_table.py, scripts/gen_golden_launch_tables.py)
+def launch_table(model, call):
+    """Run `call()` with `model`'s per-launch profiler on (spe_model_profile_*): the launches it made,
+    in issue order, as [[kind, flops, bytes], ...]."""
+    import ctypes
+
+    import torch
+
+    from spe import _lib
+    L = _lib.lib()
+    _lib.check(L.spe_model_profile_begin(model._h, b""), "spe_model_profile_begin")
+    try:
+        call()
+        torch.cuda.synchronize()
+    finally:
+        n = L.spe_model_profile_end(model._h)
+    rows = []
+    kb = ctypes.create_string_buffer(64)
+    ms, fl, by = ctypes.c_double(), ctypes.c_double(), ctypes.c_double()
+    for i in range(n):
+        _lib.check(L.spe_model_profile_get(model._h, i, kb, 64, ctypes.byref(ms), ctypes.byref(fl), ctypes.byref(by)),
+                   "spe_model_profile_get")
+        rows.append([kb.value.decode(), fl.value, by.value])
+    return rows
+
+
+# DETR cases: goldens whose configs the parity tests run in every mode (Q = 11: the xattn, xtail and
+# fp32h3-xattn branches; Q = 30: the projected-K/V branch in fp32h3), crossed with every numeric mode
+LAUNCH_TABLE_TAGS = ["s128_q11_l2", "s224_q30_l4"]
+LAUNCH_TABLE_MODES = {"bf16": ("bf16", None), "bf16_attn_fp16": ("bf16", "fp16"), "fp32": ("fp32", None),
+                      "fp32x3": ("fp32x3", None), "fp32x6": ("fp32x6", None), "fp32h3": ("fp32h3", None)}
+# s128_q11_l2 in bf16 and fp32h3, also: encode then decode as two calls (their tables concatenated), the
+# 8-bit crop entry, and a call that fills the aux outputs
+LAUNCH_TABLE_VARIANTS = ["split", "u8", "aux"]
+LAUNCH_TABLE_RTDETR = "rtdetr_r18_s128-fp32"
+
+
+def launch_table_cases():
+    """Case names of tests/golden/launch_tables.json."""
+    names = [f"{t}-{m}" for t in LAUNCH_TABLE_TAGS for m in LAUNCH_TABLE_MODES]
+    names += [f"s128_q11_l2-{m}-{v}" for m in ("bf16", "fp32h3") for v in LAUNCH_TABLE_VARIANTS]
+    return names + [LAUNCH_TABLE_RTDETR]
+
+
+_lt_models = {}
+
+
+def run_launch_table_case(name, dev):
+    """The launch table of one case: weights, batch and seeds as the parity tests take them from the golden."""
+    import json
+    import os
+
+    import torch
+
+    from spe.config import SpeConfig
+    from spe.synthetic import random_weights, synthetic_batch
+    golden = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
+    if name == LAUNCH_TABLE_RTDETR:
+        from spe.rtdetr import RTDETR
+        from spe.rtdetr_spec import RtdetrConfig, random_rtdetr_weights
+        g = np.load(os.path.join(golden, "rtdetr_r18_s128.npz"))
+        cfg = RtdetrConfig(**json.loads(str(g["config"])))
+        if name not in _lt_models:
+            _lt_models[name] = RTDETR(cfg, "fp32")
+            _lt_models[name].load_state_dict(random_rtdetr_weights(cfg, int(g["weight_seed"])))
+        m = _lt_models[name]
+        b = synthetic_batch(SpeConfig(input_size=cfg.input_size), int(g["batch"]), int(g["image_seed"]))
+        img = torch.from_numpy(b["images"]).to(dev)
+        clip = torch.from_numpy(g["clip_bbox"]).float().to(dev)
+        return launch_table(m, lambda: m(img, clip_bbox=clip))
+    tag, mode, variant = (name.split("-") + [None])[:3]
+    from spe.models import DETR
+    g = np.load(os.path.join(golden, f"model_{tag}.npz"))
+    cfg = SpeConfig(**json.loads(str(g["config"])))
+    dtype, attn_dtype = LAUNCH_TABLE_MODES[mode]
+    key = (tag, mode, variant == "aux")
+    if key not in _lt_models:
+        _lt_models[key] = DETR(cfg, dtype=dtype, aux_loss=variant == "aux", attn_dtype=attn_dtype)
+        _lt_models[key].load_state_dict(random_weights(cfg, int(g["weight_seed"])))
+    m = _lt_models[key]
+    B = int(g["batch"])
+    b = synthetic_batch(cfg, B, int(g["image_seed"]))
+    img = torch.from_numpy(b["crops_u8"] if variant == "u8" else b["images"]).to(dev)
+    clip = torch.from_numpy(b["clip_bbox"]).float().to(dev)
+    if variant == "split":
+        ws = m.workspace(B, dev)
+        return launch_table(m, lambda: m.encode(img, ws)) + launch_table(m, lambda: m.decode(B, ws, clip_bbox=clip))
+    if variant == "aux":
+        assert cfg.dec_layers > 1
+    return launch_table(m, lambda: m(img, clip_bbox=clip))
