@@ -240,6 +240,26 @@ int spe_criterion(void* stream, const float* logits, const float* points, const 
                   const float* tgt_points, int layers, int batch, int num_queries, int num_classes, int num_targets,
                   float cost_class, float cost_pts, float eos_coef, double num_points, int32_t* match, double* losses);
 
+/* The UNC RT-DETR SetCriterion.forward with its HungarianMatcher (UNC/src/zoo/rtdetr/
+ * rtdetr_criterion.py:280-337, matcher.py:53-117) for `layers` outputs (the main output first,
+ * then aux_outputs in order), the logging half of UNC/solver/speed_engine.py:145-173.  Device
+ * pointers: logits [L,B,Q,C], points [L,B,Q,2], log_sigmas [L,B,Q,2] (pred_sigmas),
+ * layer_has_sigma int32 [L] (0: the layer has no sigma and scores with s = 0, like the encoder
+ * top-k entry; log_sigmas may be NULL when every flag is 0), tgt_labels int32 [B,T] (a label
+ * outside [0,C) counts as class C-1), tgt_points [B,T,2] (crop-normalised), match int32 [L,B,T]
+ * (query matched to each target), losses fp64 [L,6] = loss_ce, class_error, cardinality_error,
+ * loss_bbox (points: sum |p - t| / num_boxes), loss_bbox (points_uncert: sum (|p - t| exp(-s) +
+ * 0.5 s) / num_boxes), points_different (sum (p - t)), all unweighted.  Matching cost
+ * cost_bbox * L1 - cost_class * prob[label] with prob = sigmoid(logit) when sigmoid_cost (the
+ * speed configs' use_focal_loss), else softmax.  num_boxes: the plain target count (> 0).
+ * Q <= 64, T <= min(Q, 32), C <= 64, else SPE_E_ARG before any launch.  Like spe_criterion it
+ * neither allocates nor synchronises once its per-stream scratch has the batch's size. */
+int spe_criterion_sigma(void* stream, const float* logits, const float* points, const float* log_sigmas,
+                        const int32_t* layer_has_sigma, const int32_t* tgt_labels, const float* tgt_points,
+                        int layers, int batch, int num_queries, int num_classes, int num_targets,
+                        float cost_class, float cost_bbox, int sigmoid_cost, float eos_coef, double num_boxes,
+                        int32_t* match, double* losses);
+
 /* Multi-checkpoint ensemble front end (Multi_Mean_PoseSolver, REV/utils/speed_eval.py:42-100;
  * REV/gen_submission_multi.py:145-186): fuses M models' PostProcess outputs per image -- labels
  * in first-seen order, per label the mean of its points after the 3-sigma filter -- into

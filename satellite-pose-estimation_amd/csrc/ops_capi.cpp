@@ -41,7 +41,7 @@ static void* stream_scratch(hipStream_t stream, int kind, size_t bytes) {
   }
   return e.first;
 }
-enum { SCRATCH_CRITERION = 0, SCRATCH_HYP = 1 };
+enum { SCRATCH_CRITERION = 0, SCRATCH_HYP = 1, SCRATCH_CRITERION_SIGMA = 2 };
 
 extern "C" {
 
@@ -59,6 +59,27 @@ int spe_criterion(void* stream, const float* logits, const float* points, const 
     if (!a.partial) return fail(SPE_E_LAUNCH, "criterion scratch allocation failed");
   }
   CK(spe_launch_criterion(a, (hipStream_t)stream));
+  return 0;
+}
+
+int spe_criterion_sigma(void* stream, const float* logits, const float* points, const float* log_sigmas,
+                        const int32_t* layer_has_sigma, const int32_t* tgt_labels, const float* tgt_points,
+                        int layers, int batch, int num_queries, int num_classes, int num_targets,
+                        float cost_class, float cost_bbox, int sigmoid_cost, float eos_coef, double num_boxes,
+                        int32_t* match, double* losses) {
+  if (!logits || !points || (log_sigmas && !layer_has_sigma) || !tgt_labels || !tgt_points || !match || !losses ||
+      layers < 1 || batch < 0 || num_queries < 1 || num_queries > 64 || num_targets < 1 || num_targets > 32 ||
+      num_targets > num_queries || num_classes < 2 || num_classes > 64 || !(num_boxes > 0))
+    return fail(SPE_E_ARG, "bad argument");
+  CritSigmaArgs a{logits, points, log_sigmas, layer_has_sigma, tgt_labels, tgt_points, layers, batch, num_queries,
+                  num_classes, num_targets, cost_class, cost_bbox, sigmoid_cost != 0, eos_coef, num_boxes, match,
+                  nullptr, losses};
+  if (batch > 0) {
+    a.partial = (double*)stream_scratch((hipStream_t)stream, SCRATCH_CRITERION_SIGMA,
+                                        spe_criterion_sigma_partial_bytes(layers, batch));
+    if (!a.partial) return fail(SPE_E_LAUNCH, "criterion scratch allocation failed");
+  }
+  CK(spe_launch_criterion_sigma(a, (hipStream_t)stream));
   return 0;
 }
 

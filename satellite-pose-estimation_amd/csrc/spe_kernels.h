@@ -311,6 +311,28 @@ struct CritArgs {
 };
 int spe_launch_criterion(const CritArgs& a, hipStream_t s);
 
+// UNC RT-DETR set criterion (criterion_sigma.hip): sigmoid / softmax matching cost, the L1 and the
+// uncertainty point loss for L layers of B images.
+struct CritSigmaArgs {
+  const float* logits;             // [L][B][Q][C]
+  const float* points;             // [L][B][Q][2]
+  const float* log_sigmas;         // [L][B][Q][2], null when no layer has a sigma
+  const int32_t* layer_has_sigma;  // [L] device flags: 0 -> the layer scores with s = 0
+  const int32_t* tgt_labels;       // [B][T]
+  const float* tgt_points;         // [B][T][2]
+  int L, B, Q, C, T;
+  float cost_class, cost_bbox;
+  int sigmoid_cost;                // matching cost on sigmoid(logit) instead of softmax(logits)
+  float eos_coef;
+  double num_boxes;                // loss_bbox normaliser
+  int32_t* match;                  // [L][B][T] matched query per target (out)
+  double* partial;                 // spe_criterion_sigma_partial_bytes(L, B) of scratch
+  double* losses;                  // [L][6] loss_ce, class_error, cardinality_error, loss_bbox (points),
+                                   // loss_bbox (points_uncert), points_different (out)
+};
+size_t spe_criterion_sigma_partial_bytes(int L, int B);
+int spe_launch_criterion_sigma(const CritSigmaArgs& a, hipStream_t s);
+
 // Multi-model keypoint fusion (ensemble.hip): M models' PostProcess outputs -> one fused
 // keypoint set per image in spe_pnp_batch's input layout.
 struct EnsembleArgs {

@@ -7,6 +7,9 @@ The criterion (Hungarian matcher + losses, REV/engine.py:99-112) runs on the dev
 MetricLogger: per-batch values averaged over batches, weighted ("loss", "loss_ce", ...) and
 "<k>_unscaled", plus "class_error".
 
+evaluate_rtdetr() is the UNC RT-DETR model's loop (UNC/solver/speed_engine.py:123-202) over the
+same pieces, with spe.rtdetr.SetCriterion and the reference's extra log fields.
+
 generate_submission() is the reference's gen_submission loop (REV/gen_submission_single.py:113-187,
 gen_submission_multi.py:123-186) from the JPEG files' bytes to the {filename: pose} log.
 """
@@ -20,6 +23,24 @@ import torch
 from . import _lib
 from . import dist as spe_dist
 from .speed_eval import SpeedEval, device_speed_score
+
+
+def _log_losses(ld, weight_dict, device, log):
+    """One batch's criterion outputs into the meters like the reference's MetricLogger update
+    (REV/engine.py:102-112, UNC/solver/speed_engine.py:157-173): rank-averaged values, "loss" = the
+    sum of the weighted ones, "<k>" weighted, "<k>_unscaled" as returned, plus "class_error"."""
+    ld = {k: float(v) for k, v in ld.items()}
+    if spe_dist.is_dist():                            # utils.reduce_dict (REV/engine.py:103)
+        vals = torch.tensor([ld[k] for k in sorted(ld)], dtype=torch.float64, device=device)
+        torch.distributed.all_reduce(vals)
+        ld = dict(zip(sorted(ld), (vals / torch.distributed.get_world_size()).tolist()))
+    scaled = {k: v * weight_dict[k] for k, v in ld.items() if k in weight_dict}
+    log("loss", sum(scaled.values()))
+    for k, v in scaled.items():
+        log(k, v)
+    for k, v in ld.items():
+        log(k + "_unscaled", v)
+    log("class_error", ld["class_error"])
 
 
 @torch.no_grad()
@@ -49,19 +70,7 @@ def evaluate(model, criterion, postprocessors, data_loader, gt_file, solver, dev
         outputs = model(samples, clip_bbox=clip)
         if criterion is not None:
             ld = criterion(outputs, [{k: v.to(device) for k, v in t.items() if torch.is_tensor(v)} for t in targets])
-            ld = {k: float(v) for k, v in ld.items()}
-            if spe_dist.is_dist():                            # utils.reduce_dict (REV/engine.py:103)
-                vals = torch.tensor([ld[k] for k in sorted(ld)], dtype=torch.float64, device=device)
-                torch.distributed.all_reduce(vals)
-                ld = dict(zip(sorted(ld), (vals / torch.distributed.get_world_size()).tolist()))
-            wd = criterion.weight_dict
-            scaled = {k: v * wd[k] for k, v in ld.items() if k in wd}
-            log("loss", sum(scaled.values()))
-            for k, v in scaled.items():
-                log(k, v)
-            for k, v in ld.items():
-                log(k + "_unscaled", v)
-            log("class_error", ld["class_error"])
+            _log_losses(ld, criterion.weight_dict, device, log)
         gt = [evaluator.ground_truth[f] for f in filenames]
         if ceres:
             # EPnPCeresSolver: one threshold per image from its ground-truth box area (UNC SpeedEval
@@ -76,6 +85,52 @@ def evaluate(model, criterion, postprocessors, data_loader, gt_file, solver, dev
         sig = outputs.get("sigmas")
         assess = solver.self_assess(outputs["probs"], sig, poses) if sig is not None else None
         evaluator.update_batch(filenames, outputs["points_px"], outputs["probs"], poses, s_t, s_q, sig, assess)
+    evaluator.log = spe_dist.all_gather_log(evaluator.log)
+    evaluator.summarize()
+    stats = {k: s / max(n, 1) for k, (s, n) in meters.items()}
+    stats["speed_eval_pose"] = evaluator.stats
+    return stats, evaluator
+
+
+@torch.no_grad()
+def evaluate_rtdetr(model, criterion, postprocessors, data_loader, gt_file, solver, device, output_dir=None):
+    """The UNC RT-DETR evaluation loop (UNC/solver/speed_engine.py:123-202) with evaluate()'s
+    interface.  Per batch: one device pass (RTDETR.forward with clip_bbox, so RTDETRPostProcessor
+    runs fused; `postprocessors` is accepted for the reference's signature), the device criterion
+    (spe.rtdetr.SetCriterion), one batched sigma solve and one D2H copy of the pose records.
+
+    The losses are logged exactly as the reference logs them: its criterion returns values already
+    multiplied by weight_dict and the loop multiplies the main layer's (the only keys weight_dict
+    names) by weight_dict again, so "loss" and "<k>" carry the weight twice and "<k>_unscaled"
+    once.  The log entries carry the reference's extra fields (UNC speed_dataset.py:424-438):
+    "sigma" and "aux_points_0..2", the first three aux_outputs entries' pred_logits (the reference
+    stores logits under that name) rounded to 2 decimals."""
+    evaluator = SpeedEval(gt_file, solver)
+    meters = {}
+
+    def log(k, v):
+        s = meters.setdefault(k, [0.0, 0])
+        s[0] += float(v)
+        s[1] += 1
+
+    for samples, targets in data_loader:
+        samples = samples.to(device)
+        filenames = [t["filename"] for t in targets]
+        clip = torch.stack([torch.as_tensor(t["clip_bbox"], dtype=torch.float32) for t in targets]).to(device)
+        outputs = model(samples, clip_bbox=clip)
+        aux = outputs.get("aux_outputs", [])
+        if len(aux) < 3:
+            raise ValueError(f"the UNC evaluation log needs three aux_outputs entries, the model returned {len(aux)}")
+        if criterion is not None:
+            ld = criterion(outputs, [{k: v.to(device) for k, v in t.items() if torch.is_tensor(v)} for t in targets])
+            _log_losses(ld, criterion.weight_dict, device, log)
+        poses = solver.solve_batch(outputs["points_px"], outputs["probs"], outputs["sigmas"])
+        gt = [evaluator.ground_truth[f] for f in filenames]
+        q_gt = torch.tensor([g["quat"] for g in gt], dtype=torch.float64, device=device)
+        t_gt = torch.tensor([g["tvec"] for g in gt], dtype=torch.float64, device=device)
+        s_t, s_q = device_speed_score(poses["quat"], poses["tvec"], q_gt, t_gt)
+        evaluator.update_batch(filenames, outputs["points_px"], outputs["probs"], poses, s_t, s_q, outputs["sigmas"],
+                               aux_logits=[a["pred_logits"] for a in aux[:3]])
     evaluator.log = spe_dist.all_gather_log(evaluator.log)
     evaluator.summarize()
     stats = {k: s / max(n, 1) for k, (s, n) in meters.items()}

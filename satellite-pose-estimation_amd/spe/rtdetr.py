@@ -165,7 +165,106 @@ class RTDETRPostProcessor(nn.Module):
         return [{"logits": prob[i], "points": pts[i], "sigmas": sig[i]} for i in range(prob.shape[0])]
 
 
+class SetCriterion(nn.Module):
+    """UNC/src/zoo/rtdetr/rtdetr_criterion.py:49-337 with the HungarianMatcher of matcher.py:20-117,
+    on the device (spe_criterion_sigma, csrc/criterion_sigma.hip): one call matches and scores the
+    main output, every aux decoder layer and the encoder top-k entry (which has no sigma).
+
+    matcher_weight_dict: cost_class / cost_bbox (a cost_giou entry, which the reference requires and
+    never uses, is ignored); use_focal_loss is the flag the speed configs share with the matcher
+    (include/rtdetr_r50vd.yml:60): the matching cost takes sigmoid(logit) instead of the softmax.
+    losses: "labels", "cardinality", "points", "points_uncert" (both point forms write loss_bbox,
+    the later entry wins, as in the reference's dict update).  forward returns the reference's dict
+    of 0-d device tensors: every loss already multiplied by weight_dict, keys outside weight_dict
+    dropped except the main layer's class_error, aux layer i under "<key>_aux_{i}".  The matching
+    of the last call is kept in `last_match` ([L,B,T] query per target; layer 0 = main output)."""
+
+    LOSSES = ("labels", "cardinality", "points", "points_uncert")
+
+    def __init__(self, matcher_weight_dict=None, weight_dict=None, losses=("labels", "points_uncert"),
+                 eos_coef: float = 1e-4, num_classes: int = 11, use_focal_loss: bool = True):
+        super().__init__()
+        m = {"cost_class": 2, "cost_bbox": 5} if matcher_weight_dict is None else matcher_weight_dict
+        self.cost_class, self.cost_bbox = float(m["cost_class"]), float(m["cost_bbox"])
+        self.weight_dict = {"loss_ce": 1, "loss_bbox": 2} if weight_dict is None else dict(weight_dict)
+        for name in losses:
+            if name not in self.LOSSES:
+                raise ValueError(f"unsupported loss {name!r}: the device criterion computes {self.LOSSES}")
+        self.losses = tuple(losses)
+        self.eos_coef, self.num_classes, self.use_focal_loss = float(eos_coef), int(num_classes), bool(use_focal_loss)
+        self.last_match = None
+        self._flags = {}
+
+    def _layer_flags(self, flags, dev):
+        t = self._flags.get((dev, flags))
+        if t is None:
+            t = self._flags[(dev, flags)] = torch.tensor(flags, dtype=torch.int32, device=dev)
+        return t
+
+    def _layer_dict(self, row, log):
+        """One layer's unweighted entries in the reference's order of insertion."""
+        d = {}
+        for name in self.losses:
+            if name == "labels":
+                d["loss_ce"] = row[0]
+                if log:
+                    d["class_error"] = row[1]
+            elif name == "cardinality":
+                d["cardinality_error"] = row[2]
+            elif name == "points":
+                d["loss_bbox"] = row[3]
+            else:
+                d["points_different"] = row[5]
+                d["loss_bbox"] = row[4]
+        return d
+
+    @torch.no_grad()
+    def forward(self, outputs, targets, stream=None):
+        layers = [outputs] + list(outputs.get("aux_outputs", []))
+        logits = torch.stack([o["pred_logits"] for o in layers]).float().contiguous()
+        points = torch.stack([o["pred_pts"] for o in layers]).float().contiguous()
+        L, B, Q, C = logits.shape
+        if C != self.num_classes + 1:
+            raise ValueError(f"pred_logits has {C} classes, the criterion was built for {self.num_classes} + no-object")
+        dev = logits.device
+        flags = tuple(int("pred_sigmas" in o) for o in layers)
+        sig = None
+        if any(flags):
+            zero = torch.zeros(B, Q, 2, device=dev)
+            sig = torch.stack([o["pred_sigmas"].float() if f else zero for o, f in zip(layers, flags)]).contiguous()
+        labels = torch.stack([t["labels"] for t in targets]).to(dev, torch.int32).contiguous()
+        tpts = torch.stack([t["landmarks"] for t in targets]).to(dev, torch.float32).contiguous()
+        T = labels.shape[1]
+        num_boxes = float(B * T)                          # rtdetr_criterion.py:293: no clamp, no rank average
+        match = torch.empty(L, B, T, dtype=torch.int32, device=dev)
+        res = torch.empty(L, 6, dtype=torch.float64, device=dev)
+        _lib.check(_lib.lib().spe_criterion_sigma(
+            _lib.stream_ptr(stream), _lib.ptr(logits), _lib.ptr(points), _lib.ptr(sig),
+            _lib.ptr(self._layer_flags(flags, dev)), _lib.ptr(labels), _lib.ptr(tpts), L, B, Q, C, T, self.cost_class,
+            self.cost_bbox, int(self.use_focal_loss), self.eos_coef, num_boxes, _lib.ptr(match), _lib.ptr(res)),
+            "spe_criterion_sigma")
+        self.last_match = match
+        wd = self.weight_dict
+        losses = {}
+        for l in range(L):
+            d = self._layer_dict(res[l], log=l == 0)
+            sfx = "" if l == 0 else f"_aux_{l - 1}"
+            if "class_error" in d:
+                losses["class_error"] = d["class_error"]
+            losses.update({k + sfx: v * wd[k] for k, v in d.items() if k in wd})
+        return losses
+
+
 def build_rtdetr(cfg: RtdetrConfig = None, dtype: str = "bf16"):
     """(model, postprocessor) of a speed config (UNC/configs/rtdetr_speed/*.yml fields)."""
     cfg = cfg or RtdetrConfig()
     return RTDETR(cfg, dtype), RTDETRPostProcessor(cfg.num_classes, num_top_queries=cfg.num_queries)
+
+
+def build_rtdetr_criterion(cfg: RtdetrConfig = None, losses=("labels", "points_uncert")):
+    """The SetCriterion of a speed config (UNC/configs/rtdetr_speed/rtdetr_r{18,50}vd_6x_speed_kl_*.yml:
+    matcher cost_class 2 / cost_bbox 5 with the shared use_focal_loss, loss_ce 1, loss_bbox 2 for
+    r18 and 5 for r50; the plain speed_*.yml configs use losses=("labels", "points"))."""
+    cfg = cfg or RtdetrConfig()
+    return SetCriterion({"cost_class": 2, "cost_bbox": 5}, {"loss_ce": 1, "loss_bbox": 5 if cfg.depth == 50 else 2},
+                        losses, eos_coef=1e-4, num_classes=cfg.num_classes, use_focal_loss=True)

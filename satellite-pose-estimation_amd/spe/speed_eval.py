@@ -103,12 +103,16 @@ class SpeedEval:
             s_t, s_q = speed_score(quat_pr, tvec_pr, gt["quat"], gt["tvec"])
             self._record(filename, ret["points"], ret["logits"], quat_pr, tvec_pr, s_t, s_q)
 
-    def update_batch(self, filenames, points_px, probs, poses, s_t=None, s_q=None, sigmas=None, assess=None):
+    def update_batch(self, filenames, points_px, probs, poses, s_t=None, s_q=None, sigmas=None, assess=None,
+                     aux_logits=None):
         """Hot-path variant: `poses` is the dict returned by solver.solve_batch (device), optional
         device scores from device_speed_score.  Failed images carry zero poses (status != 0
         except RANSAC_FALLBACK), exactly as update() produces them.  With the sigma head the
         record also carries "sigma" (UNC/src/data/speed/speed_dataset.py:437, 8 dp) and, when
-        `assess` (solver.self_assess output) is given, the self-assessment verdict."""
+        `assess` (solver.self_assess output) is given, the self-assessment verdict.  `aux_logits`
+        (a list of [B,Q,C] tensors) adds the UNC log's "aux_points_<i>" fields: the reference stores
+        the aux layers' pred_logits under that name, rounded to 2 decimals (speed_dataset.py:417-428)."""
+        aux = [a.detach().cpu().numpy() for a in aux_logits] if aux_logits is not None else []
         sg = sigmas.detach().cpu().numpy() if sigmas is not None else None
         ms = assess["mean_sigma"].cpu().numpy() if assess is not None else None
         rl = assess["reliable"].cpu().numpy() if assess is not None else None
@@ -127,6 +131,8 @@ class SpeedEval:
             self._record(fn, pts[i], prb[i], quat[i], tvec[i], a, b)
             if sg is not None:
                 self.log[fn]["sigma"] = np.around(sg[i], decimals=8).tolist()
+            for k, a in enumerate(aux):
+                self.log[fn][f"aux_points_{k}"] = np.around(a[i], decimals=2).tolist()
             if rl is not None:
                 self.log[fn]["mean_sigma"] = float(np.around(ms[i], decimals=8))
                 self.log[fn]["reliable"] = bool(rl[i])
