@@ -108,9 +108,18 @@ typedef struct {
  * RTDETRTransformer) (UNC/src/zoo/rtdetr/rtdetr.py:20-38, UNC/nn/backbone/presnet.py:156-265,
  * UNC/src/zoo/rtdetr/hybrid_encoder.py:196-401, UNC/src/zoo/rtdetr/rtdetr_decoder.py:372-710) as
  * the speed configs build it (UNC/configs/rtdetr_speed/rtdetr_r{18,50}vd_6x_speed_kl_*.yml). */
+/* spe_rtdetr_config.depth value that selects MobileNetV3_Large (UNC/nn/backbone/mobilenetv3.py:123-225,
+ * UNC/configs/rtdetr_speed/rtdetr_mobilenetv3_6x_speed_*.yml) instead of a PResNet depth.  That
+ * backbone resizes its stem output to a hard-coded 64 x 64 before the stride-8 / 16 branch, so its three
+ * maps are the stride 8 / 16 / 32 levels only at input_size 256: spe_rtdetr_create refuses every other
+ * size (SPE_E_ARG), as the reference's own hybrid encoder does.  Its never-called linear3 / bn3
+ * parameters are part of the key space (accepted and ignored). */
+#define SPE_RTDETR_MBV3_LARGE 1003
+
 typedef struct {
-  int depth;            /* PResNet depth, variant d: 18 (BasicBlock) or 50 (BottleNeck) */
-  int input_size;       /* eval_spatial_size (256); multiple of 32 */
+  int depth;            /* backbone selector: 18 (BasicBlock) or 50 (BottleNeck) = PResNet variant d of that
+                         * depth; SPE_RTDETR_MBV3_LARGE = MobileNetV3_Large */
+  int input_size;       /* eval_spatial_size (256); multiple of 32; MobileNetV3_Large: 256 only */
   int num_queries;      /* RTDETRTransformer.num_queries (30), <= 64 */
   int dec_layers;       /* num_decoder_layers (3) */
   int enc_ff;           /* HybridEncoder.dim_feedforward (1024, GELU) */
@@ -451,6 +460,34 @@ int spe_debug_btail_perm(int k);
  * input [B][S+6][S+6][4] and w [64][ldw] with k = (kh*8 + kw)*4 + ci (registry.cpp's stem). */
 int spe_debug_stempool(void* stream, const void* x, const void* w, int ldw, const float* bias, void* out, int ldo,
                        int B, int S);
+
+/* MobileNetV3_Large backbone kernels (mbv3.hip, ABI 9 additions; act: 0 none, 1 ReLU, 4 Hardswish).
+ * dwconv: depthwise k x k conv, pad k/2, over NHWC x [B][H][W][C] -> y [B][Ho][Wo][C], y = act(conv + bias);
+ * w fp32 [k*k][C] (tap-major, a folded BatchNorm scale included), bias fp32 [C]; dtype BF16_ (fp32
+ * accumulation) or F32_.  Contract, checked before any launch (SPE_E_ARG): k 3 or 5; stride 1, or 2 with
+ * even H and W (Ho = H / stride, Wo = W / stride); C % 8 == 0; B <= 65535.  pool_partials (nullable): fp32
+ * [B][spe_debug_dwconv_tiles(Ho, Wo)][C], per 8 x 8 output tile the sum of the stored outputs, added in a
+ * fixed order (no floating-point atomics: two runs give the same bits) -- the SE gate's pool. */
+int spe_debug_dwconv_tiles(int Ho, int Wo);
+int spe_debug_dwconv(void* stream, int dtype, const void* x, const float* w, const float* bias, void* y,
+                     float* pool_partials, int B, int H, int W, int C, int k, int stride, int act);
+/* se_gate: scale [B][C] = hardsigmoid(w2 . relu(w1 . mean + b1)), mean[b][c] = inv_hw * sum_t
+ * pool_partials[b][t][c]; w1 fp32 [hidden][C] (the BatchNorm folded in), b1 [hidden], w2t fp32 [hidden][C]
+ * (the second conv's [C][hidden] weight transposed).  fp32 in both model dtypes.  C <= 1024, hidden <= 256. */
+int spe_debug_se_gate(void* stream, const float* pool_partials, int tiles, float inv_hw, const float* w1, const float* b1,
+                      const float* w2t, float* scale, int B, int C, int hidden);
+/* pwconv: c [M][ldc] = act((a . scale) . w^T + bias + r): a [M][lda], w [N][ldw], r [M][ldr] (nullable) and c
+ * in dtype (BF16_: MFMA bf16, fp32 accumulation; F32_: exact-f32 MFMA); bias fp32 [N] (nullable); scale fp32
+ * [M / rows_per_image][K] (nullable): row m's a is multiplied by scale[m / rows_per_image] and rounded to
+ * dtype; the residual is added BEFORE the activation.  N, K, lda, ldw, ldc, ldr multiples of 8 (SPE_E_ARG). */
+int spe_debug_pwconv(void* stream, int dtype, const void* a, int lda, const void* w, int ldw, const float* bias,
+                     const float* scale, int rows_per_image, const void* r, int ldr, void* c, int ldc, int M, int N,
+                     int K, int act);
+/* The backbone stage alone of a finalized RT-DETR handle of either family (what spe_rtdetr_forward runs
+ * first): images as spe_rtdetr_forward's; f0 / f1 / f2 = the stride 8 / 16 / 32 maps as fp32 NCHW
+ * [B][C_l][S/8 .. S/32]^2 (C_l = 128, 256, 512, x 4 for depth 50). */
+int spe_debug_rtdetr_backbone(spe_model* m, void* stream, const float* images, int batch, void* workspace,
+                              int64_t workspace_bytes, float* f0, float* f1, float* f2);
 
 #ifdef __cplusplus
 }

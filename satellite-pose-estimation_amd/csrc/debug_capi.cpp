@@ -292,4 +292,63 @@ int spe_debug_stempool(void* stream, const void* x, const void* w, int ldw, cons
   return rc != 0 ? spe_fail(SPE_E_LAUNCH, "stempool launch rejected its arguments") : 0;
 }
 
+// ---- MobileNetV3 backbone kernels (mbv3.hip)
+int spe_debug_dwconv_tiles(int Ho, int Wo) { return Ho > 0 && Wo > 0 ? spe_mb_dwconv_tiles(Ho, Wo) : 0; }
+
+int spe_debug_dwconv(void* stream, int dtype, const void* x, const float* w, const float* bias, void* y,
+                     float* pool_partials, int B, int H, int W, int C, int k, int stride, int act) {
+  if (!x || !w || !bias || !y) return spe_fail(SPE_E_ARG, "null argument");
+  if (dtype != SPE_DTYPE_BF16 && dtype != SPE_DTYPE_F32) return spe_fail(SPE_E_ARG, "bad dtype");
+  if (!spe_mb_dwconv_fits(B, H, W, C, k, stride) || (act != MB_ACT_NONE && act != MB_ACT_RELU && act != MB_ACT_HSWISH))
+    return spe_fail(SPE_E_ARG, "dwconv: k must be 3 or 5, stride 1 or 2 (even H and W), C a multiple of 8, act 0 / 1 / 4");
+  MbDwArgs a{};
+  a.in = x; a.out = y; a.w = w; a.bias = bias; a.pool = pool_partials;
+  a.B = B; a.H = H; a.W = W; a.C = C; a.k = k; a.stride = stride; a.act = act;
+  const int rc = spe_launch_mb_dwconv(a, dtype, (hipStream_t)stream);
+  return rc < 0 ? spe_fail(SPE_E_LAUNCH, "dwconv launch rejected its arguments") : rc;
+}
+
+int spe_debug_se_gate(void* stream, const float* pool_partials, int tiles, float inv_hw, const float* w1, const float* b1,
+                      const float* w2t, float* scale, int B, int C, int hidden) {
+  MbSeArgs a{};
+  a.pool = pool_partials; a.tiles = tiles; a.inv_hw = inv_hw;
+  a.w1 = w1; a.b1 = b1; a.w2t = w2t; a.scale = scale;
+  a.B = B; a.C = C; a.hidden = hidden;
+  const int rc = spe_launch_mb_se_gate(a, (hipStream_t)stream);
+  return rc < 0 ? spe_fail(SPE_E_ARG, "se_gate: null argument, C > 1024 or hidden > 256") : rc;
+}
+
+int spe_debug_pwconv(void* stream, int dtype, const void* a, int lda, const void* w, int ldw, const float* bias,
+                     const float* scale, int rows_per_image, const void* r, int ldr, void* c, int ldc, int M, int N,
+                     int K, int act) {
+  if (!a || !w || !c) return spe_fail(SPE_E_ARG, "null argument");
+  if (dtype != SPE_DTYPE_BF16 && dtype != SPE_DTYPE_F32) return spe_fail(SPE_E_ARG, "bad dtype");
+  const int hw = scale ? rows_per_image : M;
+  if (M <= 0 || hw <= 0 || M % hw) return spe_fail(SPE_E_ARG, "pwconv: M must be a multiple of rows_per_image");
+  MbGemmArgs g{};
+  g.A = a; g.lda = lda; g.Bw = w; g.ldb = ldw; g.bias = bias; g.scale = scale;
+  g.R = r; g.ldr = ldr; g.C = c; g.ldc = ldc;
+  g.M = M; g.N = N; g.K = K;
+  g.H = 1; g.W = hw; g.Cin = K; g.KH = 1; g.KW = 1; g.stride = 1; g.pad = 0; g.Ho = 1; g.Wo = hw;
+  g.act = act;
+  if (!spe_mb_gemm_fits(g)) return spe_fail(SPE_E_ARG, "pwconv: N, K and the row strides must be multiples of 8, act 0 / 1 / 4");
+  const int rc = spe_launch_mb_gemm(g, dtype, (hipStream_t)stream);
+  return rc < 0 ? spe_fail(SPE_E_LAUNCH, "pwconv launch rejected its arguments") : rc;
+}
+
+int spe_debug_rtdetr_backbone(spe_model* m, void* stream, const float* images, int batch, void* workspace,
+                              int64_t workspace_bytes, float* f0, float* f1, float* f2) {
+  if (!f0 || !f1 || !f2) return spe_fail(SPE_E_ARG, "null argument");
+  const void* f[3];
+  int ch[3], hw[3];
+  const int rc = spe_rtdetr_backbone(m, (hipStream_t)stream, images, batch, workspace, workspace_bytes, f, ch, hw);
+  if (rc) return rc;
+  float* out[3] = {f0, f1, f2};
+  for (int l = 0; l < 3; ++l) {
+    const int e = spe_launch_mb_to_nchw(f[l], out[l], batch, hw[l] * hw[l], ch[l], m->cfg.dtype, (hipStream_t)stream);
+    if (e) return spe_fail(e < 0 ? SPE_E_LAUNCH : e, "backbone output conversion failed");
+  }
+  return 0;
+}
+
 }  // extern "C"

@@ -109,8 +109,29 @@ struct RtDec {               // decoder layer + its heads
   float *n1g, *n1b, *n2g, *n2b, *n3g, *n3b;
   RtHead head;
 };
+// MobileNetV3_Large backbone (UNC/nn/backbone/mobilenetv3.py:123-225), BatchNorm folded everywhere
+struct MbDw {                // depthwise conv: w fp32 [k*k][C] (BN scale folded), bias fp32 [C]
+  float *w = nullptr, *bias = nullptr;
+  int C = 0, k = 3, stride = 1;
+};
+struct MbBlock {             // Block (mobilenetv3.py:45-120)
+  Conv expand, project, skip_pw;     // 1x1 convs, rows [N][Kpad] T
+  MbDw dw, skip_dw;
+  float *se_w1 = nullptr, *se_b1 = nullptr, *se_w2t = nullptr;   // SE gate: [hid][C] (BN folded), [hid], [hid][C]
+  int se_hidden = 0;
+  int cin = 0, cexp = 0, cout = 0, stride = 1, act = 0;
+  bool se = false, has_skip_pw = false, has_skip_dw = false;
+};
+struct RtMbv3 {
+  float *stem_w = nullptr, *stem_b = nullptr;   // conv1 + bn1: [27][16], [16]
+  Conv conv_b, conv_c, last;   // Conv1 with the 2x2 mean folded in (6x6 / s4 / p2 over the stem output), Conv2, conv2
+  std::vector<MbBlock> blocks;
+};
 struct RtModel {
   spe_rtdetr_config cfg{};
+  bool mbv3 = false;                    // cfg.depth == SPE_RTDETR_MBV3_LARGE
+  RtMbv3 mb;
+  int fch[3] = {0, 0, 0};               // backbone output channels (the hybrid encoder's in_channels)
   int L = 0, lvl_s[3] = {0, 0, 0}, lvl_start[4] = {0, 0, 0, 0};
   Conv stem[3];
   std::vector<RtBlock> blocks;
@@ -169,6 +190,10 @@ int spe_fail(int code, const std::string& msg);
 // RT-DETR runtime hooks (rtdetr_model.cpp)
 int spe_rtdetr_build_device(spe_model* m);
 int64_t spe_rtdetr_workspace(const spe_model* m, int B);
+// the backbone stage alone (the first stage of spe_rtdetr_forward): images -> the three NHWC feature maps
+// in the workspace; f[l] (nullable) receives their addresses, ch[l] / hw[l] their channels and edge
+int spe_rtdetr_backbone(spe_model* m, hipStream_t s, const float* images, int B, void* workspace, int64_t ws_bytes,
+                        const void** f, int* ch, int* hw);
 
 // bf16 models take the decoder cross-attention against the memory itself (xattn.hip) when the
 // last encoder layer can emit memory + pos (fused FFN); fp32h3 models too, on the memory's fp16

@@ -28,6 +28,18 @@ namespace {
 
 const int RESNET_CFG18[4] = {2, 2, 2, 2}, RESNET_CFG50[4] = {3, 4, 6, 3};
 
+inline bool is_mbv3(const spe_rtdetr_config& c) { return c.depth == SPE_RTDETR_MBV3_LARGE; }
+inline int resnet_expansion(const spe_rtdetr_config& c) { return !is_mbv3(c) && c.depth >= 50 ? 4 : 1; }
+
+// MobileNetV3_Large.bneck (mobilenetv3.py:148-164): kernel, in, expand, out, Hardswish (else ReLU), SE, stride
+struct MbRow { int k, cin, cexp, cout, hs, se, stride; };
+const MbRow MBV3_LARGE[15] = {
+    {3, 16, 16, 16, 0, 0, 1},    {3, 16, 64, 24, 0, 0, 2},    {3, 24, 72, 24, 0, 0, 1},   {5, 24, 72, 40, 0, 1, 2},
+    {5, 40, 120, 40, 0, 1, 1},   {5, 40, 120, 40, 0, 1, 1},   {3, 40, 240, 80, 1, 0, 2},  {3, 80, 200, 80, 1, 0, 1},
+    {3, 80, 184, 80, 1, 0, 1},   {3, 80, 184, 80, 1, 0, 1},   {3, 80, 480, 112, 1, 1, 1}, {3, 112, 672, 112, 1, 1, 1},
+    {5, 112, 672, 160, 1, 1, 2}, {5, 160, 672, 160, 1, 1, 1}, {5, 160, 960, 160, 1, 1, 1}};
+inline int se_hidden(int c) { return c / 4 > 8 ? c / 4 : 8; }
+
 std::vector<std::pair<std::string, std::vector<int64_t>>> rt_spec(const spe_rtdetr_config& c) {
   std::vector<std::pair<std::string, std::vector<int64_t>>> s;
   const int64_t d = 256, C = c.num_classes + 1;
@@ -49,11 +61,41 @@ std::vector<std::pair<std::string, std::vector<int64_t>>> rt_spec(const spe_rtde
     lin(p + ".out_proj", d, d);
   };
   add("temper_param", {1});
+  if (is_mbv3(c)) {     // registration order of MobileNetV3_Large.__init__ (mobilenetv3.py:136-173)
+    const std::string b = "backbone.";
+    add(b + "conv1.weight", {16, 3, 3, 3});
+    bn(b + "bn1", 16); bn(b + "Bn1", 128); bn(b + "Bn2", 256);
+    add(b + "Conv1.weight", {128, 16, 3, 3});
+    add(b + "Conv2.weight", {256, 128, 3, 3});
+    for (int i = 0; i < 15; ++i) {
+      const MbRow& r = MBV3_LARGE[i];
+      const std::string p = b + "bneck." + std::to_string(i);
+      add(p + ".conv1.weight", {r.cexp, r.cin, 1, 1}); bn(p + ".bn1", r.cexp);
+      add(p + ".conv2.weight", {r.cexp, 1, r.k, r.k}); bn(p + ".bn2", r.cexp);
+      if (r.se) {
+        const int64_t h = se_hidden(r.cexp);
+        add(p + ".se.se.1.weight", {h, r.cexp, 1, 1}); bn(p + ".se.se.2", h);
+        add(p + ".se.se.4.weight", {r.cexp, h, 1, 1});
+      }
+      add(p + ".conv3.weight", {r.cout, r.cexp, 1, 1}); bn(p + ".bn3", r.cout);
+      if (r.stride == 1 && r.cin != r.cout) {
+        add(p + ".skip.0.weight", {r.cout, r.cin, 1, 1}); bn(p + ".skip.1", r.cout);
+      } else if (r.stride == 2 && r.cin != r.cout) {
+        add(p + ".skip.0.weight", {r.cin, 1, 3, 3}); bn(p + ".skip.1", r.cin);
+        add(p + ".skip.2.weight", {r.cout, r.cin, 1, 1}); add(p + ".skip.2.bias", {r.cout}); bn(p + ".skip.3", r.cout);
+      } else if (r.stride == 2) {
+        add(p + ".skip.0.weight", {r.cout, 1, 3, 3}); bn(p + ".skip.1", r.cout);
+      }
+    }
+    add(b + "conv2.weight", {512, 160, 1, 1}); bn(b + "bn2", 512);
+    add(b + "linear3.weight", {1280, 960}); bn(b + "bn3", 1280);     // built, never called
+  }
+  const bool bott = !is_mbv3(c) && c.depth >= 50;
+  const int64_t exp = bott ? 4 : 1;
+  if (!is_mbv3(c)) {
   cnl("backbone.conv1.conv1_1", 3, 32, 3);
   cnl("backbone.conv1.conv1_2", 32, 32, 3);
   cnl("backbone.conv1.conv1_3", 32, 64, 3);
-  const bool bott = c.depth >= 50;
-  const int64_t exp = bott ? 4 : 1;
   const int* nb = bott ? RESNET_CFG50 : RESNET_CFG18;
   const int64_t widths[4] = {64, 128, 256, 512};
   int64_t cin = 64;
@@ -75,6 +117,7 @@ std::vector<std::pair<std::string, std::vector<int64_t>>> rt_spec(const spe_rtde
       }
       cin = co * exp;
     }
+  }
   const int NL = 3, NP = 4, H = 8, P = H * NL * NP;
   for (int l = 0; l < NL; ++l) cnl("decoder.input_proj." + std::to_string(l), d, d, 1);
   for (int i = 0; i < c.dec_layers; ++i) {
@@ -216,11 +259,15 @@ RtCsp make_csp(spe_model* m, const std::string& p, int h) {
   return c;
 }
 
+// largest tiles x channels product of an SE block's pool partials (block 11: 4 tiles x 672 at 256 input)
+constexpr size_t MB_POOL_MAX = 4096;
+
 // ---- workspace plan
 struct RtWs {
   size_t x0, bufA, bufB, t1, t2, sc, f0, f1, f2;
   size_t cat0, cat1, catp0, catp1, aqk, avt, aao, atmp, affn, aout;
   size_t x1, x2, y, inner1, p3, n4, n5;
+  size_t mbpool, mbscale;      // MobileNetV3: dwconv pool partials [B][MB_POOL_MAX], SE scales [B][960]
   size_t mem, omem, elog, value;
   size_t topk, tgt, slog, sanc, refs, qh, qpos, hh1, hh2, dqk, dvt, dao, dtmp, t1d, t2d, soaw, dcr, dffn, hs, lgt;
   size_t total;
@@ -231,7 +278,7 @@ RtWs rt_plan(const spe_model* m, int B) {
   const auto& c = r.cfg;
   const size_t E = m->esz, S = c.input_size, Q = c.num_queries, L = r.L, BQ = (size_t)B * Q;
   const size_t s0 = r.lvl_s[0], s1 = r.lvl_s[1], s2 = r.lvl_s[2];
-  const size_t exp = c.depth >= 50 ? 4 : 1;
+  const size_t exp = resnet_expansion(c);
   RtWs w{};
   size_t off = 0;
   auto take = [&](size_t bytes) { size_t o = off; off += (bytes + 255) & ~size_t(255); return o; };
@@ -254,6 +301,9 @@ RtWs rt_plan(const spe_model* m, int B) {
   w.p3 = take((size_t)B * s0 * s0 * 256 * E);
   w.n4 = take((size_t)B * s1 * s1 * 256 * E);
   w.n5 = take((size_t)B * s2 * s2 * 256 * E);
+  // (zero bytes for PResNet handles: their plan is what it was)
+  w.mbpool = take(r.mbv3 ? (size_t)B * MB_POOL_MAX * 4 : 0);
+  w.mbscale = take(r.mbv3 ? (size_t)B * 960 * 4 : 0);
   w.mem = take((size_t)B * L * 256 * E);
   w.omem = take((size_t)B * L * 256 * E);
   w.elog = take((size_t)B * L * (c.num_classes + 1) * 4);
@@ -273,17 +323,293 @@ RtWs rt_plan(const spe_model* m, int B) {
   return w;
 }
 
+// ---- MobileNetV3_Large packing: eval BatchNorm (eps 1e-5) folded in double, like fold_conv
+void bn_fold(spe_model* m, const std::string& bn, int C, std::vector<double>& scale, std::vector<double>& shift) {
+  const auto& g = m->host[bn + ".weight"];
+  const auto& b = m->host[bn + ".bias"];
+  const auto& rm = m->host[bn + ".running_mean"];
+  const auto& rv = m->host[bn + ".running_var"];
+  scale.assign(C, 1.0);
+  shift.assign(C, 0.0);
+  for (int c = 0; c < C; ++c) {
+    scale[c] = (double)g[c] / std::sqrt((double)rv[c] + 1e-5);
+    shift[c] = (double)b[c] - (double)rm[c] * scale[c];
+  }
+}
+
+// conv [cout][cin][kh][kw] (+ a bias in front of the norm) + BatchNorm -> rows [cout][(y*kw + x)*cin + ci]
+// (the plain tap-major K order mb_gemm's A loader walks), folded bias.  pool2: the conv reads a 2x2 mean
+// of its input -- folded into a (2kh)x(2kw) kernel of stride 2*stride, pad 2*pad, w/4 per tap (exact).
+Conv mb_conv(spe_model* m, const std::string& wkey, const std::string& bn, const std::string& biaskey, int stride,
+             int pad, bool pool2 = false) {
+  const auto sh = param_shape(m, wkey);
+  const int cout = (int)sh[0], cin = (int)sh[1], kh = (int)sh[2], kw = (int)sh[3];
+  const int f = pool2 ? 2 : 1, KH = kh * f, KW = kw * f, K = KH * KW * cin;
+  std::vector<double> scale, shift;
+  bn_fold(m, bn, cout, scale, shift);
+  const auto& w = m->host[wkey];
+  std::vector<float> rows((size_t)cout * K, 0.f), bias(cout);
+  for (int co = 0; co < cout; ++co) {
+    if (!biaskey.empty()) shift[co] += (double)m->host[biaskey][co] * scale[co];
+    bias[co] = (float)shift[co];
+    for (int ci = 0; ci < cin; ++ci)
+      for (int y = 0; y < KH; ++y)
+        for (int x = 0; x < KW; ++x)
+          rows[(size_t)co * K + (size_t)(y * KW + x) * cin + ci] =
+              (float)((double)w[(((size_t)co * cin + ci) * kh + y / f) * kw + x / f] * scale[co] / (f * f));
+  }
+  Conv c;
+  c.N = cout; c.K = K; c.Kpad = pad64(K); c.Cin = cin; c.KH = KH; c.KW = KW; c.stride = stride * f; c.pad = pad * f;
+  c.w = upload_rows(m, rows, c.N, c.K, c.Kpad);
+  c.bias = upload_f32(m, bias.data(), bias.size());
+  return c;
+}
+
+MbDw mb_dw(spe_model* m, const std::string& wkey, const std::string& bn, int stride) {
+  const auto sh = param_shape(m, wkey);
+  const int C = (int)sh[0], k = (int)sh[2];
+  std::vector<double> scale, shift;
+  bn_fold(m, bn, C, scale, shift);
+  const auto& w = m->host[wkey];
+  std::vector<float> wt((size_t)k * k * C), bias(C);
+  for (int c = 0; c < C; ++c) {
+    bias[c] = (float)shift[c];
+    for (int t = 0; t < k * k; ++t) wt[(size_t)t * C + c] = (float)((double)w[(size_t)c * k * k + t] * scale[c]);
+  }
+  MbDw d;
+  d.C = C; d.k = k; d.stride = stride;
+  d.w = upload_f32(m, wt.data(), wt.size());
+  d.bias = upload_f32(m, bias.data(), bias.size());
+  return d;
+}
+
+void build_mbv3(spe_model* m) {
+  RtMbv3& mb = m->rt->mb;
+  const std::string b = "backbone.";
+  {   // conv1 + bn1: fp32 [27][16] with k = (ci*3 + kh)*3 + kw
+    std::vector<double> scale, shift;
+    bn_fold(m, b + "bn1", 16, scale, shift);
+    const auto& w = m->host[b + "conv1.weight"];
+    std::vector<float> wt(27 * 16), bias(16);
+    for (int c = 0; c < 16; ++c) {
+      bias[c] = (float)shift[c];
+      for (int k = 0; k < 27; ++k) wt[(size_t)k * 16 + c] = (float)((double)w[(size_t)c * 27 + k] * scale[c]);
+    }
+    mb.stem_w = upload_f32(m, wt.data(), wt.size());
+    mb.stem_b = upload_f32(m, bias.data(), bias.size());
+  }
+  mb.conv_b = mb_conv(m, b + "Conv1.weight", b + "Bn1", "", 2, 1, true);
+  mb.conv_c = mb_conv(m, b + "Conv2.weight", b + "Bn2", "", 2, 1);
+  mb.blocks.clear();
+  for (int i = 0; i < 15; ++i) {
+    const MbRow& r = MBV3_LARGE[i];
+    const std::string p = b + "bneck." + std::to_string(i);
+    MbBlock k;
+    k.cin = r.cin; k.cexp = r.cexp; k.cout = r.cout; k.stride = r.stride;
+    k.act = r.hs ? MB_ACT_HSWISH : MB_ACT_RELU;
+    k.expand = mb_conv(m, p + ".conv1.weight", p + ".bn1", "", 1, 0);
+    k.dw = mb_dw(m, p + ".conv2.weight", p + ".bn2", r.stride);
+    k.se = r.se != 0;
+    if (k.se) {
+      const int h = se_hidden(r.cexp), C = r.cexp;
+      k.se_hidden = h;
+      std::vector<double> scale, shift;
+      bn_fold(m, p + ".se.se.2", h, scale, shift);
+      const auto& w1 = m->host[p + ".se.se.1.weight"];
+      const auto& w2 = m->host[p + ".se.se.4.weight"];
+      std::vector<float> f1((size_t)h * C), b1(h), f2t((size_t)h * C);
+      for (int j = 0; j < h; ++j) {
+        b1[j] = (float)shift[j];
+        for (int c = 0; c < C; ++c) {
+          f1[(size_t)j * C + c] = (float)((double)w1[(size_t)j * C + c] * scale[j]);
+          f2t[(size_t)j * C + c] = w2[(size_t)c * h + j];
+        }
+      }
+      k.se_w1 = upload_f32(m, f1.data(), f1.size());
+      k.se_b1 = upload_f32(m, b1.data(), b1.size());
+      k.se_w2t = upload_f32(m, f2t.data(), f2t.size());
+    }
+    k.project = mb_conv(m, p + ".conv3.weight", p + ".bn3", "", 1, 0);
+    if (r.stride == 1 && r.cin != r.cout) {
+      k.has_skip_pw = true;
+      k.skip_pw = mb_conv(m, p + ".skip.0.weight", p + ".skip.1", "", 1, 0);
+    } else if (r.stride == 2) {
+      k.has_skip_dw = true;
+      k.skip_dw = mb_dw(m, p + ".skip.0.weight", p + ".skip.1", 2);
+      if (r.cin != r.cout) {
+        k.has_skip_pw = true;
+        k.skip_pw = mb_conv(m, p + ".skip.2.weight", p + ".skip.3", p + ".skip.2.bias", 1, 0);
+      }
+    }
+    mb.blocks.push_back(k);
+  }
+  mb.last = mb_conv(m, b + "conv2.weight", b + "bn2", "", 1, 0);
+}
+
+// ---- backbone stages: both leave f0 / f1 / f2 (NHWC, strides 8 / 16 / 32) where the hybrid encoder reads them
+int rt_backbone_presnet(spe_model* m, hipStream_t s, const float* images, int B, char* ws, const RtWs& w) {
+  const RtModel& r = *m->rt;
+  const auto& c = r.cfg;
+  const int dt = c.dtype, S = c.input_size, E = m->esz;
+  auto P = [&](size_t o) { return (void*)(ws + o); };
+  // conv as an implicit GEMM, or a plain GEMM over NHWC rows when it is 1x1 / stride 1; the
+  // residual R (same row layout as the output) is added before the activation
+  auto cgemm = [&](const char* kind, const Conv& cv, const void* in, int Hin, void* outp, int ldc, int act,
+                   const void* R) {
+    GemmArgs g;
+    int mode = GEMM_CONV;
+    if (cv.KH == 1 && cv.KW == 1 && cv.stride == 1 && cv.pad == 0) {
+      g = linear_args(cv, in, cv.Cin, B * Hin * Hin, outp, ldc);
+      mode = GEMM_LINEAR;
+    } else {
+      g = conv_args(cv, in, B, Hin, Hin, outp, ldc);
+    }
+    g.act = act;
+    g.R = R; g.ldr = ldc;
+    return run_gemm(m, kind, g, mode, s);
+  };
+
+  // ---------------- PResNet-vd (presnet.py:248-265)
+  CK(run_other(m, "eltwise.pack", 0.0, (double)B * S * S * (12 + 8 * E), s,
+               [&] { return spe_launch_pack_input(images, P(w.x0), B, S, dt, s); }));
+  int H = S;
+  size_t cur = w.x0;
+  const size_t stem_out[3] = {w.bufA, w.bufB, w.bufA};
+  for (int i = 0; i < 3; ++i) {
+    GemmArgs g = conv_args(r.stem[i], P(cur), B, H, H, P(stem_out[i]), r.stem[i].N);
+    g.act = ACT_RELU;
+    CK(run_gemm(m, "rt.conv.stem", g, GEMM_CONV, s));
+    H = g.Ho;
+    cur = stem_out[i];
+  }
+  const int Hp = (H + 2 - 3) / 2 + 1;
+  CK(run_other(m, "eltwise.maxpool", 0.0, (double)B * 64 * (H * H + Hp * Hp) * E, s,
+               [&] { return spe_launch_maxpool3s2(P(cur), P(w.bufB), B, H, H, 64, Hp, Hp, dt, s); }));
+  H = Hp;
+  cur = w.bufB;
+  const size_t feat[3] = {w.f0, w.f1, w.f2};
+  for (int st = 0; st < 4; ++st)
+    for (int j = 0; j < r.stage_n[st]; ++j) {
+      const RtBlock& b = r.blocks[r.stage_first[st] + j];
+      const int Ho = H / b.stride;
+      const bool last = j == r.stage_n[st] - 1;
+      const size_t outbuf = (last && st > 0) ? feat[st - 1] : (cur == w.bufA ? w.bufB : w.bufA);
+      size_t res = cur;
+      if (b.has_sc) {
+        CK(cgemm(b.stride == 2 ? "rt.conv.short" : "rt.conv.1x1", b.sc, P(cur), H, P(w.sc), b.cout, ACT_NONE, nullptr));
+        res = w.sc;
+      }
+      CK(cgemm(b.bottleneck ? "rt.conv.1x1" : "rt.conv.3x3", b.a, P(cur), H, P(w.t1), b.a.N, ACT_RELU, nullptr));
+      const int Ha = (H + 2 * b.a.pad - b.a.KH) / b.a.stride + 1;
+      if (b.bottleneck) {
+        CK(cgemm("rt.conv.3x3", b.b, P(w.t1), Ha, P(w.t2), b.b.N, ACT_RELU, nullptr));
+        CK(cgemm("rt.conv.1x1", b.c, P(w.t2), Ho, P(outbuf), b.cout, ACT_RELU, P(res)));
+      } else {
+        CK(cgemm("rt.conv.3x3", b.b, P(w.t1), Ha, P(outbuf), b.cout, ACT_RELU, P(res)));
+      }
+      H = Ho;
+      cur = outbuf;
+    }
+  return 0;
+}
+
+// MobileNetV3_Large.forward (mobilenetv3.py:206-225) at input 256: stem -> x0 [B][128][128][16]; Conv1 (2x2
+// mean folded in) -> f0, Conv2 -> f1; the 15 blocks ping-pong bufA / bufB with the expanded tensor in t1,
+// the depthwise output in t2 and the skip branch in sc; conv2 -> f2
+int rt_backbone_mbv3(spe_model* m, hipStream_t s, const float* images, int B, char* ws, const RtWs& w) {
+  const RtModel& r = *m->rt;
+  const RtMbv3& mb = r.mb;
+  const int dt = r.cfg.dtype, S = r.cfg.input_size;
+  const double E = m->esz;
+  auto P = [&](size_t o) { return (void*)(ws + o); };
+  // 1x1 conv (or Conv1 / Conv2's implicit GEMM) over an NHWC map of edge Hin
+  auto pw = [&](const Conv& cv, const void* in, int Hin, void* outp, int act, const void* R, const float* scale) {
+    MbGemmArgs g{};
+    const int Ho = (Hin + 2 * cv.pad - cv.KH) / cv.stride + 1;
+    g.A = in; g.lda = cv.Cin;
+    g.Bw = cv.w; g.ldb = cv.Kpad;
+    g.bias = cv.bias; g.scale = scale;
+    g.R = R; g.ldr = cv.N;
+    g.C = outp; g.ldc = cv.N;
+    g.M = B * Ho * Ho; g.N = cv.N; g.K = cv.K;
+    g.H = Hin; g.W = Hin; g.Cin = cv.Cin; g.KH = cv.KH; g.KW = cv.KW; g.stride = cv.stride; g.pad = cv.pad;
+    g.Ho = Ho; g.Wo = Ho;
+    g.act = act;
+    const double a_elems = (double)B * Hin * Hin * cv.Cin;
+    return run_other(m, "conv.pw.mb", 2.0 * g.M * g.N * g.K,
+                     (a_elems + (double)g.N * g.K + (double)g.M * g.N * (R ? 2 : 1)) * E, s,
+                     [&] { return spe_launch_mb_gemm(g, dt, s); });
+  };
+  auto dw = [&](const MbDw& d, const void* in, int Hin, void* outp, int act, float* pool) {
+    MbDwArgs a{};
+    a.in = in; a.out = outp; a.w = d.w; a.bias = d.bias; a.pool = pool;
+    a.B = B; a.H = Hin; a.W = Hin; a.C = d.C; a.k = d.k; a.stride = d.stride; a.act = act;
+    const int Ho = Hin / d.stride;
+    return run_other(m, "conv.dw", 2.0 * B * Ho * Ho * d.C * d.k * d.k,
+                     (double)B * d.C * (Hin * Hin + Ho * Ho) * E, s, [&] { return spe_launch_mb_dwconv(a, dt, s); });
+  };
+  const int H0 = S / 2;
+  CK(run_other(m, "conv.stem.mb", 2.0 * B * H0 * H0 * 16 * 27, (double)B * (S * S * 12.0 + H0 * H0 * 16 * E), s,
+               [&] { return spe_launch_mb_stem(images, mb.stem_w, mb.stem_b, P(w.x0), B, S, dt, s); }));
+  CK(pw(mb.conv_b, P(w.x0), H0, P(w.f0), MB_ACT_HSWISH, nullptr, nullptr));
+  CK(pw(mb.conv_c, P(w.f0), r.lvl_s[0], P(w.f1), MB_ACT_HSWISH, nullptr, nullptr));
+  int H = H0;
+  size_t cur = w.x0;
+  const size_t sc_pw = w.sc + (((w.f0 - w.sc) / 2) & ~size_t(255));   // second half of sc: the skip branch's 1x1 output
+  for (const MbBlock& k : mb.blocks) {
+    const int Ho = H / k.stride;
+    const size_t outbuf = cur == w.bufA ? w.bufB : w.bufA;
+    CK(pw(k.expand, P(cur), H, P(w.t1), k.act, nullptr, nullptr));
+    float* pool = nullptr;
+    const int tiles = spe_mb_dwconv_tiles(Ho, Ho);
+    if (k.se) {
+      if ((size_t)tiles * k.cexp > MB_POOL_MAX) return fail(SPE_E_WORKSPACE, "SE pool partials exceed the plan");
+      pool = (float*)P(w.mbpool);      // rows [B][tiles][C]: B * tiles * C <= B * MB_POOL_MAX floats
+    }
+    CK(dw(k.dw, P(w.t1), H, P(w.t2), k.act, pool));
+    const float* scale = nullptr;
+    if (k.se) {
+      MbSeArgs a{};
+      a.pool = pool; a.tiles = tiles; a.inv_hw = 1.0f / (float)(Ho * Ho);
+      a.w1 = k.se_w1; a.b1 = k.se_b1; a.w2t = k.se_w2t;
+      a.scale = (float*)P(w.mbscale);
+      a.B = B; a.C = k.cexp; a.hidden = k.se_hidden;
+      CK(run_other(m, "rt.se", 4.0 * B * k.cexp * k.se_hidden, ((double)B * (tiles + 1) * k.cexp + 2.0 * k.cexp * k.se_hidden) * 4, s,
+                   [&] { return spe_launch_mb_se_gate(a, s); }));
+      scale = a.scale;
+    }
+    const void* res = P(cur);
+    if (k.has_skip_dw) {
+      CK(dw(k.skip_dw, P(cur), H, P(w.sc), MB_ACT_NONE, nullptr));
+      res = P(w.sc);
+    }
+    if (k.has_skip_pw) {
+      CK(pw(k.skip_pw, res, k.has_skip_dw ? Ho : H, P(sc_pw), MB_ACT_NONE, nullptr, nullptr));
+      res = P(sc_pw);
+    }
+    CK(pw(k.project, P(w.t2), Ho, P(outbuf), k.act, res, scale));
+    H = Ho;
+    cur = outbuf;
+  }
+  CK(pw(mb.last, P(cur), H, P(w.f2), MB_ACT_HSWISH, nullptr, nullptr));
+  return 0;
+}
+
 }  // namespace
 
 int spe_rtdetr_build_device(spe_model* m) {
   RtModel& r = *m->rt;
   const auto& c = r.cfg;
   const int d = 256;
+  r.blocks.clear();
+  if (r.mbv3) {
+    build_mbv3(m);
+    r.fch[0] = 128; r.fch[1] = 256; r.fch[2] = 512;
+  } else {
   const std::string bb = "backbone.conv1.conv1_";
   r.stem[0] = make_conv(m, bb + "1.conv.weight", bb + "1.norm", "", 8, 2, 1);
   r.stem[1] = make_conv(m, bb + "2.conv.weight", bb + "2.norm", "", 0, 1, 1);
   r.stem[2] = make_conv(m, bb + "3.conv.weight", bb + "3.norm", "", 0, 1, 1);
-  r.blocks.clear();
   const bool bott = c.depth >= 50;
   const int* nb = bott ? RESNET_CFG50 : RESNET_CFG18;
   const int widths[4] = {64, 128, 256, 512}, exp = bott ? 4 : 1;
@@ -322,6 +648,8 @@ int spe_rtdetr_build_device(spe_model* m) {
       r.blocks.push_back(b);
       cin = b.cout;
     }
+  }
+  for (int l = 0; l < 3; ++l) r.fch[l] = r.blocks[r.stage_first[l + 1]].cout;
   }
   for (int l = 0; l < 3; ++l) {
     const std::string p = "encoder.input_proj." + std::to_string(l);
@@ -387,11 +715,35 @@ int spe_rtdetr_build_device(spe_model* m) {
 
 int64_t spe_rtdetr_workspace(const spe_model* m, int B) { return (int64_t)rt_plan(m, B).total; }
 
+int spe_rtdetr_backbone(spe_model* m, hipStream_t s, const float* images, int B, void* workspace, int64_t ws_bytes,
+                        const void** f, int* ch, int* hw) {
+  if (!m || !workspace || !images || B <= 0) return fail(SPE_E_ARG, "bad argument");
+  if (m->family != 1) return fail(SPE_E_ARG, "not an RT-DETR model");
+  if (!m->finalized) return fail(SPE_E_STATE, "model not finalized");
+  const RtWs w = rt_plan(m, B);
+  if ((int64_t)w.total > ws_bytes) return fail(SPE_E_WORKSPACE, "workspace too small");
+  const RtModel& r = *m->rt;
+  char* ws = (char*)workspace;
+  CK(r.mbv3 ? rt_backbone_mbv3(m, s, images, B, ws, w) : rt_backbone_presnet(m, s, images, B, ws, w));
+  const size_t off[3] = {w.f0, w.f1, w.f2};
+  for (int l = 0; l < 3; ++l) {
+    if (f) f[l] = ws + off[l];
+    if (ch) ch[l] = r.fch[l];
+    if (hw) hw[l] = r.lvl_s[l];
+  }
+  return 0;
+}
+
 extern "C" {
 
 int spe_rtdetr_create(const spe_rtdetr_config* cfg, spe_model** out) {
   if (!cfg || !out) return fail(SPE_E_ARG, "null argument");
-  if (cfg->depth != 18 && cfg->depth != 50) return fail(SPE_E_ARG, "PResNet depth must be 18 or 50");
+  if (cfg->depth != 18 && cfg->depth != 50 && !is_mbv3(*cfg))
+    return fail(SPE_E_ARG, "depth must be a PResNet depth (18 or 50) or SPE_RTDETR_MBV3_LARGE");
+  if (is_mbv3(*cfg) && cfg->input_size != 256)
+    return fail(SPE_E_ARG, "MobileNetV3_Large supports input_size 256 only: the backbone resizes its stem output to "
+                           "a hard-coded 64x64, which is the stride-4 grid the stride-8 / 16 levels are built from "
+                           "only at 256");
   if (cfg->input_size % 32 || cfg->input_size < 64) return fail(SPE_E_ARG, "input_size must be a multiple of 32, >= 64");
   if (cfg->num_queries < 1 || cfg->num_queries > 64) return fail(SPE_E_ARG, "num_queries must be in [1, 64]");
   if (cfg->dec_layers < 1 || cfg->enc_ff % 64 || cfg->dec_ff % 64 || cfg->csp_hidden % 64 || cfg->csp_hidden < 64 ||
@@ -402,6 +754,7 @@ int spe_rtdetr_create(const spe_rtdetr_config* cfg, spe_model** out) {
   m->family = 1;
   m->rt = new RtModel();
   m->rt->cfg = *cfg;
+  m->rt->mbv3 = is_mbv3(*cfg);
   m->esz = cfg->dtype == SPE_DTYPE_BF16_ ? 2 : 4;
   m->cfg.dtype = cfg->dtype;
   m->cfg.input_size = cfg->input_size;
@@ -435,68 +788,11 @@ int spe_rtdetr_forward(spe_model* m, void* stream, const float* images, int B, v
   char* ws = (char*)workspace;
   auto P = [&](size_t o) { return (void*)(ws + o); };
 
-  // conv as an implicit GEMM, or a plain GEMM over NHWC rows when it is 1x1 / stride 1; the
-  // residual R (same row layout as the output) is added before the activation
-  auto cgemm = [&](const char* kind, const Conv& cv, const void* in, int Hin, void* outp, int ldc, int act,
-                   const void* R) {
-    GemmArgs g;
-    int mode = GEMM_CONV;
-    if (cv.KH == 1 && cv.KW == 1 && cv.stride == 1 && cv.pad == 0) {
-      g = linear_args(cv, in, cv.Cin, B * Hin * Hin, outp, ldc);
-      mode = GEMM_LINEAR;
-    } else {
-      g = conv_args(cv, in, B, Hin, Hin, outp, ldc);
-    }
-    g.act = act;
-    g.R = R; g.ldr = ldc;
-    return run_gemm(m, kind, g, mode, s);
-  };
-
-  // ---------------- PResNet-vd (presnet.py:248-265)
-  CK(run_other(m, "eltwise.pack", 0.0, (double)B * S * S * (12 + 8 * E), s,
-               [&] { return spe_launch_pack_input(images, P(w.x0), B, S, dt, s); }));
-  int H = S;
-  size_t cur = w.x0;
-  const size_t stem_out[3] = {w.bufA, w.bufB, w.bufA};
-  for (int i = 0; i < 3; ++i) {
-    GemmArgs g = conv_args(r.stem[i], P(cur), B, H, H, P(stem_out[i]), r.stem[i].N);
-    g.act = ACT_RELU;
-    CK(run_gemm(m, "rt.conv.stem", g, GEMM_CONV, s));
-    H = g.Ho;
-    cur = stem_out[i];
-  }
-  const int Hp = (H + 2 - 3) / 2 + 1;
-  CK(run_other(m, "eltwise.maxpool", 0.0, (double)B * 64 * (H * H + Hp * Hp) * E, s,
-               [&] { return spe_launch_maxpool3s2(P(cur), P(w.bufB), B, H, H, 64, Hp, Hp, dt, s); }));
-  H = Hp;
-  cur = w.bufB;
-  const size_t feat[3] = {w.f0, w.f1, w.f2};
-  for (int st = 0; st < 4; ++st)
-    for (int j = 0; j < r.stage_n[st]; ++j) {
-      const RtBlock& b = r.blocks[r.stage_first[st] + j];
-      const int Ho = H / b.stride;
-      const bool last = j == r.stage_n[st] - 1;
-      const size_t outbuf = (last && st > 0) ? feat[st - 1] : (cur == w.bufA ? w.bufB : w.bufA);
-      size_t res = cur;
-      if (b.has_sc) {
-        CK(cgemm(b.stride == 2 ? "rt.conv.short" : "rt.conv.1x1", b.sc, P(cur), H, P(w.sc), b.cout, ACT_NONE, nullptr));
-        res = w.sc;
-      }
-      CK(cgemm(b.bottleneck ? "rt.conv.1x1" : "rt.conv.3x3", b.a, P(cur), H, P(w.t1), b.a.N, ACT_RELU, nullptr));
-      const int Ha = (H + 2 * b.a.pad - b.a.KH) / b.a.stride + 1;
-      if (b.bottleneck) {
-        CK(cgemm("rt.conv.3x3", b.b, P(w.t1), Ha, P(w.t2), b.b.N, ACT_RELU, nullptr));
-        CK(cgemm("rt.conv.1x1", b.c, P(w.t2), Ho, P(outbuf), b.cout, ACT_RELU, P(res)));
-      } else {
-        CK(cgemm("rt.conv.3x3", b.b, P(w.t1), Ha, P(outbuf), b.cout, ACT_RELU, P(res)));
-      }
-      H = Ho;
-      cur = outbuf;
-    }
+  CK(r.mbv3 ? rt_backbone_mbv3(m, s, images, B, ws, w) : rt_backbone_presnet(m, s, images, B, ws, w));
 
   // ---------------- HybridEncoder (hybrid_encoder.py:332-401)
   const int s0 = r.lvl_s[0], s1 = r.lvl_s[1], s2 = r.lvl_s[2];
-  const int fch[3] = {r.blocks[r.stage_first[1]].cout, r.blocks[r.stage_first[2]].cout, r.blocks[r.stage_first[3]].cout};
+  const int* fch = r.fch;
   {  // input_proj (1x1 + BN): levels 0 / 1 straight into the second half of their FPN concat
     GemmArgs g0 = linear_args(r.in_proj[0], P(w.f0), fch[0], B * s0 * s0, (char*)P(w.cat0) + d * E, 2 * d);
     CK(run_gemm(m, "rt.enc.proj", g0, GEMM_LINEAR, s));

@@ -388,3 +388,54 @@ struct RtHeadArgs {
   float* log_sigmas; float* sigmas;         // [rows][2]
 };
 int spe_launch_head_finish(const RtHeadArgs& a, int dtype, hipStream_t s);
+
+// ---- MobileNetV3_Large backbone kernels (mbv3.hip).  Every launcher returns -1 before any launch
+// when the shapes are outside its contract, 0 or a hipError_t otherwise.
+enum { MB_ACT_NONE = 0, MB_ACT_RELU = 1, MB_ACT_HSWISH = 4 };   // Hardswish: x relu6(x + 3) / 6
+// conv1 3x3/s2/p1 3 -> 16 + bias + Hardswish from the fp32 NCHW batch [B][3][S][S] (S even) into NHWC T
+// [B][S/2][S/2][16]; w fp32 [27][16] with k = (ci*3 + kh)*3 + kw
+int spe_launch_mb_stem(const float* images, const float* w, const float* bias, void* out, int B, int S, int dtype,
+                       hipStream_t s);
+// depthwise k x k, pad k/2, over NHWC T.  Contract: k 3 or 5; stride 1, or 2 with even H and W (Ho = H /
+// stride); C % 8 == 0; B <= 65535.  w fp32 [k*k][C] (BatchNorm scale folded in), bias fp32 [C].
+// pool (nullable): fp32 [B][spe_mb_dwconv_tiles(Ho, Wo)][C], per 8 x 8 output tile the sum of the
+// stored outputs, reduced in a fixed order (two runs give the same bits).
+struct MbDwArgs {
+  const void* in; void* out;
+  const float* w; const float* bias;
+  float* pool;
+  int B, H, W, C, k, stride, act;
+  int Ho, Wo, cg;                  // set by the launcher
+};
+int spe_mb_dwconv_tiles(int Ho, int Wo);
+bool spe_mb_dwconv_fits(int B, int H, int W, int C, int k, int stride);
+int spe_launch_mb_dwconv(MbDwArgs a, int dtype, hipStream_t s);
+// SE gate: scale[b][c] = hardsigmoid(w2 . relu(w1 . mean_b + b1)) with mean_b[c] = inv_hw * sum over tiles
+// of pool[b][t][c]; w1 fp32 [hidden][C] (BatchNorm folded), b1 [hidden], w2t fp32 [hidden][C] (the second
+// conv's weight transposed).  C <= 1024, hidden <= 256.  fp32 throughout in both model dtypes.
+struct MbSeArgs {
+  const float* pool; int tiles; float inv_hw;
+  const float* w1; const float* b1; const float* w2t;
+  float* scale;
+  int B, C, hidden;
+};
+int spe_launch_mb_se_gate(const MbSeArgs& a, hipStream_t s);
+// C[m][n] = act((A . scale) . W^T + bias + R): A row m = output pixel (b, oy, ox) of an NHWC T tensor
+// [*][H][W][lda >= Cin], column k = (kh*KW + kw)*Cin + ci (zero outside the image); W T [N][ldb]; bias
+// fp32 [N] (nullable); scale fp32 [B][K] (nullable, 1x1 only): A[m][k] * scale[b][k], rounded to T;
+// R T [M][ldr] (nullable), added before the activation.  Contract: N, K, Cin, lda, ldb, ldc, ldr % 8 ==
+// 0; M = B * Ho * Wo.
+struct MbGemmArgs {
+  const void* A; int lda;
+  const void* Bw; int ldb;
+  const float* bias; const float* scale;
+  const void* R; int ldr;
+  void* C; int ldc;
+  int M, N, K;
+  int H, W, Cin, KH, KW, stride, pad, Ho, Wo;
+  int act;
+};
+bool spe_mb_gemm_fits(const MbGemmArgs& g);
+int spe_launch_mb_gemm(const MbGemmArgs& g, int dtype, hipStream_t s);
+// NHWC T [B][HW][C] -> NCHW fp32
+int spe_launch_mb_to_nchw(const void* in, float* out, int B, int HW, int C, int dtype, hipStream_t s);

@@ -25,7 +25,8 @@ from .rtdetr_spec import RtdetrConfig, rtdetr_param_shapes, random_rtdetr_weight
 
 
 class RTDETR(nn.Module):
-    """RTDETR(PResNet-vd, HybridEncoder, RTDETRTransformer) with the sigma head, eval forward.
+    """RTDETR(PResNet-vd | MobileNetV3_Large, HybridEncoder, RTDETRTransformer) with the sigma head, eval
+    forward; cfg.backbone picks the backbone ("mobilenetv3_large": input_size 256 only).
     dtype "bf16": bf16 storage / MFMA with fp32 accumulation, LayerNorm, softmax and heads;
     "fp32": exact-f32 MFMA everywhere (parity path)."""
 
@@ -36,7 +37,8 @@ class RTDETR(nn.Module):
         self._pending = {}
         self._ready = False
         self._ws = {}
-        c = _lib.RtdetrConfig(cfg.depth, cfg.input_size, cfg.num_queries, cfg.dec_layers, cfg.enc_ff, cfg.dec_ff,
+        selector = _lib.SPE_RTDETR_MBV3_LARGE if cfg.backbone == "mobilenetv3_large" else cfg.depth
+        c = _lib.RtdetrConfig(selector, cfg.input_size, cfg.num_queries, cfg.dec_layers, cfg.enc_ff, cfg.dec_ff,
                               cfg.csp_hidden, cfg.num_classes,
                               _lib.SPE_DTYPE_BF16 if dtype == "bf16" else _lib.SPE_DTYPE_F32)
         h = ctypes.c_void_p()
@@ -130,6 +132,19 @@ class RTDETR(nn.Module):
             out["aux_outputs"].append({"pred_logits": el, "pred_pts": ep})
             out["topk"] = topk
         return out
+
+    def backbone_features(self, images, stream=None):
+        """The backbone stage alone (spe_debug_rtdetr_backbone): the stride 8 / 16 / 32 maps as fp32 NCHW."""
+        if not self._ready:
+            raise RuntimeError("RTDETR: load_state_dict() with every parameter before backbone_features()")
+        images = images.contiguous().float()
+        B, dev = images.shape[0], images.device
+        feats = [torch.empty(B, ch, s, s, device=dev) for ch, s in zip(self.cfg.backbone_channels, self.cfg.level_sizes)]
+        ws = self.workspace(B, dev, stream)
+        _lib.check(_lib.lib().spe_debug_rtdetr_backbone(self._h, _lib.stream_ptr(stream), _lib.ptr(images), B, _lib.ptr(ws),
+                                                        ws.numel(), *[_lib.ptr(f) for f in feats]),
+                   "spe_debug_rtdetr_backbone")
+        return feats
 
     def __del__(self):
         try:

@@ -18,6 +18,15 @@ from dataclasses import dataclass, asdict
 
 import numpy as np
 
+BACKBONES = ("presnet", "mobilenetv3_large")
+# MobileNetV3_Large.bneck (UNC/nn/backbone/mobilenetv3.py:148-164): kernel, in, expand, out, hardswish, SE, stride
+MBV3_LARGE_BLOCKS = [
+    (3, 16, 16, 16, False, False, 1), (3, 16, 64, 24, False, False, 2), (3, 24, 72, 24, False, False, 1),
+    (5, 24, 72, 40, False, True, 2), (5, 40, 120, 40, False, True, 1), (5, 40, 120, 40, False, True, 1),
+    (3, 40, 240, 80, True, False, 2), (3, 80, 200, 80, True, False, 1), (3, 80, 184, 80, True, False, 1),
+    (3, 80, 184, 80, True, False, 1), (3, 80, 480, 112, True, True, 1), (3, 112, 672, 112, True, True, 1),
+    (5, 112, 672, 160, True, True, 2), (5, 160, 672, 160, True, True, 1), (5, 160, 960, 160, True, True, 1),
+]
 RESNET_CFG = {18: [2, 2, 2, 2], 34: [3, 4, 6, 3], 50: [3, 4, 6, 3], 101: [3, 4, 23, 3]}   # presnet.py:17-23
 
 
@@ -35,9 +44,16 @@ class RtdetrConfig:
     num_levels: int = 3
     num_points: int = 4             # num_decoder_points
     num_classes: int = 11           # + 1 no-object logit
+    backbone: str = "presnet"       # "presnet" (depth 18 / 50) or "mobilenetv3_large" (depth unused, 256 input only)
+
+    def __post_init__(self):
+        if self.backbone not in BACKBONES:
+            raise ValueError(f"backbone must be one of {BACKBONES}, got {self.backbone!r}")
 
     @property
     def backbone_channels(self):
+        if self.backbone == "mobilenetv3_large":
+            return [128, 256, 512]                  # Conv1 / Conv2 / conv2 outputs (mobilenetv3.py:215-225)
         e = 1 if self.depth < 50 else 4
         return [128 * e, 256 * e, 512 * e]          # return_idx [1, 2, 3]: strides 8, 16, 32
 
@@ -81,11 +97,47 @@ def _mha(p, d):
     return [(f"{p}.in_proj_weight", (3 * d, d)), (f"{p}.in_proj_bias", (3 * d,))] + _lin(f"{p}.out_proj", d, d)
 
 
+def mbv3_large_param_shapes():
+    """MobileNetV3_Large's parameters in registration order (mobilenetv3.py:136-173); linear3 / bn3 are
+    built and never called, their keys are part of the state_dict all the same."""
+    b = "backbone"
+    out = [(f"{b}.conv1.weight", (16, 3, 3, 3))] + _bn(f"{b}.bn1", 16) + _bn(f"{b}.Bn1", 128) + _bn(f"{b}.Bn2", 256)
+    out += [(f"{b}.Conv1.weight", (128, 16, 3, 3)), (f"{b}.Conv2.weight", (256, 128, 3, 3))]
+    for i, (k, cin, ce, cout, _hs, se, stride) in enumerate(MBV3_LARGE_BLOCKS):
+        p = f"{b}.bneck.{i}"
+        out += [(f"{p}.conv1.weight", (ce, cin, 1, 1))] + _bn(f"{p}.bn1", ce)
+        out += [(f"{p}.conv2.weight", (ce, 1, k, k))] + _bn(f"{p}.bn2", ce)
+        if se:
+            h = max(ce // 4, 8)
+            out += [(f"{p}.se.se.1.weight", (h, ce, 1, 1))] + _bn(f"{p}.se.se.2", h)
+            out += [(f"{p}.se.se.4.weight", (ce, h, 1, 1))]
+        out += [(f"{p}.conv3.weight", (cout, ce, 1, 1))] + _bn(f"{p}.bn3", cout)
+        if stride == 1 and cin != cout:
+            out += [(f"{p}.skip.0.weight", (cout, cin, 1, 1))] + _bn(f"{p}.skip.1", cout)
+        elif stride == 2 and cin != cout:
+            out += [(f"{p}.skip.0.weight", (cin, 1, 3, 3))] + _bn(f"{p}.skip.1", cin)
+            out += [(f"{p}.skip.2.weight", (cout, cin, 1, 1)), (f"{p}.skip.2.bias", (cout,))] + _bn(f"{p}.skip.3", cout)
+        elif stride == 2:
+            out += [(f"{p}.skip.0.weight", (cout, 1, 3, 3))] + _bn(f"{p}.skip.1", cout)
+    out += [(f"{b}.conv2.weight", (512, 160, 1, 1))] + _bn(f"{b}.bn2", 512)
+    out += [(f"{b}.linear3.weight", (1280, 960))] + _bn(f"{b}.bn3", 1280)
+    return out
+
+
 def rtdetr_param_shapes(cfg: RtdetrConfig):
     d, C = cfg.hidden_dim, cfg.num_classes + 1
     out = [("temper_param", (1,))]
+    if cfg.backbone == "mobilenetv3_large":
+        out += mbv3_large_param_shapes()
+    else:
+        out += _presnet_param_shapes(cfg)
+    out += _rtdetr_tail_shapes(cfg, d, C)
+    return out
+
+
+def _presnet_param_shapes(cfg):
     # ---- backbone: PResNet variant d (presnet.py:156-230)
-    out += _cnl("backbone.conv1.conv1_1", 3, 32, 3) + _cnl("backbone.conv1.conv1_2", 32, 32, 3)
+    out = _cnl("backbone.conv1.conv1_1", 3, 32, 3) + _cnl("backbone.conv1.conv1_2", 32, 32, 3)
     out += _cnl("backbone.conv1.conv1_3", 32, 64, 3)
     bottleneck = cfg.depth >= 50
     exp = 4 if bottleneck else 1
@@ -106,6 +158,11 @@ def rtdetr_param_shapes(cfg: RtdetrConfig):
                 blk += _cnl(f"{p}.branch2a", cin, cout, 3) + _cnl(f"{p}.branch2b", cout, cout, 3)
                 out += (blk_short if j == 0 else []) + blk
             cin = cout * exp
+    return out
+
+
+def _rtdetr_tail_shapes(cfg, d, C):
+    out = []
     # ---- decoder (RTDETRTransformer, rtdetr_decoder.py:372-505), registered before the encoder
     for lv in range(cfg.num_levels):
         out += _cnl(f"decoder.input_proj.{lv}", d, d, 1)
@@ -147,6 +204,36 @@ def rtdetr_param_shapes(cfg: RtdetrConfig):
     return out
 
 
+def _draw_mbv3(rng, key, shape):
+    """One MobileNetV3_Large backbone parameter: He-normal convs (depthwise: fan-in k*k), non-trivial
+    BatchNorm statistics, the projection norm bn3 damped (gain 0.3) so the residual stream stays O(1)
+    through 15 blocks, norms in front of a Hardswish widened (gain 0.75 .. 1.5) so its inputs reach
+    past -3 and 3, the SE gate's first conv halved and its second doubled so most gate pre-activations
+    stay in (-3, 3) while a few saturate."""
+    if key.endswith("running_mean"):
+        return rng.normal(0.0, 0.1, shape)
+    if key.endswith("running_var"):
+        return rng.uniform(0.5, 1.5, shape)
+    if len(shape) == 4:
+        a = rng.normal(0.0, np.sqrt(2.0 / (shape[1] * shape[2] * shape[3])), shape)
+        return a * 0.5 if ".se.se.1." in key else a * 2.0 if ".se.se.4." in key else a
+    if len(shape) == 2:
+        lim = np.sqrt(6.0 / (shape[0] + shape[1]))
+        return rng.uniform(-lim, lim, shape)
+    if ".skip.2.bias" in key:
+        return rng.normal(0.0, 0.02, shape)
+    if key.endswith("weight"):
+        part = key.split(".")
+        blk = int(part[2]) if part[1] == "bneck" else None
+        name = part[-2]
+        if blk is not None and name == "bn3":
+            return 0.3 * rng.uniform(0.5, 1.0, shape)
+        hswish = (blk is None and name in ("bn1", "Bn1", "Bn2", "bn2")) or \
+                 (blk is not None and blk >= 6 and name in ("bn1", "bn2"))
+        return rng.uniform(0.75, 1.5, shape) if hswish else rng.uniform(0.5, 1.0, shape)
+    return rng.normal(0.0, 0.05, shape)
+
+
 def random_rtdetr_weights(cfg: RtdetrConfig, seed: int = 0):
     """Deterministic random weights (key -> float32 ndarray) that exercise every path: He-normal
     convs with non-trivial BatchNorm statistics (residual gains damped so activations stay O(1)
@@ -154,8 +241,11 @@ def random_rtdetr_weights(cfg: RtdetrConfig, seed: int = 0):
     and outside the value maps) and attention logits, non-zero box/sigma heads."""
     rng = np.random.Generator(np.random.PCG64(seed))
     w = {}
+    mbv3 = cfg.backbone == "mobilenetv3_large"
     for key, shape in rtdetr_param_shapes(cfg):
-        if key.endswith("running_mean"):
+        if mbv3 and key.startswith("backbone."):
+            a = _draw_mbv3(rng, key, shape)
+        elif key.endswith("running_mean"):
             a = rng.normal(0.0, 0.1, shape)
         elif key.endswith("running_var"):
             a = rng.uniform(0.5, 1.5, shape)
