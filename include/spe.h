@@ -115,11 +115,16 @@ typedef struct {
  * size (SPE_E_ARG), as the reference's own hybrid encoder does.  Its never-called linear3 / bn3
  * parameters are part of the key space (accepted and ignored). */
 #define SPE_RTDETR_MBV3_LARGE 1003
+/* spe_rtdetr_config.depth value that selects GhostNetV2 (UNC/nn/backbone/ghostnetv2.py:286-441,
+ * UNC/configs/rtdetr_speed/include/rtdetr_ghostnetv2.yml).  It resizes its raw stem output to the same
+ * hard-coded 64 x 64, so it too is accepted at input_size 256 only (SPE_E_ARG otherwise).  Its never-called
+ * conv_head / classifier parameters are part of the key space (accepted and ignored). */
+#define SPE_RTDETR_GHOSTNETV2 1004
 
 typedef struct {
   int depth;            /* backbone selector: 18 (BasicBlock) or 50 (BottleNeck) = PResNet variant d of that
-                         * depth; SPE_RTDETR_MBV3_LARGE = MobileNetV3_Large */
-  int input_size;       /* eval_spatial_size (256); multiple of 32; MobileNetV3_Large: 256 only */
+                         * depth; SPE_RTDETR_MBV3_LARGE = MobileNetV3_Large; SPE_RTDETR_GHOSTNETV2 = GhostNetV2 */
+  int input_size;       /* eval_spatial_size (256); multiple of 32; MobileNetV3_Large / GhostNetV2: 256 only */
   int num_queries;      /* RTDETRTransformer.num_queries (30), <= 64 */
   int dec_layers;       /* num_decoder_layers (3) */
   int enc_ff;           /* HybridEncoder.dim_feedforward (1024, GELU) */
@@ -488,6 +493,32 @@ int spe_debug_pwconv(void* stream, int dtype, const void* a, int lda, const void
  * [B][C_l][S/8 .. S/32]^2 (C_l = 128, 256, 512, x 4 for depth 50). */
 int spe_debug_rtdetr_backbone(spe_model* m, void* stream, const float* images, int batch, void* workspace,
                               int64_t workspace_bytes, float* f0, float* f1, float* f2);
+
+/* GhostNetV2 backbone kernels (ghostv2.hip, ABI 9 additions).  Every refusal below is SPE_E_ARG before any
+ * launch; dtype BF16_ (fp32 accumulation) or F32_.
+ * ghost_cheap: the second half of a ghost module and what follows it.  x1 is a channel slice of an NHWC
+ * tensor: pixel (b, h, w) at x1 + ((b*H + h)*W + w)*ldx + xoff, `half` channels.  x2 = act(dw3x3(x1) + bias)
+ * (pad 1; w fp32 [9][half] tap-major with the BatchNorm scale folded in, bias fp32 [half]; act 0 none or 1
+ * ReLU).  y [B][H][W][2*half]: y[:half] = post(x1), y[half:] = post(x2) with post 0 nothing, 1 multiply by
+ * gate[b][h/2][w/2][c] (dtype [B][H/2][W/2][2*half]; H and W even) -- the gate applies to the activated
+ * concat, the depthwise conv reads the ungated x1 --, 2 add resid[b][h][w][c] (dtype, y's layout).
+ * pool_partials (nullable): fp32 [B][spe_debug_dwconv_tiles(H, W)][2*half], per 8 x 8 tile the sum of the
+ * stored outputs in a fixed order (two runs give the same bits).  Contract: half, ldx, xoff multiples of 8
+ * (a narrower half is stored padded to 8 with zero weights and bias: its pad lanes come out exactly 0),
+ * ldx >= xoff + half, B <= 65535, y not aliasing x1. */
+int spe_debug_ghost_cheap(void* stream, int dtype, const void* x1, int ldx, int xoff, const float* w, const float* bias,
+                          void* y, const void* gate, const void* resid, float* pool_partials, int B, int H, int W,
+                          int half, int act, int post);
+/* dfc_gate: gate = sigmoid(dw5x1(dw1x5(x) + b1) + b2) over NHWC x [B][H][W][C] -> gate, same shape; w1 / w2
+ * fp32 [5][C] (tap-major: w1 along W, pad 2; w2 along H, pad 2), b1 / b2 fp32 [C]; no activation or rounding
+ * between the two convs.  Contract: H, W <= 32 (the whole map sits in LDS), C % 8 == 0, B <= 65535. */
+int spe_debug_dfc_gate(void* stream, int dtype, const void* x, const float* w1, const float* b1, const float* w2,
+                       const float* b2, void* gate, int B, int H, int W, int C);
+/* se_gate_bias: spe_debug_se_gate with the second conv's bias b2 fp32 [C] added before the Hardsigmoid. */
+int spe_debug_se_gate_bias(void* stream, const float* pool_partials, int tiles, float inv_hw, const float* w1,
+                           const float* b1, const float* w2t, const float* b2, float* scale, int B, int C, int hidden);
+/* pool2: 2 x 2 mean, NHWC x [B][H][W][C] -> y [B][H/2][W/2][C]; H, W even, C % 8 == 0. */
+int spe_debug_pool2(void* stream, int dtype, const void* x, void* y, int B, int H, int W, int C);
 
 #ifdef __cplusplus
 }

@@ -351,4 +351,54 @@ int spe_debug_rtdetr_backbone(spe_model* m, void* stream, const float* images, i
   return 0;
 }
 
+// ---- GhostNetV2 backbone kernels (ghostv2.hip)
+int spe_debug_ghost_cheap(void* stream, int dtype, const void* x1, int ldx, int xoff, const float* w, const float* bias,
+                          void* y, const void* gate, const void* resid, float* pool_partials, int B, int H, int W,
+                          int half, int act, int post) {
+  if (!x1 || !w || !bias || !y) return spe_fail(SPE_E_ARG, "null argument");
+  if (dtype != SPE_DTYPE_BF16 && dtype != SPE_DTYPE_F32) return spe_fail(SPE_E_ARG, "bad dtype");
+  GhCheapArgs a{};
+  a.x1 = x1; a.ldx = ldx; a.xoff = xoff; a.w = w; a.bias = bias; a.out = y; a.gate = gate; a.resid = resid;
+  a.pool = pool_partials;
+  a.B = B; a.H = H; a.W = W; a.half = half; a.act = act; a.post = post;
+  if (!spe_gh_cheap_fits(a))
+    return spe_fail(SPE_E_ARG, "ghost_cheap: half, ldx, xoff must be multiples of 8 (ldx >= xoff + half), act 0 / 1, post 0 / "
+                               "1 / 2, even H and W under the gate");
+  if ((post == GH_POST_GATE && !gate) || (post == GH_POST_RESIDUAL && !resid))
+    return spe_fail(SPE_E_ARG, "ghost_cheap: post 1 needs gate, post 2 needs resid");
+  const int rc = spe_launch_gh_cheap(a, dtype, (hipStream_t)stream);
+  return rc < 0 ? spe_fail(SPE_E_LAUNCH, "ghost_cheap launch rejected its arguments") : rc;
+}
+
+int spe_debug_dfc_gate(void* stream, int dtype, const void* x, const float* w1, const float* b1, const float* w2,
+                       const float* b2, void* gate, int B, int H, int W, int C) {
+  if (!x || !w1 || !b1 || !w2 || !b2 || !gate) return spe_fail(SPE_E_ARG, "null argument");
+  if (dtype != SPE_DTYPE_BF16 && dtype != SPE_DTYPE_F32) return spe_fail(SPE_E_ARG, "bad dtype");
+  if (!spe_gh_dfc_fits(B, H, W, C)) return spe_fail(SPE_E_ARG, "dfc_gate: H, W <= 32, C a multiple of 8");
+  GhDfcArgs a{};
+  a.x = x; a.gate = gate; a.w1 = w1; a.b1 = b1; a.w2 = w2; a.b2 = b2;
+  a.B = B; a.H = H; a.W = W; a.C = C;
+  const int rc = spe_launch_gh_dfc(a, dtype, (hipStream_t)stream);
+  return rc < 0 ? spe_fail(SPE_E_LAUNCH, "dfc_gate launch rejected its arguments") : rc;
+}
+
+int spe_debug_se_gate_bias(void* stream, const float* pool_partials, int tiles, float inv_hw, const float* w1,
+                           const float* b1, const float* w2t, const float* b2, float* scale, int B, int C, int hidden) {
+  if (!b2) return spe_fail(SPE_E_ARG, "null argument");
+  MbSeArgs a{};
+  a.pool = pool_partials; a.tiles = tiles; a.inv_hw = inv_hw;
+  a.w1 = w1; a.b1 = b1; a.w2t = w2t; a.b2 = b2; a.scale = scale;
+  a.B = B; a.C = C; a.hidden = hidden;
+  const int rc = spe_launch_mb_se_gate(a, (hipStream_t)stream);
+  return rc < 0 ? spe_fail(SPE_E_ARG, "se_gate_bias: null argument, C > 1024 or hidden > 256") : rc;
+}
+
+int spe_debug_pool2(void* stream, int dtype, const void* x, void* y, int B, int H, int W, int C) {
+  if (!x || !y) return spe_fail(SPE_E_ARG, "null argument");
+  if (dtype != SPE_DTYPE_BF16 && dtype != SPE_DTYPE_F32) return spe_fail(SPE_E_ARG, "bad dtype");
+  if (!spe_gh_pool2_fits(B, H, W, C)) return spe_fail(SPE_E_ARG, "pool2: H and W must be even, C a multiple of 8");
+  const int rc = spe_launch_gh_pool2(x, y, B, H, W, C, dtype, (hipStream_t)stream);
+  return rc < 0 ? spe_fail(SPE_E_LAUNCH, "pool2 launch rejected its arguments") : rc;
+}
+
 }  // extern "C"

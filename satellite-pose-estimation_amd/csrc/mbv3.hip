@@ -7,8 +7,8 @@
 //                patch with its halo staged once in LDS; optionally the per-(image, tile, channel) sums
 //                of the stored outputs, reduced in a fixed order (no floating-point atomics): the SE
 //                gate's pool without a second pass over the expanded tensor
-//   mb_se_gate   pooled mean -> fc1 + folded BN + ReLU -> fc2 -> Hardsigmoid -> fp32 [B][C] scales, one
-//                work-group per image, one launch per block
+//   mb_se_gate   pooled mean -> fc1 + folded BN + ReLU -> fc2 (+ bias, GhostNetV2) -> Hardsigmoid -> fp32 [B][C]
+//                scales, one work-group per image, one launch per block
 //   mb_gemm      C = act((A * scale) . W^T + bias + R): the 1x1 convolutions (expand, project, skip) and,
 //                through the implicit-GEMM A loader, Conv1 / Conv2; the SE scale is applied to the A
 //                operand while it is staged, the residual is added BEFORE the activation
@@ -172,6 +172,7 @@ __global__ __launch_bounds__(256) void mb_se_gate_kernel(MbSeArgs a) {
     float p = 0.f;
 #pragma unroll 8
     for (int j = 0; j < Hd; ++j) p = fmaf(a.w2t[(size_t)j * C + c], hid[j], p);   // (loads of 8 rows in flight)
+    if (a.b2) p += a.b2[c];
     a.scale[(size_t)b * C + c] = fminf(fmaxf(p + 3.f, 0.f), 6.f) / 6.f;
   }
 }

@@ -127,10 +127,38 @@ struct RtMbv3 {
   Conv conv_b, conv_c, last;   // Conv1 with the 2x2 mean folded in (6x6 / s4 / p2 over the stem output), Conv2, conv2
   std::vector<MbBlock> blocks;
 };
+// GhostNetV2 backbone (UNC/nn/backbone/ghostnetv2.py:88-441), BatchNorm folded everywhere.  A ghost tensor of
+// C channels is stored as two halves of pad8(C / 2) lanes each; the pad lanes hold exactly 0 (zero weights and
+// biases produce them, zero K columns / depthwise taps consume them).
+struct GhModule {            // GhostModuleV2: primary 1x1 (rows [half_p][Kpad]) + cheap depthwise 3x3
+  Conv primary;
+  float *cheap_w = nullptr, *cheap_b = nullptr;   // [9][half_p], [half_p]
+  int half_p = 0;
+  bool attn = false;         // mode "attn": short_conv = 1x1 (BN folded) -> gh_dfc
+  Conv short_pw;
+  float *dfc_w1 = nullptr, *dfc_b1 = nullptr, *dfc_w2 = nullptr, *dfc_b2 = nullptr;   // [5][2 half_p], [2 half_p]
+};
+struct GhBlock {             // GhostBottleneckV2
+  GhModule g1, g2;
+  MbDw dw, sc_dw;            // conv_dw + bn_dw (stride 2), shortcut.0 + .1
+  Conv sc_pw;                // shortcut.2 + .3
+  float *se_w1 = nullptr, *se_b1 = nullptr, *se_w2t = nullptr, *se_b2 = nullptr;   // [hid][mid_p], [hid], [hid][mid_p], [mid_p]
+  int se_hidden = 0;
+  int cin_p = 0, mid_p = 0, cout_p = 0, k = 3, stride = 1;
+  bool se = false, has_sc = false;
+};
+struct RtGhost {
+  float *stem_w = nullptr, *stem_scale = nullptr, *stem_shift = nullptr;   // conv_stem [27][16]; bn1 as scale / shift [16]
+  Conv conv_b, conv_c, head, last;   // Conv1 with the 2x2 mean folded in (6x6 / s4 / p2 over the raw stem output), Conv2,
+                                     // blocks.9.0 (160 -> 960, ReLU), Conv3
+  std::vector<GhBlock> blocks;
+};
 struct RtModel {
   spe_rtdetr_config cfg{};
   bool mbv3 = false;                    // cfg.depth == SPE_RTDETR_MBV3_LARGE
   RtMbv3 mb;
+  bool ghost = false;                   // cfg.depth == SPE_RTDETR_GHOSTNETV2
+  RtGhost gh;
   int fch[3] = {0, 0, 0};               // backbone output channels (the hybrid encoder's in_channels)
   int L = 0, lvl_s[3] = {0, 0, 0}, lvl_start[4] = {0, 0, 0, 0};
   Conv stem[3];

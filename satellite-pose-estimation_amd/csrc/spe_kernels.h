@@ -413,11 +413,13 @@ int spe_launch_mb_dwconv(MbDwArgs a, int dtype, hipStream_t s);
 // SE gate: scale[b][c] = hardsigmoid(w2 . relu(w1 . mean_b + b1)) with mean_b[c] = inv_hw * sum over tiles
 // of pool[b][t][c]; w1 fp32 [hidden][C] (BatchNorm folded), b1 [hidden], w2t fp32 [hidden][C] (the second
 // conv's weight transposed).  C <= 1024, hidden <= 256.  fp32 throughout in both model dtypes.
+// b2 (nullable, last so that older initialisers leave it null): fp32 [C], the second conv's bias (GhostNetV2).
 struct MbSeArgs {
   const float* pool; int tiles; float inv_hw;
   const float* w1; const float* b1; const float* w2t;
   float* scale;
   int B, C, hidden;
+  const float* b2;
 };
 int spe_launch_mb_se_gate(const MbSeArgs& a, hipStream_t s);
 // C[m][n] = act((A . scale) . W^T + bias + R): A row m = output pixel (b, oy, ox) of an NHWC T tensor
@@ -439,3 +441,42 @@ bool spe_mb_gemm_fits(const MbGemmArgs& g);
 int spe_launch_mb_gemm(const MbGemmArgs& g, int dtype, hipStream_t s);
 // NHWC T [B][HW][C] -> NCHW fp32
 int spe_launch_mb_to_nchw(const void* in, float* out, int B, int HW, int C, int dtype, hipStream_t s);
+
+// ---- GhostNetV2 backbone kernels (ghostv2.hip).  Every launcher returns -1 before any launch when the
+// shapes are outside its contract, 0 or a hipError_t otherwise.
+enum { GH_POST_NONE = 0, GH_POST_GATE = 1, GH_POST_RESIDUAL = 2 };
+// conv_stem 3x3/s2/p1 3 -> 16 from the fp32 NCHW batch [B][3][S][S] (S even) into two NHWC T tensors
+// [B][S/2][S/2][16]: raw = the conv output, act = relu(raw * scale + shift) (bn1 folded); w fp32 [27][16]
+int spe_launch_gh_stem(const float* images, const float* w, const float* scale, const float* shift, void* raw, void* act,
+                       int B, int S, int dtype, hipStream_t s);
+// Ghost module tail.  x1: NHWC T, pixel stride ldx, channels [xoff, xoff + half); x2 = act(dw3x3(x1) + bias),
+// w fp32 [9][half] (BatchNorm folded), act none / ReLU.  out T [B][H][W][2 half]: out[:half] = post(x1),
+// out[half:] = post(x2); post GATE: * gate[b][h/2][w/2][c] (T [B][H/2][W/2][2 half], H and W even), post
+// RESIDUAL: + resid[b][h][w][c] (T, out's layout).  pool (nullable): fp32 [B][spe_gh_cheap_tiles(H, W)][2 half],
+// per 8 x 8 tile the sum of the stored outputs in a fixed order.  Contract: half, ldx, xoff % 8 == 0,
+// ldx >= xoff + half, B <= 65535.  out must not alias x1.
+struct GhCheapArgs {
+  const void* x1; int ldx, xoff;
+  const float* w; const float* bias;
+  void* out;
+  const void* gate; const void* resid;
+  float* pool;
+  int B, H, W, half, act, post;
+  int cg;                          // set by the launcher
+};
+int spe_gh_cheap_tiles(int H, int W);
+bool spe_gh_cheap_fits(const GhCheapArgs& a);
+int spe_launch_gh_cheap(GhCheapArgs a, int dtype, hipStream_t s);
+// DFC gate: gate = sigmoid(dw5x1(dw1x5(x) + b1) + b2) over NHWC T [B][H][W][C], H, W <= 32, C % 8 == 0;
+// w1 / w2 fp32 [5][C] (tap-major, BatchNorm folded), b1 / b2 fp32 [C]; zero padding on both convs' inputs
+struct GhDfcArgs {
+  const void* x; void* gate;
+  const float* w1; const float* b1; const float* w2; const float* b2;
+  int B, H, W, C;
+  int cg;                          // set by the launcher
+};
+bool spe_gh_dfc_fits(int B, int H, int W, int C);
+int spe_launch_gh_dfc(GhDfcArgs a, int dtype, hipStream_t s);
+// 2x2 mean, NHWC T [B][H][W][C] -> [B][H/2][W/2][C]; H, W even, C % 8 == 0
+bool spe_gh_pool2_fits(int B, int H, int W, int C);
+int spe_launch_gh_pool2(const void* in, void* out, int B, int H, int W, int C, int dtype, hipStream_t s);

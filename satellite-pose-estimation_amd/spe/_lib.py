@@ -38,6 +38,8 @@ D = ctypes.c_double
 
 SPE_DTYPE_BF16, SPE_DTYPE_F32, SPE_DTYPE_F16, SPE_DTYPE_F32X3, SPE_DTYPE_F32X6, SPE_DTYPE_F32H3 = 0, 1, 2, 4, 5, 6
 SPE_RTDETR_MBV3_LARGE = 1003     # spe_rtdetr_config.depth: MobileNetV3_Large instead of a PResNet depth
+SPE_RTDETR_GHOSTNETV2 = 1004     # spe_rtdetr_config.depth: GhostNetV2
+GH_POST_NONE, GH_POST_GATE, GH_POST_RESIDUAL = 0, 1, 2
 MB_ACT_NONE, MB_ACT_RELU, MB_ACT_HSWISH = 0, 1, 4
 SPE_STAGE_ENCODE, SPE_STAGE_DECODE, SPE_STAGE_BACKBONE, SPE_STAGE_TRANSFORMER = 1, 2, 4, 8
 SPE_PNP_EPNP, SPE_PNP_RANSAC_P3P_LM, SPE_PNP_EPNP_RANSAC_SIGMA, SPE_PNP_EPNP_LM, SPE_PNP_EPNP_CERES = 0, 1, 2, 3, 4
@@ -50,7 +52,8 @@ EXPORTS = ["spe_abi_version", "spe_last_error", "spe_model_create", "spe_model_d
            "spe_model_profile_end", "spe_model_profile_get", "spe_debug_gemm", "spe_debug_gemm_path", "spe_debug_gemm_h3", "spe_debug_ffn_h3", "spe_debug_ffn_h3_perm", "spe_debug_gemm_planes", "spe_debug_attention",
            "spe_debug_layernorm", "spe_debug_ffn", "spe_debug_xattn", "spe_debug_xattn_h3", "spe_debug_upconv", "spe_debug_btail", "spe_debug_decsa", "spe_debug_decproj", "spe_debug_decxproj", "spe_debug_wfrag_pack", "spe_debug_decffn", "spe_debug_decq", "spe_debug_btail_perm", "spe_debug_stempool", "spe_rtdetr_create", "spe_rtdetr_forward",
            "spe_jpeg_workspace_bytes", "spe_jpeg_decode",
-           "spe_debug_dwconv_tiles", "spe_debug_dwconv", "spe_debug_se_gate", "spe_debug_pwconv", "spe_debug_rtdetr_backbone"]
+           "spe_debug_dwconv_tiles", "spe_debug_dwconv", "spe_debug_se_gate", "spe_debug_pwconv", "spe_debug_rtdetr_backbone",
+           "spe_debug_ghost_cheap", "spe_debug_dfc_gate", "spe_debug_se_gate_bias", "spe_debug_pool2"]
 
 
 class ModelConfig(ctypes.Structure):
@@ -148,6 +151,10 @@ def load(path: str):
     L.spe_debug_se_gate.argtypes = [P, P, I, F, P, P, P, P, I, I, I]
     L.spe_debug_pwconv.argtypes = [P, I, P, I, P, I, P, P, I, P, I, P, I, I, I, I, I]
     L.spe_debug_rtdetr_backbone.argtypes = [P, P, P, I, P, I64, P, P, P]
+    L.spe_debug_ghost_cheap.argtypes = [P, I, P, I, I, P, P, P, P, P, P, I, I, I, I, I, I]
+    L.spe_debug_dfc_gate.argtypes = [P, I, P, P, P, P, P, P, I, I, I, I]
+    L.spe_debug_se_gate_bias.argtypes = [P, P, I, F, P, P, P, P, P, I, I, I]
+    L.spe_debug_pool2.argtypes = [P, I, P, P, I, I, I, I]
     L.spe_jpeg_workspace_bytes.argtypes = [I, I, I, I64]
     L.spe_jpeg_workspace_bytes.restype = I64
     L.spe_jpeg_decode.argtypes = [P, P, P, P, I, I, I, I64, P, P, P, I64]

@@ -18,7 +18,7 @@ from dataclasses import dataclass, asdict
 
 import numpy as np
 
-BACKBONES = ("presnet", "mobilenetv3_large")
+BACKBONES = ("presnet", "mobilenetv3_large", "ghostnetv2")
 # MobileNetV3_Large.bneck (UNC/nn/backbone/mobilenetv3.py:148-164): kernel, in, expand, out, hardswish, SE, stride
 MBV3_LARGE_BLOCKS = [
     (3, 16, 16, 16, False, False, 1), (3, 16, 64, 24, False, False, 2), (3, 24, 72, 24, False, False, 1),
@@ -27,6 +27,37 @@ MBV3_LARGE_BLOCKS = [
     (3, 80, 184, 80, True, False, 1), (3, 80, 480, 112, True, True, 1), (3, 112, 672, 112, True, True, 1),
     (5, 112, 672, 160, True, True, 2), (5, 160, 672, 160, True, True, 1), (5, 160, 960, 160, True, True, 1),
 ]
+# GhostNetV2.cfgs at width 1.0 (UNC/nn/backbone/ghostnetv2.py:297-319), one row a block in layer_id order:
+# dw kernel, mid (expansion) width, out width, SE ratio, stride.  Blocks 0-1 build ghost1 in mode "original",
+# blocks >= 2 in mode "attn" (the DFC branch); the stem and every block's input width chain from 16.
+GHOSTV2_BLOCKS = [
+    (3, 16, 16, 0, 1), (3, 48, 24, 0, 2), (3, 72, 24, 0, 1), (5, 72, 40, 0.25, 2), (5, 120, 40, 0.25, 1),
+    (3, 240, 80, 0, 2), (3, 200, 80, 0, 1), (3, 184, 80, 0, 1), (3, 184, 80, 0, 1), (3, 480, 112, 0.25, 1),
+    (3, 672, 112, 0.25, 1), (5, 672, 160, 0.25, 2), (5, 960, 160, 0, 1), (5, 960, 160, 0.25, 1), (5, 960, 160, 0, 1),
+    (5, 960, 160, 0.25, 1),
+]
+GHOSTV2_STAGES = [1, 1, 1, 1, 1, 1, 5, 1, 4]       # blocks per nn.Sequential stage: the key is blocks.{stage}.{j}
+GHOSTV2_ATTN_FROM = 2                              # layer_id <= 1: ghost1 mode "original", else "attn"
+
+
+def ghostv2_se_width(mid):
+    """SqueezeExcite's reduced width, _make_divisible(mid * 0.25, 4) (ghostnetv2.py:21-34, 57): 20, 32, 120, 168, 240."""
+    v = mid * 0.25
+    n = max(4, int(v + 2) // 4 * 4)
+    return n + 4 if n < 0.9 * v else n
+
+
+def ghostv2_block_keys():
+    """(layer_id, key prefix, in width) of the 16 blocks."""
+    out, cin, lid = [], 16, 0
+    for st, n in enumerate(GHOSTV2_STAGES):
+        for j in range(n):
+            out.append((lid, f"backbone.blocks.{st}.{j}", cin))
+            cin = GHOSTV2_BLOCKS[lid][2]
+            lid += 1
+    return out
+
+
 RESNET_CFG = {18: [2, 2, 2, 2], 34: [3, 4, 6, 3], 50: [3, 4, 6, 3], 101: [3, 4, 23, 3]}   # presnet.py:17-23
 
 
@@ -44,7 +75,7 @@ class RtdetrConfig:
     num_levels: int = 3
     num_points: int = 4             # num_decoder_points
     num_classes: int = 11           # + 1 no-object logit
-    backbone: str = "presnet"       # "presnet" (depth 18 / 50) or "mobilenetv3_large" (depth unused, 256 input only)
+    backbone: str = "presnet"       # "presnet" (depth 18 / 50), "mobilenetv3_large" or "ghostnetv2" (depth unused, 256 input only)
 
     def __post_init__(self):
         if self.backbone not in BACKBONES:
@@ -54,6 +85,8 @@ class RtdetrConfig:
     def backbone_channels(self):
         if self.backbone == "mobilenetv3_large":
             return [128, 256, 512]                  # Conv1 / Conv2 / conv2 outputs (mobilenetv3.py:215-225)
+        if self.backbone == "ghostnetv2":
+            return [128, 256, 512]                  # Conv1 / Conv2 / Conv3 outputs (ghostnetv2.py:339-341)
         e = 1 if self.depth < 50 else 4
         return [128 * e, 256 * e, 512 * e]          # return_idx [1, 2, 3]: strides 8, 16, 32
 
@@ -124,11 +157,52 @@ def mbv3_large_param_shapes():
     return out
 
 
+def _ghost_module(p, cin, cout, attn):
+    """GhostModuleV2 (ghostnetv2.py:88-186): primary 1x1 to ceil(cout / 2), cheap depthwise 3x3 on it, and in
+    mode "attn" short_conv = 1x1 + BN, depthwise 1x5 + BN, depthwise 5x1 + BN at full width."""
+    h = -(-cout // 2)
+    out = [(f"{p}.primary_conv.0.weight", (h, cin, 1, 1))] + _bn(f"{p}.primary_conv.1", h)
+    out += [(f"{p}.cheap_operation.0.weight", (h, 1, 3, 3))] + _bn(f"{p}.cheap_operation.1", h)
+    if attn:
+        out += [(f"{p}.short_conv.0.weight", (cout, cin, 1, 1))] + _bn(f"{p}.short_conv.1", cout)
+        out += [(f"{p}.short_conv.2.weight", (cout, 1, 1, 5))] + _bn(f"{p}.short_conv.3", cout)
+        out += [(f"{p}.short_conv.4.weight", (cout, 1, 5, 1))] + _bn(f"{p}.short_conv.5", cout)
+    return out
+
+
+def ghostv2_param_shapes():
+    """GhostNetV2's parameters in registration order (ghostnetv2.py:331-387); conv_head and classifier are
+    built and never called, their keys are part of the state_dict all the same."""
+    b = "backbone"
+    out = _bn(f"{b}.Bn1", 128) + _bn(f"{b}.Bn2", 256) + _bn(f"{b}.Bn3", 512)
+    out += [(f"{b}.Conv1.weight", (128, 16, 3, 3)), (f"{b}.Conv2.weight", (256, 128, 3, 3)),
+            (f"{b}.Conv3.weight", (512, 960, 1, 1)), (f"{b}.conv_stem.weight", (16, 3, 3, 3))] + _bn(f"{b}.bn1", 16)
+    for lid, p, cin in ghostv2_block_keys():
+        k, mid, cout, se, stride = GHOSTV2_BLOCKS[lid]
+        out += _ghost_module(f"{p}.ghost1", cin, mid, lid >= GHOSTV2_ATTN_FROM)
+        if stride > 1:
+            out += [(f"{p}.conv_dw.weight", (mid, 1, k, k))] + _bn(f"{p}.bn_dw", mid)
+        if se:
+            r = ghostv2_se_width(mid)
+            out += [(f"{p}.se.conv_reduce.weight", (r, mid, 1, 1)), (f"{p}.se.conv_reduce.bias", (r,)),
+                    (f"{p}.se.conv_expand.weight", (mid, r, 1, 1)), (f"{p}.se.conv_expand.bias", (mid,))]
+        out += _ghost_module(f"{p}.ghost2", mid, cout, False)
+        if not (cin == cout and stride == 1):
+            out += [(f"{p}.shortcut.0.weight", (cin, 1, k, k))] + _bn(f"{p}.shortcut.1", cin)
+            out += [(f"{p}.shortcut.2.weight", (cout, cin, 1, 1))] + _bn(f"{p}.shortcut.3", cout)
+    out += [(f"{b}.blocks.9.0.conv.weight", (960, 160, 1, 1))] + _bn(f"{b}.blocks.9.0.bn1", 960)
+    out += [(f"{b}.conv_head.weight", (1280, 960, 1, 1)), (f"{b}.conv_head.bias", (1280,))]
+    out += _lin(f"{b}.classifier", 1000, 1280)
+    return out
+
+
 def rtdetr_param_shapes(cfg: RtdetrConfig):
     d, C = cfg.hidden_dim, cfg.num_classes + 1
     out = [("temper_param", (1,))]
     if cfg.backbone == "mobilenetv3_large":
         out += mbv3_large_param_shapes()
+    elif cfg.backbone == "ghostnetv2":
+        out += ghostv2_param_shapes()
     else:
         out += _presnet_param_shapes(cfg)
     out += _rtdetr_tail_shapes(cfg, d, C)
@@ -234,6 +308,43 @@ def _draw_mbv3(rng, key, shape):
     return rng.normal(0.0, 0.05, shape)
 
 
+GH_RES_GAIN = 0.6      # gain of ghost2's norms and of the shortcut's last norm (see _draw_ghostv2)
+
+
+def _draw_ghostv2(rng, key, shape):
+    """One GhostNetV2 backbone parameter: He-normal convs (depthwise: fan-in k*k), non-trivial BatchNorm
+    statistics.  ghost2 has no activation in front of the residual add, so its two norms are damped (gain
+    GH_RES_GAIN) to keep the residual stream O(1-10) through 16 blocks, and so is the shortcut's last norm.
+    The DFC branch's last norm is widened so the sigmoid's pre-activations reach its saturated ends while
+    most stay in its linear region; the SE convs carry biases, the second conv is doubled and its bias
+    spread so the Hardsigmoid's pre-activations lie on both sides of -3 and 3."""
+    if key.endswith("running_mean"):
+        return rng.normal(0.0, 0.1, shape)
+    if key.endswith("running_var"):
+        return rng.uniform(0.5, 1.5, shape)
+    if len(shape) == 4:
+        a = rng.normal(0.0, np.sqrt(2.0 / (shape[1] * shape[2] * shape[3])), shape)
+        return a * 2.0 if ".se.conv_expand." in key else a
+    if len(shape) == 2:
+        lim = np.sqrt(6.0 / (shape[0] + shape[1]))
+        return rng.uniform(-lim, lim, shape)
+    if ".se.conv_reduce.bias" in key:
+        return rng.normal(0.0, 0.1, shape)
+    if ".se.conv_expand.bias" in key:
+        return rng.normal(0.0, 1.5, shape)
+    if key.endswith("weight"):
+        if ".ghost2." in key or ".shortcut.3." in key:
+            return GH_RES_GAIN * rng.uniform(0.5, 1.0, shape)
+        if ".short_conv.5." in key:
+            return rng.uniform(2.0, 4.0, shape)
+        if key.split(".")[1] in ("Bn1", "Bn2", "Bn3"):
+            return rng.uniform(0.75, 1.5, shape)
+        return rng.uniform(0.5, 1.0, shape)
+    if ".short_conv.5." in key:
+        return rng.normal(0.0, 0.5, shape)
+    return rng.normal(0.0, 0.05, shape)
+
+
 def random_rtdetr_weights(cfg: RtdetrConfig, seed: int = 0):
     """Deterministic random weights (key -> float32 ndarray) that exercise every path: He-normal
     convs with non-trivial BatchNorm statistics (residual gains damped so activations stay O(1)
@@ -245,6 +356,8 @@ def random_rtdetr_weights(cfg: RtdetrConfig, seed: int = 0):
     for key, shape in rtdetr_param_shapes(cfg):
         if mbv3 and key.startswith("backbone."):
             a = _draw_mbv3(rng, key, shape)
+        elif cfg.backbone == "ghostnetv2" and key.startswith("backbone."):
+            a = _draw_ghostv2(rng, key, shape)
         elif key.endswith("running_mean"):
             a = rng.normal(0.0, 0.1, shape)
         elif key.endswith("running_var"):

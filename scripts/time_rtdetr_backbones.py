@@ -1,7 +1,8 @@
-"""bf16 forward of the RT-DETR model at B = 64 behind MobileNetV3_Large and PResNet-vd r18: ms per step (HIP
+"""bf16 forward of the RT-DETR model at B = 64 behind GhostNetV2, MobileNetV3_Large and PResNet-vd r18: ms per step (HIP
 events, median of 5 x 20 steps after 10 warm-up steps) and the per-kind launch table of the built-in profiler
 (spe_model_profile_*).  Run from the repository root; writes bench_out/time_rtdetr_backbones.json
-(profiles/r7_rtdetr_mbv3l_vs_r18_b64.json is one such run)."""
+(profiles/r7_rtdetr_mbv3l_vs_r18_b64.json and profiles/r8_rtdetr_backbones_b64.json are such runs; the latter has
+all three backbones and, per backbone, backbone_ms / backbone_share: the launch kinds up to the hybrid encoder)."""
 import ctypes, json, os, sys
 sys.path[:0] = ["satellite-pose-estimation_amd", "oracle", "tests"]
 import numpy as np, torch
@@ -12,7 +13,13 @@ from spe.rtdetr_spec import RtdetrConfig, random_rtdetr_weights
 dev = torch.device("cuda:0")
 B = 64
 out = {}
-for name, cfg in (("mbv3l", RtdetrConfig(backbone="mobilenetv3_large")), ("r18", RtdetrConfig(depth=18))):
+# launch kinds of the backbone stage (r18: rt.conv.1x1 / rt.conv.3x3 are shared with the hybrid encoder's CSP
+# layers, so its figure is an upper bound)
+BACKBONE_KINDS = {"ghostv2": ("conv.stem.gh", "conv.pw.mb", "conv.dw", "rt.se", "conv.ghost", "conv.dfc", "eltwise.pool2"),
+                  "mbv3l": ("conv.stem.mb", "conv.pw.mb", "conv.dw", "rt.se"),
+                  "r18": ("eltwise.pack", "rt.conv.stem", "eltwise.maxpool", "rt.conv.short", "rt.conv.1x1", "rt.conv.3x3")}
+for name, cfg in (("ghostv2", RtdetrConfig(backbone="ghostnetv2")), ("mbv3l", RtdetrConfig(backbone="mobilenetv3_large")),
+                  ("r18", RtdetrConfig(depth=18))):
     m = RTDETR(cfg, "bf16", aux_outputs=False)
     m.load_state_dict(random_rtdetr_weights(cfg, 1))
     x = torch.randn(B, 3, 256, 256, device=dev)
@@ -44,9 +51,12 @@ for name, cfg in (("mbv3l", RtdetrConfig(backbone="mobilenetv3_large")), ("r18",
     out[name] = {"ms_per_step_median": float(np.median(ms)), "ms_all": ms, "img_per_s": B / float(np.median(ms)) * 1e3,
                  "kinds": {k: {"launches": v[0] // 5, "ms": v[1], "gflops": v[2] / 1e9, "mbytes": v[3] / 1e6,
                                "gb_per_s": v[3] / max(v[1], 1e-9) / 1e6} for k, v in sorted(kinds.items())}}
+    bb = sum(v["ms"] for k, v in out[name]["kinds"].items() if k in BACKBONE_KINDS[name])
+    out[name]["backbone_ms"] = bb
+    out[name]["backbone_share"] = bb / max(sum(v["ms"] for v in out[name]["kinds"].values()), 1e-9)
 os.makedirs("bench_out", exist_ok=True)
 json.dump(out, open("bench_out/time_rtdetr_backbones.json", "w"), indent=1)
 for n, r in out.items():
-    print(n, "ms/step", r["ms_per_step_median"], "img/s", r["img_per_s"])
+    print(n, "ms/step", r["ms_per_step_median"], "img/s", r["img_per_s"], "backbone ms", r["backbone_ms"], "share", r["backbone_share"])
     for k, v in r["kinds"].items():
         print("   %-18s n=%3d  %8.3f ms  %8.1f GB/s" % (k, v["launches"], v["ms"], v["gb_per_s"]))

@@ -1,0 +1,163 @@
+"""Golden-vector generator for the UNC RT-DETR model behind the GhostNetV2 backbone
+(UNC/configs/rtdetr_speed/include/rtdetr_ghostnetv2.yml).  Runs ONLY where the reference checkout
+exists (the build machine); the test-suite reads what it wrote.
+
+The reference's own model files are loaded through oracle/gen_golden_rtdetr.py's import_reference /
+_load helpers, UNC/nn/backbone/ghostnetv2.py the same way.  That file imports
+timm.models.registry.register_model, which is not needed to build the model: a stand-in module with an
+identity decorator is put into sys.modules first.  Only numbers and key names are written:
+
+  tests/golden/rtdetr_keys_ghostv2.json : the reference model's state_dict keys and shapes
+  tests/golden/rtdetr_ghostv2_s256.npz  : the record of the other RT-DETR goldens (config, seeds, input
+      checksum, outputs, aux layers, encoder top-k, topk_ind, per-stage checksums) plus a strided fp32
+      sample of each backbone map (feat{i}_sample, every SAMPLE_STRIDE-th value) and topk_min_gap, the
+      smallest gap between adjacent encoder scores among the top Q + 1 of each image.
+
+It prints, per block, the output range and the share of DFC-gate (sigmoid) and SE-gate (Hardsigmoid)
+pre-activations in the saturated and linear regions, so a reader can see that the random weights
+exercise every branch.  The seeds are accepted only when topk_min_gap >= 10 x the largest
+encoder-score difference between tests/rtdetr_ghostv2_ref.py and the reference, so that exact top-k is
+a fair demand.
+
+Usage: python tools/gen_golden_rtdetr_ghostv2.py
+"""
+from __future__ import annotations
+
+import json
+import os
+import sys
+import types
+
+import numpy as np
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+REPO = os.path.dirname(HERE)
+for p in ("satellite-pose-estimation_amd", "oracle", "tests"):
+    sys.path.insert(0, os.path.join(REPO, p))
+
+import gen_golden_rtdetr as gg  # noqa: E402
+from gen_golden_rtdetr_mbv3 import _spy_topk  # noqa: E402
+from spe.config import SpeConfig  # noqa: E402
+from spe.rtdetr_spec import RtdetrConfig, random_rtdetr_weights  # noqa: E402
+from spe.synthetic import synthetic_batch  # noqa: E402
+
+CFG = RtdetrConfig(backbone="ghostnetv2", input_size=256)
+BATCH = 2
+SEEDS = [(5, 6), (7, 8), (11, 12), (13, 14)]      # (weight, image) candidates: the acceptable pair with the widest gap wins
+SAMPLE_STRIDE = 257
+
+
+def _timm_stand_in():
+    if "timm" in sys.modules:
+        return
+    timm, models, registry = (types.ModuleType(n) for n in ("timm", "timm.models", "timm.models.registry"))
+    registry.register_model = lambda fn: fn
+    timm.models, models.registry = models, registry
+    sys.modules.update({"timm": timm, "timm.models": models, "timm.models.registry": registry})
+
+
+def build_reference(cfg):
+    _pres, he, dec, rt = gg.import_reference()
+    _timm_stand_in()
+    gn = gg._load("unc_backbone.ghostnetv2", os.path.join(gg.UNC, "nn", "backbone", "ghostnetv2.py"), "unc_backbone")
+    S = [cfg.input_size, cfg.input_size]
+    bb = gn.GhostNetV2(depth=18, pretrained=False)
+    enc = he.HybridEncoder(in_channels=cfg.backbone_channels, feat_strides=[8, 16, 32], hidden_dim=cfg.hidden_dim,
+                           use_encoder_idx=[2], num_encoder_layers=1, nhead=cfg.nheads, dim_feedforward=cfg.enc_ff,
+                           dropout=0.0, enc_act="gelu", expansion=cfg.expansion, depth_mult=1, act="silu",
+                           eval_spatial_size=S)
+    d = dec.RTDETRTransformer(num_classes=cfg.num_classes, feat_channels=[cfg.hidden_dim] * 3, feat_strides=[8, 16, 32],
+                              hidden_dim=cfg.hidden_dim, num_levels=cfg.num_levels, num_queries=cfg.num_queries,
+                              num_decoder_layers=cfg.dec_layers, dim_feedforward=cfg.dec_ff, num_denoising=0, eval_idx=-1,
+                              eval_spatial_size=S)
+    return rt.RTDETR(bb, enc, d).eval()
+
+
+def run(cfg, wseed, iseed):
+    import torch
+    import rtdetr_ghostv2_ref
+    model = build_reference(cfg)
+    w = random_rtdetr_weights(cfg, wseed)
+    missing, unexpected = model.load_state_dict({k: torch.from_numpy(v) for k, v in w.items()}, strict=False)
+    assert not unexpected and all(k.endswith("num_batches_tracked") for k in missing), (missing, unexpected)
+    batch = synthetic_batch(SpeConfig(input_size=cfg.input_size), BATCH, iseed)
+    stages = {}
+    model.backbone.register_forward_hook(lambda mod, i, o: stages.update(feats=[t.detach() for t in o]))
+    model.encoder.register_forward_hook(lambda mod, i, o: stages.update(enc=[t.detach() for t in o]))
+    with torch.no_grad():
+        out, seen = _spy_topk(lambda: model(torch.from_numpy(batch["images"])))
+    trace = {}
+    mine, seen_mine = _spy_topk(lambda: rtdetr_ghostv2_ref.forward(batch["images"], w, cfg, trace))
+    score_diff = float((seen["scores"] - seen_mine["scores"]).abs().max())
+    Q = cfg.num_queries
+    top = torch.sort(seen["scores"], dim=1, descending=True).values[:, :Q + 1]
+    gap = float((top[:, :-1] - top[:, 1:]).min())
+    return dict(model=model, w=w, batch=batch, stages=stages, out=out, seen=seen, trace=trace, mine=mine,
+                score_diff=score_diff, gap=gap)
+
+
+def _shares(x, lim):
+    return " / ".join(f"{float(v.float().mean()):.3f}" for v in (x < -lim, (x >= -lim) & (x < 0), (x >= 0) & (x <= lim), x > lim))
+
+
+def report(trace):
+    from spe.rtdetr_spec import ghostv2_block_keys
+    print("block  out range              DFC pre-act <-4 / (-4,0) / (0,4) / >4      SE pre-act <-3 / (-3,0) / (0,3) / >3")
+    for (lid, p, _cin), o in zip(ghostv2_block_keys(), trace["block_out"]):
+        dfc = trace.get("dfc_pre", {}).get(f"{p}.ghost1")
+        se = trace.get("se_pre", {}).get(p)
+        print(f"{lid:5d}  [{float(o.min()):9.3f}, {float(o.max()):9.3f}]  "
+              f"{'-' if dfc is None else _shares(dfc, 4.0):40s}  {'-' if se is None else _shares(se, 3.0)}")
+
+
+def main():
+    import torch
+    torch.set_num_threads(os.cpu_count() or 8)
+    out_dir = os.path.join(REPO, "tests", "golden")
+    m = build_reference(CFG)
+    keys = [[k, list(v.shape)] for k, v in m.state_dict().items()]
+    with open(os.path.join(out_dir, "rtdetr_keys_ghostv2.json"), "w") as f:
+        json.dump(keys, f)
+    bbk = [(k, s) for k, s in keys if k.startswith("backbone.")]
+    print("backbone state_dict entries", len(bbk), "values", sum(int(np.prod(s)) if s else 1 for _, s in bbk))
+    best = None
+    for ws, is_ in SEEDS:
+        c = run(CFG, ws, is_)
+        print(f"seeds ({ws}, {is_}): topk_min_gap {c['gap']:.3e}, restatement-vs-reference encoder score diff "
+              f"{c['score_diff']:.3e}")
+        if c["gap"] >= 10 * c["score_diff"] and (best is None or c["gap"] > best[0]["gap"]):
+            best = (c, ws, is_)
+    if best is None:
+        raise SystemExit("no candidate seed pair separates the top-k scores")
+    r, wseed, iseed = best
+    print("chosen seeds", wseed, iseed)
+    report(r["trace"])
+    out, aux, batch = r["out"], r["out"]["aux_outputs"], r["batch"]
+    rec = {
+        "config": json.dumps(CFG.to_dict()), "batch": BATCH, "weight_seed": wseed, "image_seed": iseed,
+        "input_checksum": gg._chk(batch["images"]),
+        "pred_logits": out["pred_logits"].numpy(), "pred_pts": out["pred_pts"].numpy(),
+        "pred_sigmas": out["pred_sigmas"].numpy(),
+        "aux_logits": np.stack([a["pred_logits"].numpy() for a in aux[:-1]]),
+        "aux_pts": np.stack([a["pred_pts"].numpy() for a in aux[:-1]]),
+        "aux_sigmas": np.stack([a["pred_sigmas"].numpy() for a in aux[:-1]]),
+        "enc_topk_logits": aux[-1]["pred_logits"].numpy(), "enc_topk_bboxes": aux[-1]["pred_pts"].numpy(),
+        "topk_ind": r["seen"]["ind"].numpy(), "clip_bbox": batch["clip_bbox"],
+        "topk_min_gap": np.float64(r["gap"]), "oracle_score_diff": np.float64(r["score_diff"]),
+        "sample_stride": SAMPLE_STRIDE,
+    }
+    for i, t in enumerate(r["stages"]["feats"]):
+        rec[f"chk_feat{i}"] = gg._chk(t.numpy())
+        rec[f"feat{i}_sample"] = np.ascontiguousarray(t.numpy().ravel()[::SAMPLE_STRIDE], np.float32)
+        print(f"feat{i}", tuple(t.shape), "range", float(t.min()), float(t.max()))
+    for i, t in enumerate(r["stages"]["enc"]):
+        rec[f"chk_enc{i}"] = gg._chk(t.numpy())
+    for k in ("pred_logits", "pred_pts", "pred_sigmas"):
+        print(k, "restatement vs reference max |d|", float((r["mine"][k] - out[k]).abs().max()))
+    path = os.path.join(out_dir, "rtdetr_ghostv2_s256.npz")
+    np.savez_compressed(path, **rec)
+    print("wrote", path, os.path.getsize(path), "bytes")
+
+
+if __name__ == "__main__":
+    main()
