@@ -200,6 +200,34 @@ int spe_forward_stages(spe_model* m, void* stream, const float* images, int batc
 int spe_forward_stages_u8(spe_model* m, void* stream, const uint8_t* crops, int channels, int batch, void* workspace,
                           int64_t workspace_bytes, const spe_forward_outputs* out, int stages);
 
+/* spe_rtdetr_forward in stages, with the SPE_STAGE_* bits read for the RT-DETR model:
+ *   BACKBONE     the backbone: images -> the stride 8 / 16 / 32 maps, kept in `workspace`
+ *   TRANSFORMER  the HybridEncoder (input_proj, AIFI, FPN, PAN): the maps -> the three level outputs, kept
+ *                in `workspace`
+ *   ENCODE       BACKBONE followed by TRANSFORMER
+ *   DECODE       the RTDETRTransformer, the heads and the fused RTDETRPostProcessor: `workspace` -> out
+ * spe_rtdetr_forward == every stage in order: the same launches with the same results.  `stages` names
+ * one stage or neighbours in that order (BACKBONE | DECODE without TRANSFORMER is refused); `out` may be NULL
+ * when DECODE is not asked for, `images` when BACKBONE is not.
+ * Staging contract: everything a later stage reads lies in `workspace`, and a forward writes device memory
+ * nowhere else but `out` (the packed model is read-only after finalize).  Two batches in flight therefore
+ * take two workspaces and share nothing writable; the stages of one batch are ordered by the caller
+ * (one stream, or events between streams), and a workspace is free for the next batch once its DECODE is done.
+ * Refusals, before any launch and in this order: a null handle / workspace or batch <= 0, a DETR handle
+ * ("not an RT-DETR model"), a bad stage mask, BACKBONE without images / crops, DECODE without out /
+ * out->logits / out->points, channels other than 1 or 3 (all SPE_E_ARG); a model not finalized
+ * (SPE_E_STATE); a workspace below spe_model_workspace_bytes (SPE_E_WORKSPACE).  (ABI 9 addition) */
+int spe_rtdetr_forward_stages(spe_model* m, void* stream, const float* images, int batch, void* workspace,
+                              int64_t workspace_bytes, const spe_rtdetr_outputs* out, int stages);
+/* The same stages fed with 8-bit crops, device [B][S][S][channels] u8 (channels 1: grayscale, replicated into
+ * the three channels; 3: RGB) -- the pad-to-square crops of spe_preprocess_submission, which is UNC's
+ * SpeedSubmission crop (UNC/src/data/speed/speed_dataset.py:59-168), or a loader's crops before to_tensor +
+ * Normalize.  Each pixel is normalised (u8 / 255 - mean) / std in fp32 where the backbone first reads it (the
+ * PResNet input pack, the MobileNetV3_Large / GhostNetV2 stem): bit-identical to spe_rtdetr_forward_stages on
+ * the fp32 batch normalised that way. */
+int spe_rtdetr_forward_stages_u8(spe_model* m, void* stream, const uint8_t* crops, int channels, int batch,
+                                 void* workspace, int64_t workspace_bytes, const spe_rtdetr_outputs* out, int stages);
+
 /* Validation input pipeline on the device (SpeedTrain.__getitem__ with train=False,
  * REV/datasets/speed.py:209-233): generate_clip_bbox_val (:246-258), Pillow crop,
  * A.Resize(S, S, cv2.INTER_CUBIC) (make_transforms(train=False), :295-299), F.to_tensor and

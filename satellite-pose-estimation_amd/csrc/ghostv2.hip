@@ -2,7 +2,8 @@
 // NHWC, storage T = bf16 or float, fp32 accumulation, 16-byte channel vectors, no floating-point atomics:
 //
 //   gh_stem    conv_stem 3x3/s2 3 -> 16 from the fp32 NCHW batch, two outputs: the raw conv output (what
-//              the 64 x 64 resize and Conv1 read) and relu(bn1(.)) (what the blocks read)
+//              the 64 x 64 resize and Conv1 read) and relu(bn1(.)) (what the blocks read); gh_stem_u8: the
+//              same from the 8-bit crops the batch is normalised from, tiled through LDS
 //   gh_cheap   the ghost module's second half and what follows it: x2 = act(dw3x3(x1) + bias) over an
 //              8 x 8 tile x a group of channel vectors, x1 (a channel slice of a wider tensor) staged with
 //              its halo in LDS; writes out[:half] = post(x1), out[half:] = post(x2), post = nothing, the
@@ -22,10 +23,11 @@
 
 #include "spe_common.h"
 #include "spe_kernels.h"
+#include "stem_u8.h"
 
 namespace {
 
-constexpr int GH_T = 8;                        // output tile edge
+constexpr int GH_T = 8;                       // output tile edge
 constexpr int GH_P = GH_T + 2;                 // patch edge (3x3, stride 1)
 constexpr int GH_CGMAX = 8;                    // 16-byte channel vectors per work-group
 constexpr int GH_LDS = 2 * 256 * 8 * 4;        // the pool reduction's slot-major partials (>= the patch's 12.5 KB)
@@ -60,6 +62,34 @@ __global__ __launch_bounds__(256) void gh_stem_kernel(const float* __restrict__ 
       }
     }
   constexpr int CE = Chunk<T>::CE;
+#pragma unroll
+  for (int c = 0; c < 16; c += CE) st16(raw + pix * 16 + c, pack16<T>(acc + c));
+#pragma unroll
+  for (int c = 0; c < 16; ++c) acc[c] = fmaxf(fmaf(acc[c], wl[432 + c], wl[448 + c]), 0.f);
+#pragma unroll
+  for (int c = 0; c < 16; c += CE) st16(act + pix * 16 + c, pack16<T>(acc + c));
+}
+
+// the same stem from the 8-bit crops [B][S][S][CH]: a 16 x 16 output tile a work-group, the patch staged and
+// normalised once in LDS (stem_u8.h); both outputs bit-identical to gh_stem_kernel's on the batch normalised
+// that way
+template <typename T, int CH>
+__global__ __launch_bounds__(256) void gh_stem_u8_kernel(const uint8_t* __restrict__ crops, const float* __restrict__ w,
+                                                         const float* __restrict__ scale, const float* __restrict__ shift,
+                                                         T* __restrict__ raw, T* __restrict__ act, int S) {
+  __shared__ float wl[27 * 16 + 32];
+  __shared__ StemU8Lds lds;
+  for (int i = threadIdx.x; i < 27 * 16 + 32; i += 256) wl[i] = i < 432 ? w[i] : i < 448 ? scale[i - 432] : shift[i - 448];
+  const int So = S >> 1, tiles_x = So / SU_T;
+  const int ty0 = (blockIdx.x / tiles_x) * SU_T, tx0 = (blockIdx.x % tiles_x) * SU_T, b = blockIdx.y;
+  stem_u8_stage<CH>(crops, S, b, ty0, tx0, lds);          // (its barriers cover wl)
+  const int ox = threadIdx.x & (SU_T - 1), oy = threadIdx.x / SU_T, gy = ty0 + oy, gx = tx0 + ox;
+  float acc[16];
+#pragma unroll
+  for (int c = 0; c < 16; ++c) acc[c] = 0.f;
+  stem_u8_accumulate(lds.x, wl, S, gy, gx, oy, ox, acc);
+  constexpr int CE = Chunk<T>::CE;
+  const size_t pix = ((size_t)b * So + gy) * So + gx;
 #pragma unroll
   for (int c = 0; c < 16; c += CE) st16(raw + pix * 16 + c, pack16<T>(acc + c));
 #pragma unroll
@@ -255,8 +285,22 @@ int pow2_vecs(int nvec, int cap) {
 
 }  // namespace
 
-int spe_launch_gh_stem(const float* images, const float* w, const float* scale, const float* shift, void* raw, void* act,
+int spe_launch_gh_stem(const ImageSrc& src, const float* w, const float* scale, const float* shift, void* raw, void* act,
                        int B, int S, int dtype, hipStream_t s) {
+  if (src.u8) {
+    if (!w || !scale || !shift || !raw || !act || !stem_u8_fits(src.u8, src.ch, B, S)) return -1;
+    const dim3 grid((unsigned)((S / 2 / SU_T) * (S / 2 / SU_T)), (unsigned)B);
+    const bool bf = dtype == SPE_DTYPE_BF16;
+    if (src.ch == 1) {
+      if (bf) gh_stem_u8_kernel<bf16, 1><<<grid, 256, 0, s>>>(src.u8, w, scale, shift, (bf16*)raw, (bf16*)act, S);
+      else gh_stem_u8_kernel<float, 1><<<grid, 256, 0, s>>>(src.u8, w, scale, shift, (float*)raw, (float*)act, S);
+    } else {
+      if (bf) gh_stem_u8_kernel<bf16, 3><<<grid, 256, 0, s>>>(src.u8, w, scale, shift, (bf16*)raw, (bf16*)act, S);
+      else gh_stem_u8_kernel<float, 3><<<grid, 256, 0, s>>>(src.u8, w, scale, shift, (float*)raw, (float*)act, S);
+    }
+    return launch_rc();
+  }
+  const float* images = src.f32;
   if (!images || !w || !scale || !shift || !raw || !act || B <= 0 || S < 2 || (S & 1)) return -1;
   const size_t pix = (size_t)B * (S / 2) * (S / 2);
   const unsigned grid = (unsigned)((pix + 255) / 256);

@@ -1,7 +1,8 @@
 // MobileNetV3_Large backbone kernels of the UNC RT-DETR model (UNC/nn/backbone/mobilenetv3.py:28-225),
 // gfx950, NHWC, storage T = bf16 (fp32 accumulation) or float (exact-f32 MFMA):
 //
-//   mb_stem      conv1 3x3/s2 3 -> 16 + folded BN + Hardswish, read straight from the fp32 NCHW batch
+//   mb_stem      conv1 3x3/s2 3 -> 16 + folded BN + Hardswish, read straight from the fp32 NCHW batch, or
+//                (mb_stem_u8) from the 8-bit crops it is normalised from, tiled through LDS
 //   mb_dwconv    depthwise k x k (k 3 / 5, stride 1 / 2, pad k/2) + folded BN + none / ReLU / Hardswish;
 //                an 8 x 8 output tile x a group of 16-byte channel vectors per work-group, the input
 //                patch with its halo staged once in LDS; optionally the per-(image, tile, channel) sums
@@ -18,6 +19,7 @@
 
 #include "spe_common.h"
 #include "spe_kernels.h"
+#include "stem_u8.h"
 
 namespace {
 
@@ -61,6 +63,30 @@ __global__ __launch_bounds__(256) void mb_stem_kernel(const float* __restrict__ 
   for (int c = 0; c < 16; ++c) acc[c] = mb_act(acc[c], MB_ACT_HSWISH);
   constexpr int CE = Chunk<T>::CE;
   T* o = out + pix * 16;
+#pragma unroll
+  for (int c = 0; c < 16; c += CE) st16(o + c, pack16<T>(acc + c));
+}
+
+// the same stem from the 8-bit crops [B][S][S][CH]: a 16 x 16 output tile a work-group, the patch staged and
+// normalised once in LDS (stem_u8.h); bit-identical to mb_stem_kernel on the batch normalised that way
+template <typename T, int CH>
+__global__ __launch_bounds__(256) void mb_stem_u8_kernel(const uint8_t* __restrict__ crops, const float* __restrict__ w,
+                                                         const float* __restrict__ bias, T* __restrict__ out, int S) {
+  __shared__ float wl[27 * 16 + 16];
+  __shared__ StemU8Lds lds;
+  for (int i = threadIdx.x; i < 27 * 16 + 16; i += 256) wl[i] = i < 432 ? w[i] : bias[i - 432];
+  const int So = S >> 1, tiles_x = So / SU_T;
+  const int ty0 = (blockIdx.x / tiles_x) * SU_T, tx0 = (blockIdx.x % tiles_x) * SU_T, b = blockIdx.y;
+  stem_u8_stage<CH>(crops, S, b, ty0, tx0, lds);          // (its barriers cover wl)
+  const int ox = threadIdx.x & (SU_T - 1), oy = threadIdx.x / SU_T, gy = ty0 + oy, gx = tx0 + ox;
+  float acc[16];
+#pragma unroll
+  for (int c = 0; c < 16; ++c) acc[c] = wl[432 + c];
+  stem_u8_accumulate(lds.x, wl, S, gy, gx, oy, ox, acc);
+#pragma unroll
+  for (int c = 0; c < 16; ++c) acc[c] = mb_act(acc[c], MB_ACT_HSWISH);
+  constexpr int CE = Chunk<T>::CE;
+  T* o = out + (((size_t)b * So + gy) * So + gx) * 16;
 #pragma unroll
   for (int c = 0; c < 16; c += CE) st16(o + c, pack16<T>(acc + c));
 }
@@ -309,8 +335,22 @@ int launch_rc() {
 
 }  // namespace
 
-int spe_launch_mb_stem(const float* images, const float* w, const float* bias, void* out, int B, int S, int dtype,
+int spe_launch_mb_stem(const ImageSrc& src, const float* w, const float* bias, void* out, int B, int S, int dtype,
                        hipStream_t s) {
+  if (src.u8) {
+    if (!w || !bias || !out || !stem_u8_fits(src.u8, src.ch, B, S)) return -1;
+    const dim3 grid((unsigned)((S / 2 / SU_T) * (S / 2 / SU_T)), (unsigned)B);
+    const bool bf = dtype == SPE_DTYPE_BF16;
+    if (src.ch == 1) {
+      if (bf) mb_stem_u8_kernel<bf16, 1><<<grid, 256, 0, s>>>(src.u8, w, bias, (bf16*)out, S);
+      else mb_stem_u8_kernel<float, 1><<<grid, 256, 0, s>>>(src.u8, w, bias, (float*)out, S);
+    } else {
+      if (bf) mb_stem_u8_kernel<bf16, 3><<<grid, 256, 0, s>>>(src.u8, w, bias, (bf16*)out, S);
+      else mb_stem_u8_kernel<float, 3><<<grid, 256, 0, s>>>(src.u8, w, bias, (float*)out, S);
+    }
+    return launch_rc();
+  }
+  const float* images = src.f32;
   if (!images || !w || !bias || !out || B <= 0 || S < 2 || (S & 1)) return -1;
   const size_t pix = (size_t)B * (S / 2) * (S / 2);
   const unsigned grid = (unsigned)((pix + 255) / 256);

@@ -513,8 +513,11 @@ void build_mbv3(spe_model* m) {
   mb.last = mb_conv(m, b + "conv2.weight", b + "bn2", "", 1, 0);
 }
 
+// bytes a backbone's first launch reads per input pixel: the fp32 batch's three channels or the crop's 1 / 3
+inline double image_px_bytes(const ImageSrc& img) { return img.u8 ? (double)img.ch : 12.0; }
+
 // ---- backbone stages: both leave f0 / f1 / f2 (NHWC, strides 8 / 16 / 32) where the hybrid encoder reads them
-int rt_backbone_presnet(spe_model* m, hipStream_t s, const float* images, int B, char* ws, const RtWs& w) {
+int rt_backbone_presnet(spe_model* m, hipStream_t s, const ImageSrc& images, int B, char* ws, const RtWs& w) {
   const RtModel& r = *m->rt;
   const auto& c = r.cfg;
   const int dt = c.dtype, S = c.input_size, E = m->esz;
@@ -537,7 +540,7 @@ int rt_backbone_presnet(spe_model* m, hipStream_t s, const float* images, int B,
   };
 
   // ---------------- PResNet-vd (presnet.py:248-265)
-  CK(run_other(m, "eltwise.pack", 0.0, (double)B * S * S * (12 + 8 * E), s,
+  CK(run_other(m, "eltwise.pack", 0.0, (double)B * S * S * (image_px_bytes(images) + 8 * E), s,
                [&] { return spe_launch_pack_input(images, P(w.x0), B, S, dt, s); }));
   int H = S;
   size_t cur = w.x0;
@@ -583,7 +586,7 @@ int rt_backbone_presnet(spe_model* m, hipStream_t s, const float* images, int B,
 // MobileNetV3_Large.forward (mobilenetv3.py:206-225) at input 256: stem -> x0 [B][128][128][16]; Conv1 (2x2
 // mean folded in) -> f0, Conv2 -> f1; the 15 blocks ping-pong bufA / bufB with the expanded tensor in t1,
 // the depthwise output in t2 and the skip branch in sc; conv2 -> f2
-int rt_backbone_mbv3(spe_model* m, hipStream_t s, const float* images, int B, char* ws, const RtWs& w) {
+int rt_backbone_mbv3(spe_model* m, hipStream_t s, const ImageSrc& images, int B, char* ws, const RtWs& w) {
   const RtModel& r = *m->rt;
   const RtMbv3& mb = r.mb;
   const int dt = r.cfg.dtype, S = r.cfg.input_size;
@@ -616,7 +619,8 @@ int rt_backbone_mbv3(spe_model* m, hipStream_t s, const float* images, int B, ch
                      (double)B * d.C * (Hin * Hin + Ho * Ho) * E, s, [&] { return spe_launch_mb_dwconv(a, dt, s); });
   };
   const int H0 = S / 2;
-  CK(run_other(m, "conv.stem.mb", 2.0 * B * H0 * H0 * 16 * 27, (double)B * (S * S * 12.0 + H0 * H0 * 16 * E), s,
+  CK(run_other(m, "conv.stem.mb", 2.0 * B * H0 * H0 * 16 * 27,
+               (double)B * (S * S * image_px_bytes(images) + H0 * H0 * 16 * E), s,
                [&] { return spe_launch_mb_stem(images, mb.stem_w, mb.stem_b, P(w.x0), B, S, dt, s); }));
   CK(pw(mb.conv_b, P(w.x0), H0, P(w.f0), MB_ACT_HSWISH, nullptr, nullptr));
   CK(pw(mb.conv_c, P(w.f0), r.lvl_s[0], P(w.f1), MB_ACT_HSWISH, nullptr, nullptr));
@@ -798,7 +802,7 @@ void build_ghost(spe_model* m) {
 // bufB with a module's primary output in t1, ghost1's output in t2 and, in eighths of sc, the stride-2
 // depthwise output (2), the pooled input, the DFC branch's 1x1 output, its gate, the shortcut's depthwise
 // and 1x1 outputs; blocks.9.0 -> t2, Conv3 -> f2
-int rt_backbone_ghostv2(spe_model* m, hipStream_t s, const float* images, int B, char* ws, const RtWs& w) {
+int rt_backbone_ghostv2(spe_model* m, hipStream_t s, const ImageSrc& images, int B, char* ws, const RtWs& w) {
   const RtModel& r = *m->rt;
   const RtGhost& gh = r.gh;
   const int dt = r.cfg.dtype, S = r.cfg.input_size;
@@ -842,7 +846,8 @@ int rt_backbone_ghostv2(spe_model* m, hipStream_t s, const float* images, int B,
                      [&] { return spe_launch_gh_cheap(a, dt, s); });
   };
   const int H0 = S / 2;
-  CK(run_other(m, "conv.stem.gh", 2.0 * B * H0 * H0 * 16 * 27, (double)B * (S * S * 12.0 + 2.0 * H0 * H0 * 16 * E), s, [&] {
+  CK(run_other(m, "conv.stem.gh", 2.0 * B * H0 * H0 * 16 * 27,
+               (double)B * (S * S * image_px_bytes(images) + 2.0 * H0 * H0 * 16 * E), s, [&] {
     return spe_launch_gh_stem(images, gh.stem_w, gh.stem_scale, gh.stem_shift, P(w.x0), P(w.bufA), B, S, dt, s);
   }));
   CK(pw(gh.conv_b, P(w.x0), H0, P(w.f0), MB_ACT_HSWISH, nullptr));
@@ -1043,8 +1048,9 @@ int spe_rtdetr_backbone(spe_model* m, hipStream_t s, const float* images, int B,
   if ((int64_t)w.total > ws_bytes) return fail(SPE_E_WORKSPACE, "workspace too small");
   const RtModel& r = *m->rt;
   char* ws = (char*)workspace;
-  CK(r.ghost ? rt_backbone_ghostv2(m, s, images, B, ws, w)
-     : r.mbv3 ? rt_backbone_mbv3(m, s, images, B, ws, w) : rt_backbone_presnet(m, s, images, B, ws, w));
+  const ImageSrc src{images, nullptr, 0};
+  CK(r.ghost ? rt_backbone_ghostv2(m, s, src, B, ws, w)
+     : r.mbv3 ? rt_backbone_mbv3(m, s, src, B, ws, w) : rt_backbone_presnet(m, s, src, B, ws, w));
   const size_t off[3] = {w.f0, w.f1, w.f2};
   for (int l = 0; l < 3; ++l) {
     if (f) f[l] = ws + off[l];
@@ -1098,25 +1104,31 @@ int spe_rtdetr_create(const spe_rtdetr_config* cfg, spe_model** out) {
   return 0;
 }
 
-int spe_rtdetr_forward(spe_model* m, void* stream, const float* images, int B, void* workspace, int64_t ws_bytes,
-                       const spe_rtdetr_outputs* out) {
-  if (!m || !workspace || !images || B <= 0 || !out || !out->logits || !out->points) return fail(SPE_E_ARG, "bad argument");
-  if (m->family != 1) return fail(SPE_E_ARG, "not an RT-DETR model");
-  if (!m->finalized) return fail(SPE_E_STATE, "model not finalized");
-  const RtWs w = rt_plan(m, B);
-  if ((int64_t)w.total > ws_bytes) return fail(SPE_E_WORKSPACE, "workspace too small");
-  hipStream_t s = (hipStream_t)stream;
+}  // extern "C"
+
+namespace {
+
+// One forward call's context: the stages below are the launch sequence of RTDETR.forward cut at the
+// two points where everything the rest reads lies in the workspace (include/spe.h, staging contract).
+struct RtFwd {
+  spe_model* m;
+  const RtWs& w;
+  char* ws;
+  hipStream_t s;
+  int B;
+  void* P(size_t o) const { return (void*)(ws + o); }
+};
+
+// TRANSFORMER: HybridEncoder (hybrid_encoder.py:332-401) over f0 / f1 / f2 -> p3 / n4 / n5
+int rt_encoder_stage(const RtFwd& f) {
+  spe_model* m = f.m;
+  const RtWs& w = f.w;
+  hipStream_t s = f.s;
+  const int B = f.B;
   const RtModel& r = *m->rt;
   const auto& c = r.cfg;
-  const int dt = c.dtype, S = c.input_size, d = 256, Q = c.num_queries, C = c.num_classes + 1, E = m->esz;
-  const int BQ = B * Q, h = c.csp_hidden;
-  char* ws = (char*)workspace;
-  auto P = [&](size_t o) { return (void*)(ws + o); };
-
-  CK(r.ghost ? rt_backbone_ghostv2(m, s, images, B, ws, w)
-     : r.mbv3 ? rt_backbone_mbv3(m, s, images, B, ws, w) : rt_backbone_presnet(m, s, images, B, ws, w));
-
-  // ---------------- HybridEncoder (hybrid_encoder.py:332-401)
+  const int dt = c.dtype, d = 256, E = m->esz, h = c.csp_hidden;
+  auto P = [&](size_t o) { return f.P(o); };
   const int s0 = r.lvl_s[0], s1 = r.lvl_s[1], s2 = r.lvl_s[2];
   const int* fch = r.fch;
   {  // input_proj (1x1 + BN): levels 0 / 1 straight into the second half of their FPN concat
@@ -1199,8 +1211,21 @@ int spe_rtdetr_forward(spe_model* m, void* stream, const float* images, int B, v
                  [&] { return spe_launch_resample2x(P(w.n4), d, P(w.catp1), 2 * d, B, s1, s1, d, 1, dt, s); }));
     CK(csp(r.pan[1], w.catp1, s2, w.n5));
   }
+  return 0;
+}
 
-  // ---------------- RTDETRTransformer (rtdetr_decoder.py:505-710)
+// DECODE: RTDETRTransformer (rtdetr_decoder.py:505-710), the heads and the fused RTDETRPostProcessor over
+// p3 / n4 / n5 (everything else it reads it writes first)
+int rt_decoder_stage(const RtFwd& f, const spe_rtdetr_outputs* out) {
+  spe_model* m = f.m;
+  const RtWs& w = f.w;
+  hipStream_t s = f.s;
+  const int B = f.B;
+  const RtModel& r = *m->rt;
+  const auto& c = r.cfg;
+  const int dt = c.dtype, d = 256, Q = c.num_queries, C = c.num_classes + 1, E = m->esz;
+  const int BQ = B * Q;
+  auto P = [&](size_t o) { return f.P(o); };
   const size_t lvl_out[3] = {w.p3, w.n4, w.n5};
   for (int l = 0; l < 3; ++l) {   // level-major memory: rows [B * lvl_start[l] + b * hw_l + t]
     GemmArgs g = linear_args(r.dec_in[l], P(lvl_out[l]), d, B * r.lvl_s[l] * r.lvl_s[l],
@@ -1348,6 +1373,59 @@ int spe_rtdetr_forward(spe_model* m, void* stream, const float* images, int B, v
       CK((int)hipMemcpyAsync(out->aux_points + aoff * 2, ref_buf(i + 1), (size_t)BQ * 2 * 4, hipMemcpyDeviceToDevice, s));
   }
   return 0;
+}
+
+// the stage bits in pipeline order: ENCODE stands for BACKBONE | TRANSFORMER; a mask must name neighbours
+int rt_stage_mask(int stages) {
+  const int all = SPE_STAGE_ENCODE | SPE_STAGE_DECODE | SPE_STAGE_BACKBONE | SPE_STAGE_TRANSFORMER;
+  if (!stages || (stages & ~all)) return 0;
+  if (stages & SPE_STAGE_ENCODE) stages = (stages & ~SPE_STAGE_ENCODE) | SPE_STAGE_BACKBONE | SPE_STAGE_TRANSFORMER;
+  if ((stages & SPE_STAGE_BACKBONE) && (stages & SPE_STAGE_DECODE) && !(stages & SPE_STAGE_TRANSFORMER)) return 0;
+  return stages;
+}
+
+int rt_forward_stages(spe_model* m, void* stream, const ImageSrc& images, bool u8, int B, void* workspace, int64_t ws_bytes,
+                      const spe_rtdetr_outputs* out, int stages) {
+  if (!m || !workspace || B <= 0) return fail(SPE_E_ARG, "bad argument");
+  if (m->family != 1) return fail(SPE_E_ARG, "not an RT-DETR model");
+  stages = rt_stage_mask(stages);
+  if (!stages) return fail(SPE_E_ARG, "stages: a contiguous, non-empty set of SPE_STAGE_* bits");
+  if ((stages & SPE_STAGE_BACKBONE) && !images.f32 && !images.u8) return fail(SPE_E_ARG, "null images");
+  if ((stages & SPE_STAGE_DECODE) && (!out || !out->logits || !out->points)) return fail(SPE_E_ARG, "null outputs");
+  if (u8 && images.ch != 1 && images.ch != 3) return fail(SPE_E_ARG, "u8 crops: 1 or 3 channels");
+  if (!m->finalized) return fail(SPE_E_STATE, "model not finalized");
+  const RtWs w = rt_plan(m, B);
+  if ((int64_t)w.total > ws_bytes) return fail(SPE_E_WORKSPACE, "workspace too small");
+  const RtModel& r = *m->rt;
+  const RtFwd f{m, w, (char*)workspace, (hipStream_t)stream, B};
+  if (stages & SPE_STAGE_BACKBONE)
+    CK(r.ghost ? rt_backbone_ghostv2(m, f.s, images, B, f.ws, w)
+       : r.mbv3 ? rt_backbone_mbv3(m, f.s, images, B, f.ws, w) : rt_backbone_presnet(m, f.s, images, B, f.ws, w));
+  // (a stage's failing launch has recorded its own error)
+  if (stages & SPE_STAGE_TRANSFORMER)
+    if (const int rc = rt_encoder_stage(f)) return rc;
+  if (stages & SPE_STAGE_DECODE)
+    if (const int rc = rt_decoder_stage(f, out)) return rc;
+  return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int spe_rtdetr_forward(spe_model* m, void* stream, const float* images, int B, void* workspace, int64_t ws_bytes,
+                       const spe_rtdetr_outputs* out) {
+  return spe_rtdetr_forward_stages(m, stream, images, B, workspace, ws_bytes, out, SPE_STAGE_ENCODE | SPE_STAGE_DECODE);
+}
+
+int spe_rtdetr_forward_stages(spe_model* m, void* stream, const float* images, int B, void* workspace, int64_t ws_bytes,
+                              const spe_rtdetr_outputs* out, int stages) {
+  return rt_forward_stages(m, stream, ImageSrc{images, nullptr, 0}, false, B, workspace, ws_bytes, out, stages);
+}
+
+int spe_rtdetr_forward_stages_u8(spe_model* m, void* stream, const uint8_t* crops, int channels, int B, void* workspace,
+                                 int64_t ws_bytes, const spe_rtdetr_outputs* out, int stages) {
+  return rt_forward_stages(m, stream, ImageSrc{nullptr, crops, channels}, true, B, workspace, ws_bytes, out, stages);
 }
 
 }  // extern "C"

@@ -393,8 +393,10 @@ int spe_launch_head_finish(const RtHeadArgs& a, int dtype, hipStream_t s);
 // when the shapes are outside its contract, 0 or a hipError_t otherwise.
 enum { MB_ACT_NONE = 0, MB_ACT_RELU = 1, MB_ACT_HSWISH = 4 };   // Hardswish: x relu6(x + 3) / 6
 // conv1 3x3/s2/p1 3 -> 16 + bias + Hardswish from the fp32 NCHW batch [B][3][S][S] (S even) into NHWC T
-// [B][S/2][S/2][16]; w fp32 [27][16] with k = (ci*3 + kh)*3 + kw
-int spe_launch_mb_stem(const float* images, const float* w, const float* bias, void* out, int B, int S, int dtype,
+// [B][S/2][S/2][16]; w fp32 [27][16] with k = (ci*3 + kh)*3 + kw.  A u8 source ([B][S][S][ch] crops, ch 1 / 3,
+// 4-byte aligned, S % 32 == 0, B <= 65535) takes the tiled 8-bit kernel (stem_u8.h), bit-identical to the fp32
+// kernel on the batch normalised from the crops.
+int spe_launch_mb_stem(const ImageSrc& src, const float* w, const float* bias, void* out, int B, int S, int dtype,
                        hipStream_t s);
 // depthwise k x k, pad k/2, over NHWC T.  Contract: k 3 or 5; stride 1, or 2 with even H and W (Ho = H /
 // stride); C % 8 == 0; B <= 65535.  w fp32 [k*k][C] (BatchNorm scale folded in), bias fp32 [C].
@@ -446,8 +448,9 @@ int spe_launch_mb_to_nchw(const void* in, float* out, int B, int HW, int C, int 
 // shapes are outside its contract, 0 or a hipError_t otherwise.
 enum { GH_POST_NONE = 0, GH_POST_GATE = 1, GH_POST_RESIDUAL = 2 };
 // conv_stem 3x3/s2/p1 3 -> 16 from the fp32 NCHW batch [B][3][S][S] (S even) into two NHWC T tensors
-// [B][S/2][S/2][16]: raw = the conv output, act = relu(raw * scale + shift) (bn1 folded); w fp32 [27][16]
-int spe_launch_gh_stem(const float* images, const float* w, const float* scale, const float* shift, void* raw, void* act,
+// [B][S/2][S/2][16]: raw = the conv output, act = relu(raw * scale + shift) (bn1 folded); w fp32 [27][16].
+// A u8 source: as spe_launch_mb_stem's.
+int spe_launch_gh_stem(const ImageSrc& src, const float* w, const float* scale, const float* shift, void* raw, void* act,
                        int B, int S, int dtype, hipStream_t s);
 // Ghost module tail.  x1: NHWC T, pixel stride ldx, channels [xoff, xoff + half); x2 = act(dw3x3(x1) + bias),
 // w fp32 [9][half] (BatchNorm folded), act none / ReLU.  out T [B][H][W][2 half]: out[:half] = post(x1),

@@ -183,11 +183,21 @@ def generate_submission(models, postprocessors, anns, read_file, solver, device,
     reference; a failed solve (the reference's IndexError / cv2.error) or a status-1 crop gives the
     zero pose.  `postprocessors` is accepted for the reference's signature: PostProcess runs fused
     in the model's forward.  decoder / transform default to JpegDecoder() (SPEED's 1920x1200 frames)
-    and SpeedSubmissionTransform(input_size); every frame of a run has the decoder's size."""
+    and SpeedSubmissionTransform(input_size); every frame of a run has the decoder's size.
+
+    A single spe.rtdetr.RTDETR works the same way (UNC's SpeedSubmission, src/data/speed/speed_dataset.py:
+    59-168, is this pad-to-square crop): its u8 stems take the crops, its sigmas go to the solver -- a sigma
+    solver such as SimplePoseSolverSigma (epnp_ransac_sigma).  Not supported here: a list of RTDETR models
+    (the reference has no sigma fusion rule), and EPnPCeresSolver, whose per-image thresholds the reference
+    derives from the ground-truth box areas a submission set does not have (ValueError)."""
     from .datasets import JpegDecoder, SpeedSubmissionTransform
     multi = isinstance(models, (list, tuple))
     if multi and not hasattr(solver, "solve_batch_multi"):
         raise ValueError("a list of models needs an ensemble solver (Multi_Mean_PoseSolver)")
+    if getattr(solver, "mode", None) == _lib.SPE_PNP_EPNP_CERES:
+        raise ValueError("generate_submission: EPnPCeresSolver takes one threshold per image from the ground-truth "
+                         "box areas (UNC speed_dataset.py:366-399), which a submission set lacks; use a solver "
+                         "without them (epnp_ransac_sigma)")
     decoder = decoder if decoder is not None else JpegDecoder()
     transform = transform if transform is not None else SpeedSubmissionTransform(input_size)
     names = list(anns)

@@ -35,8 +35,22 @@ def pipeline_stream(device, role: str):
     return st
 
 
+def _tensors(fo):
+    """Every tensor of a forward's output dict (an RTDETR's carries its aux_outputs as a list of dicts)."""
+    for v in fo.values() if isinstance(fo, dict) else fo:
+        if torch.is_tensor(v):
+            yield v
+        elif isinstance(v, (dict, list, tuple)):
+            yield from _tensors(v)
+
+
 class PosePipeline:
-    def __init__(self, model: DETR, solver: PoseSolver, batch: int, device="cuda", use_graph: bool = False,
+    """model: a DETR or an spe.rtdetr.RTDETR -- the pipeline uses cfg.input_size, cfg.num_queries, workspace,
+    new_workspace, encode, decode and __call__, which the two share; an RTDETR's sigmas reach the solver
+    (the sigma solvers, self_assess) in every mode, and its 8-bit crops (host_input) go straight to its u8
+    stems."""
+
+    def __init__(self, model: "DETR | RTDETR", solver: PoseSolver, batch: int, device="cuda", use_graph: bool = False,
                  self_assess: bool = True, overlap: bool = False, raw_frames=None, overlap_decode: bool = False,
                  jpeg_max_bytes: int = 0, overlap_backbone: bool = False, host_input: bool = False):
         self.model, self.solver, self.B = model, solver, batch
@@ -240,7 +254,7 @@ class PosePipeline:
         s1 = self.solve_stream
         s1.wait_stream(d)
         with torch.cuda.stream(s1):
-            for t in fo.values():
+            for t in _tensors(fo):
                 t.record_stream(s1)
             out = self._solve(fo, stream=s1, q_gt=self.slot_q[slot], t_gt=self.slot_t[slot],
                               repro=self.slot_repro[slot])
@@ -276,7 +290,7 @@ class PosePipeline:
         q_gt, t_gt, repro = self.q_gt.clone(), self.t_gt.clone(), self.repro.clone()
         s1.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(s1):
-            for t in list(fo.values()) + [q_gt, t_gt, repro]:
+            for t in list(_tensors(fo)) + [q_gt, t_gt, repro]:
                 t.record_stream(s1)          # consumed on the solver stream
             out = self._solve(fo, stream=s1, q_gt=q_gt, t_gt=t_gt, repro=repro)
         out["stream"] = s1
@@ -346,7 +360,7 @@ class PosePipeline:
                 torch.cuda.synchronize()
                 self.graph.replay()
             torch.cuda.synchronize()
-            pairs = [(ref["forward"][k], self.out["forward"][k]) for k in ref["forward"]]
+            pairs = list(zip(_tensors(ref["forward"]), _tensors(self.out["forward"])))
             pairs += [(ref["poses"][k], self.out["poses"][k]) for k in ("status", "quat", "tvec")]
             if not all(torch.equal(a, b) for a, b in pairs):
                 self.graph = None

@@ -86,30 +86,66 @@ class RTDETR(nn.Module):
                 self._ws[key] = ws = (torch.empty(int(nbytes), dtype=torch.uint8, device=device), B)
         return ws[0]
 
-    def forward(self, samples, clip_bbox=None, stream=None, aux=None, return_hs=False):
-        """rtdetr.py:36-53 in eval.  Returns pred_logits [B,Q,C+1], pred_pts [B,Q,2], pred_sigmas
-        [B,Q,2] (raw) and, with aux, the reference's aux_outputs list.  Passing `clip_bbox`
-        ([B,4] device) also runs the fused RTDETRPostProcessor: probs, points_px, sigmas.
-        return_hs adds "hs" [B,Q,256], the last decoder layer's output (the heads' input)."""
+    def new_workspace(self, B, device):
+        """A separate workspace for another in-flight batch (staged overlap), like DETR.new_workspace."""
+        return torch.empty(int(_lib.lib().spe_model_workspace_bytes(self._h, B)), dtype=torch.uint8, device=device)
+
+    def _crop_channels(self, crops):
+        """8-bit crops [B,S,S] (grayscale) or [B,S,S,3] (RGB), contiguous on the device -> channels."""
+        S = self.cfg.input_size
+        if not crops.is_cuda or not crops.is_contiguous():
+            raise ValueError("u8 crops: a contiguous device tensor")
+        if crops.dim() == 3 and tuple(crops.shape[1:]) == (S, S):
+            return 1
+        if crops.dim() == 4 and tuple(crops.shape[1:]) == (S, S, 3):
+            return 3
+        raise ValueError(f"u8 crops: expected [B,{S},{S}] or [B,{S},{S},3], got {tuple(crops.shape)}")
+
+    def _run(self, images, B, ws, stream, o, stages):
+        """The stages of one forward over `ws`: fp32 images, 8-bit crops, or None without a backbone stage."""
+        L = _lib.lib()
+        out = ctypes.byref(o) if o is not None else None
+        if images is not None and images.dtype == torch.uint8:
+            ch = self._crop_channels(images)
+            _lib.check(L.spe_rtdetr_forward_stages_u8(self._h, _lib.stream_ptr(stream), _lib.ptr(images), ch, B,
+                                                      _lib.ptr(ws), ws.numel(), out, stages),
+                       "spe_rtdetr_forward_stages_u8")
+            return
+        _lib.check(L.spe_rtdetr_forward_stages(self._h, _lib.stream_ptr(stream), _lib.ptr(images), B, _lib.ptr(ws),
+                                               ws.numel(), out, stages), "spe_rtdetr_forward_stages")
+
+    def encode(self, images, ws, stream=None, part=None, B=None):
+        """Encode stage (backbone + HybridEncoder): images -> the three level outputs kept in `ws`.
+        part="backbone": the backbone alone (images -> the stride 8 / 16 / 32 maps in `ws`);
+        part="transformer": the HybridEncoder over the maps a backbone part left in `ws` (images may be
+        None, B given).  images: the fp32 batch [B,3,S,S] or 8-bit crops (forward's forms), on the device."""
         if not self._ready:
-            raise RuntimeError("RTDETR: load_state_dict() with every parameter before forward()")
-        aux = self.aux_outputs if aux is None else aux
-        if isinstance(samples, (list, tuple)):
-            samples = nested_tensor_from_tensor_list(list(samples))
-        images = samples.tensors if isinstance(samples, NestedTensor) else samples
-        if not images.is_cuda:
-            raise RuntimeError("RTDETR (HIP) expects device tensors")
-        images = images.contiguous().float()
-        B, C3, H, W = images.shape
-        S, Q, C = self.cfg.input_size, self.cfg.num_queries, self.cfg.num_classes + 1
-        if C3 != 3 or H != S or W != S:
-            raise ValueError(f"expected [B,3,{S},{S}] input, got {tuple(images.shape)}")
-        dev = images.device
+            raise RuntimeError("RTDETR: load_state_dict() with every parameter before encode()")
+        stage = {None: _lib.SPE_STAGE_ENCODE, "backbone": _lib.SPE_STAGE_BACKBONE,
+                 "transformer": _lib.SPE_STAGE_TRANSFORMER}[part]
+        B = images.shape[0] if images is not None else int(B)
+        self._run(images, B, ws, stream, None, stage)
+
+    def decode(self, B, ws, clip_bbox=None, stream=None, aux=None, return_hs=False):
+        """Decode stage (RTDETRTransformer, heads, fused RTDETRPostProcessor) of the level outputs an
+        encode() left in `ws`; returns forward's dict."""
+        if not self._ready:
+            raise RuntimeError("RTDETR: load_state_dict() with every parameter before decode()")
+        dev = ws.device
+        if clip_bbox is not None:
+            clip_bbox = clip_bbox.to(device=dev, dtype=torch.float32).contiguous()
+        out, o = self._outputs(B, dev, clip_bbox, self.aux_outputs if aux is None else aux, return_hs)
+        self._run(None, B, ws, stream, o, _lib.SPE_STAGE_DECODE)
+        return out
+
+    def _outputs(self, B, dev, clip_bbox, aux, return_hs):
+        """The output dict of one forward (tensors the call fills) and the C struct over it; clip_bbox:
+        fp32, contiguous, on `dev` (the caller keeps it alive over the call)."""
+        Q, C = self.cfg.num_queries, self.cfg.num_classes + 1
         f = dict(device=dev)
         out = {"pred_logits": torch.empty(B, Q, C, **f), "pred_pts": torch.empty(B, Q, 2, **f),
                "pred_sigmas": torch.empty(B, Q, 2, **f)}
         if clip_bbox is not None:
-            clip_bbox = clip_bbox.to(device=dev, dtype=torch.float32).contiguous()
             out.update(probs=torch.empty(B, Q, C, **f), points_px=torch.empty(B, Q, 2, **f),
                        sigmas=torch.empty(B, Q, 2, **f))
         nl = self.cfg.dec_layers - 1
@@ -125,13 +161,43 @@ class RTDETR(nn.Module):
                                _lib.ptr(clip_bbox), _lib.ptr(out.get("probs")), _lib.ptr(out.get("points_px")),
                                _lib.ptr(out.get("sigmas")), _lib.ptr(al), _lib.ptr(ap), _lib.ptr(asg), _lib.ptr(el),
                                _lib.ptr(ep), _lib.ptr(topk), _lib.ptr(out.get("hs")))
-        ws = self.workspace(B, dev, stream)
-        _lib.check(_lib.lib().spe_rtdetr_forward(self._h, _lib.stream_ptr(stream), _lib.ptr(images), B, _lib.ptr(ws),
-                                                 ws.numel(), ctypes.byref(o)), "spe_rtdetr_forward")
         if aux:   # rtdetr_decoder.py:680-700: decoder layers first, the encoder top-k last
             out["aux_outputs"] = [{"pred_logits": al[i], "pred_pts": ap[i], "pred_sigmas": asg[i]} for i in range(nl)]
             out["aux_outputs"].append({"pred_logits": el, "pred_pts": ep})
             out["topk"] = topk
+        return out, o
+
+    def forward(self, samples, clip_bbox=None, stream=None, aux=None, return_hs=False):
+        """rtdetr.py:36-53 in eval.  Returns pred_logits [B,Q,C+1], pred_pts [B,Q,2], pred_sigmas
+        [B,Q,2] (raw) and, with aux, the reference's aux_outputs list.  Passing `clip_bbox`
+        ([B,4] device) also runs the fused RTDETRPostProcessor: probs, points_px, sigmas.
+        return_hs adds "hs" [B,Q,256], the last decoder layer's output (the heads' input).
+        A contiguous device uint8 tensor [B,S,S] (grayscale) or [B,S,S,3] (RGB) is taken as the 8-bit
+        crops to_tensor + Normalize would make the batch from (spe_rtdetr_forward_stages_u8):
+        bit-identical to the fp32 batch normalised that way."""
+        if torch.is_tensor(samples) and samples.dtype == torch.uint8:
+            self._crop_channels(samples)              # (a malformed crop batch is refused whatever the model's state)
+        if not self._ready:
+            raise RuntimeError("RTDETR: load_state_dict() with every parameter before forward()")
+        aux = self.aux_outputs if aux is None else aux
+        if isinstance(samples, (list, tuple)):
+            samples = nested_tensor_from_tensor_list(list(samples))
+        images = samples.tensors if isinstance(samples, NestedTensor) else samples
+        if images.dtype != torch.uint8:
+            if not images.is_cuda:
+                raise RuntimeError("RTDETR (HIP) expects device tensors")
+            images = images.contiguous().float()
+            B, C3, H, W = images.shape
+            S = self.cfg.input_size
+            if C3 != 3 or H != S or W != S:
+                raise ValueError(f"expected [B,3,{S},{S}] input, got {tuple(images.shape)}")
+        else:
+            self._crop_channels(images)
+        B, dev = images.shape[0], images.device
+        if clip_bbox is not None:
+            clip_bbox = clip_bbox.to(device=dev, dtype=torch.float32).contiguous()
+        out, o = self._outputs(B, dev, clip_bbox, aux, return_hs)
+        self._run(images, B, self.workspace(B, dev, stream), stream, o, _lib.SPE_STAGE_ENCODE | _lib.SPE_STAGE_DECODE)
         return out
 
     def backbone_features(self, images, stream=None):
