@@ -60,9 +60,33 @@ enum { SPE_DTYPE_BF16_ = 0, SPE_DTYPE_F32_ = 1, SPE_DTYPE_F16_ = 2, SPE_DTYPE_F3
  *                            builds an empty Ceres problem, tests/golden/solver_front_ref.npz), PARITY
  *                            UNPINNED in one point: whether OpenCV 4.4's undistortPoints accepts the
  *                            empty point set (a cv2.error there would make SpeedEval log a zero pose)
+ *  SPE_PNP_EXHAUSTIVE        UNC PoseSolver.exhausive_pnp behind SimplePoseSolver.__call__
+ *                            (UNC/utils/speed_eval_ceres.py:326-399, :465-522), through spe_pnp_exhaustive only
+ *                            (spe_pnp_batch refuses it).  EPnP on every four-point subset of the selected
+ *                            correspondences in itertools.combinations order; a hypothesis's error is the
+ *                            float32 sum of its 4 squared reprojection errors (cv2's reprojectionError is the
+ *                            RMSE of the same, only the order is used), +inf when pose or error is not finite.
+ *                            The topk smallest are kept; the sort is STABLE, ties go to the lower subset index
+ *                            (np.argsort's default quicksort is not: equal errors are unpinned there), +inf
+ *                            records are never kept.  Walking them in order with th = the image's threshold:
+ *                            float32 errors of all points (epnp_init's arithmetic), inliers err < th; fewer
+ *                            than 4 -> th += 5 (carried to later candidates) and the next one; else the
+ *                            sigma-weighted Huber(0.001) LM on the inliers, weights normalised over them, the
+ *                            unrefined pose kept when the refined error sum over all points is larger; the
+ *                            candidate with the smallest sum (< 100000, the first of equals) wins.  The walk
+ *                            repeats until a pass had a candidate with 4 inliers; th after s failures is
+ *                            th0 + 5 s in fp64, and passes that cannot succeed are skipped arithmetically.
+ *                            Status UNPINNED (zero pose) where the reference never returns: no finite
+ *                            hypothesis, no kept candidate with 4 finite errors, or every qualifying
+ *                            candidate's sum >= 100000 or NaN.  PARITY UNPINNED: cv2 is absent here (EPnP, the
+ *                            projection and Rodrigues are the oracle's restatements), and the reference's call
+ *                            ceres_pnp(inlier_wld, inlier_obj, r_, t_) (:382) lacks the sigma argument of its
+ *                            own definition (:172), so it raises TypeError as written; the sigma rule above
+ *                            (the selected sigmas, or unit weights without a sigma input) is this project's
+ *                            reading, EPnPCeresSolver's.
  * SPE_PNP_EPNP's inlier_mask is epnp_init's set, reprojection error < repro (:163-166). */
 enum { SPE_PNP_EPNP = 0, SPE_PNP_RANSAC_P3P_LM = 1, SPE_PNP_EPNP_RANSAC_SIGMA = 2, SPE_PNP_EPNP_LM = 3,
-       SPE_PNP_EPNP_CERES = 4 };
+       SPE_PNP_EPNP_CERES = 4, SPE_PNP_EXHAUSTIVE = 5 };
 
 /* Per-image solver status (reference exception mapping, REV/datasets/speed.py:355-363).
  *  OK              pose solved
@@ -326,6 +350,25 @@ int spe_pnp_batch(void* stream, const float* points_px, const float* probs, cons
                   int num_queries, int num_classes, const double* K, const double* world, int mode, float repro,
                   int ransac_iters, double confidence, float* quat, double* tvec, double* rvec, int32_t* status,
                   int32_t* n_corr, int32_t* corr_label, uint32_t* inlier_mask, const float* repro_per_image);
+
+/* SPE_PNP_EXHAUSTIVE (see the solver modes): spe_pnp_batch's arguments without the RANSAC ones, plus
+ * topk in [1,64]; cand_index [B]: the winning hypothesis's subset index (its rank in
+ * itertools.combinations(range(n_corr), 4)), -1 without a pose; repro_final [B]: the image's threshold
+ * after growth.  inlier_mask is the winner's inlier set at the threshold it was tested with.  Both new
+ * outputs are nullable.  num_classes - 1 <= 16.  Hypothesis records live in per-(device, stream)
+ * scratch like the sigma mode's: no allocation or synchronisation once it has its size. */
+int spe_pnp_exhaustive(void* stream, const float* points_px, const float* probs, const float* sigmas, int batch,
+                       int num_queries, int num_classes, const double* K, const double* world, float repro, int topk,
+                       float* quat, double* tvec, double* rvec, int32_t* status, int32_t* n_corr,
+                       int32_t* corr_label, uint32_t* inlier_mask, const float* repro_per_image,
+                       int32_t* cand_index, float* repro_final);
+/* The same with a stage mask (measurement only): 1 = the hypothesis kernel, 2 = selection + refinement on
+ * the records a stage-1 call left in this stream's scratch, 3 = both. */
+int spe_debug_pnp_exhaustive_stages(void* stream, const float* points_px, const float* probs, const float* sigmas,
+                                    int batch, int num_queries, int num_classes, const double* K, const double* world,
+                                    float repro, int topk, float* quat, double* tvec, double* rvec, int32_t* status,
+                                    int32_t* n_corr, int32_t* corr_label, uint32_t* inlier_mask,
+                                    const float* repro_per_image, int32_t* cand_index, float* repro_final, int stages);
 
 /* Self-assessment filter over the sigma solver's output (BASELINE config 4).  No reference code
  * exists: the UNC README (ROOT/README.md:15-20) names the mechanism and the commented gate

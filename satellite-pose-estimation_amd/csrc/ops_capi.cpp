@@ -1,7 +1,7 @@
 // C entry points of the native runtime outside the model's forward pass (include/spe.h): the set
 // criterion, ensemble fusion, pre- and post-processing, the batched solver, its self-assessment and the
-// SPEED score.  No allocation or synchronisation happens inside spe_pnp_batch / spe_speed_score once the
-// per-stream scratch has its size, so a caller may capture them into a hipGraph.
+// SPEED score.  No allocation or synchronisation happens inside spe_pnp_batch / spe_pnp_exhaustive /
+// spe_speed_score once the per-stream scratch has its size, so a caller may capture them into a hipGraph.
 #include <hip/hip_runtime.h>
 
 #include <map>
@@ -41,7 +41,7 @@ static void* stream_scratch(hipStream_t stream, int kind, size_t bytes) {
   }
   return e.first;
 }
-enum { SCRATCH_CRITERION = 0, SCRATCH_HYP = 1, SCRATCH_CRITERION_SIGMA = 2 };
+enum { SCRATCH_CRITERION = 0, SCRATCH_HYP = 1, SCRATCH_CRITERION_SIGMA = 2, SCRATCH_EXH = 3 };
 
 extern "C" {
 
@@ -144,6 +144,45 @@ int spe_pnp_batch(void* stream, const float* points_px, const float* probs, cons
   }
   CK(spe_launch_pnp(a, (hipStream_t)stream));
   return 0;
+}
+
+static int pnp_exhaustive(void* stream, const float* points_px, const float* probs, const float* sigmas, int B, int Q,
+                          int C, const double* K, const double* world, float repro, int topk, float* quat, double* tvec,
+                          double* rvec, int32_t* status, int32_t* n_corr, int32_t* corr_label, uint32_t* inlier_mask,
+                          const float* repro_per_image, int32_t* cand_index, float* repro_final, int stages) {
+  if (!points_px || !probs || !K || !world || !quat || !tvec || B < 0 || Q <= 0 || Q > 64 || C < 2 || C > 17)
+    return fail(SPE_E_ARG, "bad argument");
+  if (topk < 1 || topk > 64) return fail(SPE_E_ARG, "topk must be in [1,64]");
+  if (stages < 1 || stages > 3) return fail(SPE_E_ARG, "bad stage mask");
+  if (B == 0) return 0;
+  PnpArgs a{};
+  a.points = points_px; a.probs = probs; a.sigmas = sigmas;
+  a.B = B; a.Q = Q; a.C = C; a.K = K; a.world = world; a.mode = SPE_PNP_EXHAUSTIVE; a.repro = repro;
+  a.repro_img = repro_per_image;
+  a.quat = quat; a.tvec = tvec; a.rvec = rvec; a.status = status; a.n_corr = n_corr;
+  a.corr_label = corr_label; a.inlier_mask = inlier_mask;
+  ExhRec* rec = (ExhRec*)stream_scratch((hipStream_t)stream, SCRATCH_EXH,
+                                        (size_t)B * spe_pnp_exhaustive_subsets(C) * sizeof(ExhRec));
+  if (!rec) return fail(SPE_E_LAUNCH, "hypothesis scratch allocation failed");
+  CK(spe_launch_pnp_exhaustive(a, rec, topk, cand_index, repro_final, stages, (hipStream_t)stream));
+  return 0;
+}
+
+int spe_pnp_exhaustive(void* stream, const float* points_px, const float* probs, const float* sigmas, int B, int Q, int C,
+                       const double* K, const double* world, float repro, int topk, float* quat, double* tvec,
+                       double* rvec, int32_t* status, int32_t* n_corr, int32_t* corr_label, uint32_t* inlier_mask,
+                       const float* repro_per_image, int32_t* cand_index, float* repro_final) {
+  return pnp_exhaustive(stream, points_px, probs, sigmas, B, Q, C, K, world, repro, topk, quat, tvec, rvec, status,
+                        n_corr, corr_label, inlier_mask, repro_per_image, cand_index, repro_final, 3);
+}
+
+int spe_debug_pnp_exhaustive_stages(void* stream, const float* points_px, const float* probs, const float* sigmas, int B,
+                                    int Q, int C, const double* K, const double* world, float repro, int topk,
+                                    float* quat, double* tvec, double* rvec, int32_t* status, int32_t* n_corr,
+                                    int32_t* corr_label, uint32_t* inlier_mask, const float* repro_per_image,
+                                    int32_t* cand_index, float* repro_final, int stages) {
+  return pnp_exhaustive(stream, points_px, probs, sigmas, B, Q, C, K, world, repro, topk, quat, tvec, rvec, status,
+                        n_corr, corr_label, inlier_mask, repro_per_image, cand_index, repro_final, stages);
 }
 
 int spe_self_assess(void* stream, const float* probs, const float* sigmas, const int32_t* status,

@@ -829,7 +829,240 @@ __global__ void self_assess_kernel(SelfAssessArgs a) {
   a.reliable[b] = (n > 0 && nconf >= a.min_inliers && ms < a.sigma_th) ? 1 : 0;
 }
 
+// ---------------------------------------------------------------- exhaustive four-point subsets
+// UNC PoseSolver.exhausive_pnp (UNC/utils/speed_eval_ceres.py:326-399) behind SimplePoseSolver.__call__
+// (:465-522): EPnP on every four-point subset of the selected correspondences, the topk smallest
+// four-point errors, and per kept hypothesis the inliers over all points, the sigma-weighted
+// Huber(0.001) LM on them and revert-if-worse; the candidate with the smallest error sum wins.
+
+// C(m, k) for k <= 4 (0 when m < k); m <= 16
+SPE_DEV int binom4(int m, int k) {
+  if (m < k) return 0;
+  switch (k) {
+    case 0: return 1;
+    case 1: return m;
+    case 2: return m * (m - 1) / 2;
+    case 3: return m * (m - 1) * (m - 2) / 6;
+    default: return m * (m - 1) * (m - 2) * (m - 3) / 24;
+  }
+}
+
+// subset `h` of itertools.combinations(range(n), 4) (lexicographic); h < C(n, 4)
+SPE_DEV void unrank_comb4(int n, int h, int* idx) {
+  int c = 0;
+  for (int i = 0; i < 4; ++i) {
+    // subsets that put c at position i: C(n - 1 - c, 3 - i); c cannot pass n - 4 + i
+    while (c < n - 4 + i) {
+      const int cnt = binom4(n - 1 - c, 3 - i);
+      if (h < cnt) break;
+      h -= cnt;
+      ++c;
+    }
+    idx[i] = c++;
+  }
+}
+
+// Hypotheses, one wave per (image, subset): the grid covers C(C-1, 4) subsets per image, waves
+// beyond the image's own C(n, 4) exit.  The four-point error is the float32 sum of squared
+// reprojection errors (cv2's reprojectionError is its RMSE: the same order); a pose or error that is
+// not finite is recorded as +inf and never selected.
+__global__ __launch_bounds__(WAVE) void pnp_exh_hyp_kernel(PnpArgs a, ExhRec* __restrict__ rec, int hmax) {
+  const int b = blockIdx.x / hmax, h = blockIdx.x - b * hmax;
+  const int lane = threadIdx.x;
+  __shared__ SelShared sel;
+  __shared__ float h_img[8], h_wld[12];
+  __shared__ EpnpShared s_ep;
+  select_correspondences(a, b, lane, sel);
+  const int nl = sel.nl;
+  if (nl < 4 || h >= binom4(nl, 4)) return;          // wave-uniform
+  if (lane < 4) {
+    int idx[4];
+    unrank_comb4(nl, h, idx);
+    const int j = idx[lane];
+    h_img[2 * lane] = sel.img[2 * j]; h_img[2 * lane + 1] = sel.img[2 * j + 1];
+    for (int c = 0; c < 3; ++c) h_wld[3 * lane + c] = sel.wld[3 * j + c];
+  }
+  __syncthreads();
+  const cam_t k = {a.K[0], a.K[4], a.K[2], a.K[5]};
+  double r[3], tt[3];
+  epnp_solve_wave(s_ep, &k, h_img, h_wld, 4, 0xFu, 1, r, tt, lane);
+  if (lane == 0) {
+    double R[9];
+    rodrigues_r2R(r, R);
+    float e = 0.f;
+    for (int i = 0; i < 4; ++i) {
+      float uv[2];
+      project_f(&k, R, tt, h_wld + 3 * i, uv);
+      e = e + sq_err_f(h_img + 2 * i, uv);
+    }
+    bool fin = isfinite(e);
+    for (int c = 0; c < 3; ++c) fin = fin && isfinite(r[c]) && isfinite(tt[c]);
+    ExhRec& o = rec[(size_t)b * hmax + h];
+    for (int c = 0; c < 3; ++c) { o.rt[c] = r[c]; o.rt[3 + c] = tt[c]; }
+    o.err = fin ? e : INFINITY;
+  }
+}
+
+constexpr int EXH_MAXH = 1820;     // C(16, 4)
+constexpr int EXH_MAXK = 64;
+constexpr int EXH_PASSES = 5;
+
+// Selection and refinement, one wave per image.
+__global__ __launch_bounds__(WAVE) void pnp_exh_refine_kernel(PnpArgs a, const ExhRec* __restrict__ rec, int hmax,
+                                                              int topk, int32_t* __restrict__ cand_index,
+                                                              float* __restrict__ repro_final) {
+  const int b = blockIdx.x;
+  const int lane = threadIdx.x;
+  __shared__ SelShared sel;
+  __shared__ LmShared s_lm;
+  __shared__ float s_e[EXH_MAXH];                 // four-point errors, +inf once taken
+  __shared__ int s_cand[EXH_MAXK];                // subset index of candidate j
+  __shared__ double s_rt[EXH_MAXK][6];
+  __shared__ float s_tab[EXH_MAXK][MAXN];         // candidate j's error on every correspondence
+  __shared__ float s_e4[EXH_MAXK];                // its 4th smallest error (+inf: never 4 inliers)
+  __shared__ float s_err[MAXN];
+
+  const cam_t k = {a.K[0], a.K[4], a.K[2], a.K[5]};
+  select_correspondences(a, b, lane, sel);
+  const int nl = sel.nl;
+  const double th0 = a.repro_img ? a.repro_img[b] : a.repro;
+
+  double rvec[3] = {0, 0, 0}, t[3] = {0, 0, 0}, th = th0;
+  int status = SPE_PNP_OK, win = -1;
+  uint32_t inl_win = 0;
+
+  if (nl == 0) {
+    status = SPE_PNP_NO_FG;
+  } else if (nl < 4) {
+    status = SPE_PNP_CV_ERROR;
+  } else {
+    const int H = binom4(nl, 4);
+    const ExhRec* const r0 = rec + (size_t)b * hmax;
+    for (int h = lane; h < H; h += WAVE) s_e[h] = r0[h].err;
+    __syncthreads();
+    // stable top-K: K rounds of the smallest (error, subset index) still present
+    int K = 0;
+    for (; K < topk; ++K) {
+      float be = INFINITY;
+      int bi = 0x7fffffff;
+      for (int h = lane; h < H; h += WAVE) {
+        const float e = s_e[h];
+        if (e < be) { be = e; bi = h; }             // ascending h per lane: the first of equals stays
+      }
+#pragma unroll
+      for (int o = 32; o > 0; o >>= 1) {
+        const float oe = __shfl_xor(be, o);
+        const int oi = __shfl_xor(bi, o);
+        if (oe < be || (oe == be && oi < bi)) { be = oe; bi = oi; }
+      }
+      if (!(be < INFINITY)) break;                  // wave-uniform: no finite record left
+      if (lane == 0) { s_cand[K] = bi; s_e[bi] = INFINITY; }
+      __syncthreads();
+    }
+    __syncthreads();
+    if (K == 0) {
+      status = SPE_PNP_UNPINNED;                    // no finite hypothesis
+    } else {
+      // every candidate's error table, one candidate per lane (epnp_init's arithmetic)
+      if (lane < K) {
+        const ExhRec& c = r0[s_cand[lane]];
+        double R[9], rt[6];
+        for (int i = 0; i < 6; ++i) { rt[i] = c.rt[i]; s_rt[lane][i] = rt[i]; }
+        rodrigues_r2R(rt, R);
+        float lo[4] = {INFINITY, INFINITY, INFINITY, INFINITY};   // the 4 smallest, ascending
+        for (int i = 0; i < nl; ++i) {
+          float uv[2];
+          project_f(&k, R, rt + 3, sel.wld + 3 * i, uv);
+          float e = repro_err_f(sel.img + 2 * i, uv);
+          s_tab[lane][i] = e;
+#pragma unroll
+          for (int p = 0; p < 4; ++p)
+            if (e < lo[p]) { const float x = lo[p]; lo[p] = e; e = x; }
+        }
+        s_e4[lane] = lo[3];
+      }
+      __syncthreads();
+      // Bounding the reference's `while rvec_opt is None` walk: candidate j has 4 inliers once
+      // th > e4[j] and every failing candidate adds 5, so with E = min e4 no candidate of a pass
+      // p < ((E - th0) / 5 - (K - 1)) / K can qualify and one of the next three must.  Passes
+      // before that bound (less one for rounding) are skipped by adding their K failures each.
+      float E = INFINITY;
+      for (int j = 0; j < K; ++j) E = fminf(E, s_e4[j]);
+      if (!(E < INFINITY)) {
+        status = SPE_PNP_UNPINNED;                  // no candidate can ever reach 4 inliers
+      } else {
+        double fails = 0;                           // failing candidates so far: th = th0 + 5 * fails
+        const double x = floor((((double)E - th0) / 5.0 - (double)(K - 1)) / (double)K) - 1.0;
+        if (x > 0) fails = x * (double)K;
+        double err_opt = 100000;
+        bool qualified = false;
+        for (int pass = 0; pass < EXH_PASSES && !qualified; ++pass) {
+          for (int j = 0; j < K; ++j) {
+            th = th0 + 5.0 * fails;
+            const uint32_t inl = (uint32_t)__ballot(lane < nl && (double)s_tab[j][lane] < th);
+            const int m = __popc(inl);
+            if (m < 4) { fails += 1; continue; }    // wave-uniform
+            qualified = true;
+            const float before = np_sum_f32(s_tab[j], nl);
+            double r1[3] = {s_rt[j][0], s_rt[j][1], s_rt[j][2]}, t1[3] = {s_rt[j][3], s_rt[j][4], s_rt[j][5]};
+            double r2[3] = {r1[0], r1[1], r1[2]}, t2[3] = {t1[0], t1[1], t1[2]};
+            sigma_lm_wave(s_lm, &k, lm_point(sel.img, sel.wld, sel.sig, nl, inl, lane), m, 0.001, r2, t2, lane);
+            const float after = repro_errors_wave(s_err, &k, sel.img, sel.wld, nl, r2, t2, lane);
+            const bool worse = after > before;
+            const double rep = worse ? before : after;
+            if (err_opt > rep) {
+              err_opt = rep;
+              win = s_cand[j];
+              inl_win = inl;
+              for (int c = 0; c < 3; ++c) { rvec[c] = worse ? r1[c] : r2[c]; t[c] = worse ? t1[c] : t2[c]; }
+            }
+          }
+        }
+        th = th0 + 5.0 * fails;
+        // every qualifying candidate summed to 100000 px or more, or to NaN: the reference would walk
+        // forever; defined here as no pose
+        if (win < 0) status = SPE_PNP_UNPINNED;
+      }
+    }
+  }
+
+  if (lane != 0) return;
+  const bool have_pose = status == SPE_PNP_OK;
+  float qf[4] = {0.f, 0.f, 0.f, 0.f};
+  if (have_pose) {
+    double R[9];
+    rodrigues_r2R(rvec, R);
+    blender_quat(R, qf);
+  } else {
+    t[0] = t[1] = t[2] = 0;
+    win = -1;
+    inl_win = 0;
+  }
+  for (int i = 0; i < 4; ++i) a.quat[4 * b + i] = qf[i];
+  for (int i = 0; i < 3; ++i) a.tvec[3 * b + i] = t[i];
+  if (a.rvec) for (int i = 0; i < 3; ++i) a.rvec[3 * b + i] = have_pose ? rvec[i] : 0.0;
+  if (a.status) a.status[b] = status;
+  if (a.n_corr) a.n_corr[b] = nl;
+  if (a.inlier_mask) a.inlier_mask[b] = inl_win;
+  if (a.corr_label) for (int j = 0; j < MAXN; ++j) a.corr_label[MAXN * b + j] = j < nl ? sel.order[j] : -1;
+  if (cand_index) cand_index[b] = win;
+  if (repro_final) repro_final[b] = (float)th;
+}
+
 }  // namespace
+
+int spe_pnp_exhaustive_subsets(int C) { return C - 1 >= 4 ? (C - 1) * (C - 2) * (C - 3) * (C - 4) / 24 : 1; }
+
+int spe_launch_pnp_exhaustive(const PnpArgs& a, ExhRec* rec, int topk, int32_t* cand_index, float* repro_final,
+                              int stages, hipStream_t s) {
+  if (a.B <= 0) return 0;
+  if (a.Q > WAVE || a.C < 2 || a.C - 1 > MAXN || topk < 1 || topk > EXH_MAXK || !rec) return -7;
+  const int hmax = spe_pnp_exhaustive_subsets(a.C);
+  if (stages & 1) hipLaunchKernelGGL(pnp_exh_hyp_kernel, dim3(a.B * hmax), dim3(WAVE), 0, s, a, rec, hmax);
+  if (stages & 2)
+    hipLaunchKernelGGL(pnp_exh_refine_kernel, dim3(a.B), dim3(WAVE), 0, s, a, rec, hmax, topk, cand_index, repro_final);
+  return (int)hipGetLastError();
+}
 
 int spe_launch_self_assess(const SelfAssessArgs& a, hipStream_t s) {
   if (a.B <= 0) return 0;

@@ -35,6 +35,19 @@ struct PnpArgs {
 };
 int spe_launch_pnp(const PnpArgs& a, hipStream_t s);
 
+// One four-point EPnP hypothesis of the exhaustive solver (pnp_exh_hyp_kernel -> pnp_exh_refine_kernel)
+struct ExhRec {
+  double rt[6];            // rvec, tvec
+  float err;               // float32 sum of the 4 squared reprojection errors; +inf: not finite, never selected
+  int pad;
+};
+// records per image: C(C-1, 4), the subsets of a full set of landmarks
+int spe_pnp_exhaustive_subsets(int C);
+// SPE_PNP_EXHAUSTIVE on PnpArgs (mode, ransac_iters, confidence, hyp unused); rec: [B][spe_pnp_exhaustive_subsets(C)].
+// stages: bit 0 the hypothesis kernel, bit 1 selection + refinement (3 = the solver).
+int spe_launch_pnp_exhaustive(const PnpArgs& a, ExhRec* rec, int topk, int32_t* cand_index, float* repro_final,
+                              int stages, hipStream_t s);
+
 struct SelfAssessArgs {
   const float* probs;         // [B][Q][C]
   const float* sigmas;        // [B][Q][2]

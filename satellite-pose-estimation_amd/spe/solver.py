@@ -178,6 +178,67 @@ class EPnPCeresSolver(PoseSolver):
         return PoseSolver.__call__(self, points, logits, sigma, device=device)
 
 
+class ExhaustivePoseSolver(PoseSolver):
+    """UNC PoseSolver(pnp_method="exhausive") behind SimplePoseSolver.__call__
+    (UNC/utils/speed_eval_ceres.py:326-399, :465-522): EPnP on every four-point subset of the selected
+    correspondences, the `topk` smallest four-point errors, and per kept hypothesis the inliers over
+    all points (threshold + 5 whenever fewer than 4), the sigma-weighted Huber(0.001) LM on them and
+    revert-if-worse; the candidate with the smallest error sum wins.  Draws no samples: the result is a
+    function of the correspondences alone.  What is unpinned: include/spe.h, SPE_PNP_EXHAUSTIVE."""
+
+    def __init__(self, topk=10, input_size=256, repro=20.0):
+        topk = int(topk)
+        if not 1 <= topk <= 64:
+            raise ValueError(f"topk must be in [1, 64], got {topk}")
+        super().__init__(_lib.SPE_PNP_EXHAUSTIVE, repro)
+        self.topk = topk
+        self.input_size = input_size
+
+    repro_th = EPnPCeresSolver.repro_th
+    get_repro_th = EPnPCeresSolver.get_repro_th
+
+    def solve_batch(self, points_px, probs, sigmas=None, stream=None, out=None, repro_per_image=None, area=None):
+        """As PoseSolver.solve_batch plus cand_index [B] i32 (the winner's subset index, -1 without a
+        pose) and repro_final [B] f32 (the threshold after growth).  `area` (B box areas, get_repro_th
+        each) or `repro_per_image` (device fp32 [B]) gives one threshold per image; with neither the
+        batch-wide reprojectionError is used."""
+        B, Q, C = probs.shape
+        dev = probs.device
+        Kd, Wd = self._consts(dev)
+        if repro_per_image is None and area is not None:
+            repro_per_image = torch.tensor([self.repro_th(float(a)) for a in area], dtype=torch.float32, device=dev)
+        if repro_per_image is not None:
+            repro_per_image = repro_per_image.float().contiguous()
+        if out is None:
+            out = dict(quat=torch.empty(B, 4, device=dev), tvec=torch.empty(B, 3, dtype=torch.float64, device=dev),
+                       rvec=torch.empty(B, 3, dtype=torch.float64, device=dev),
+                       status=torch.empty(B, dtype=torch.int32, device=dev),
+                       n_corr=torch.empty(B, dtype=torch.int32, device=dev),
+                       corr_label=torch.empty(B, 16, dtype=torch.int32, device=dev),
+                       inlier_mask=torch.empty(B, dtype=torch.int32, device=dev))
+        for k, dt in (("cand_index", torch.int32), ("repro_final", torch.float32)):
+            if k not in out:
+                out[k] = torch.empty(B, dtype=dt, device=dev)
+        _lib.check(_lib.lib().spe_pnp_exhaustive(
+            _lib.stream_ptr(stream), _lib.ptr(points_px.contiguous()), _lib.ptr(probs.contiguous()),
+            _lib.ptr(sigmas.contiguous() if sigmas is not None else None), B, Q, C, _lib.ptr(Kd), _lib.ptr(Wd),
+            self.reprojectionError, self.topk, _lib.ptr(out["quat"]), _lib.ptr(out["tvec"]), _lib.ptr(out["rvec"]),
+            _lib.ptr(out["status"]), _lib.ptr(out["n_corr"]), _lib.ptr(out["corr_label"]),
+            _lib.ptr(out["inlier_mask"]), _lib.ptr(repro_per_image), _lib.ptr(out["cand_index"]),
+            _lib.ptr(out["repro_final"])), "spe_pnp_exhaustive")
+        if repro_per_image is not None:
+            # the kernel may still read the thresholds on `stream` after this returns
+            if stream is not None:
+                repro_per_image.record_stream(stream)
+            out["repro_per_image"] = repro_per_image
+        return out
+
+    def __call__(self, points, logits, area, sigma=None, device=None):
+        """One image, the reference's signature (:473) plus the optional sigmas: numpy in / numpy out."""
+        self.get_repro_th(area)
+        return PoseSolver.__call__(self, points, logits, sigma, device=device)
+
+
 class Multi_Mean_PoseSolver(PoseSolver):
     """Multi-checkpoint ensemble (REV/utils/speed_eval.py:42-140): the M models' keypoints are
     fused per label (mean after a 3-sigma filter, first-seen label order) on the device
@@ -223,4 +284,7 @@ def build_solver(args=None):
         return EPnPSolver(args, refine=name == "epnp_lm")
     if name == "epnp_ceres":
         return EPnPCeresSolver(getattr(args, "input_size", 256) if args is not None else 256)
+    if name == "exhaustive":
+        return ExhaustivePoseSolver(getattr(args, "topk", 10), getattr(args, "input_size", 256),
+                                    getattr(args, "repro", 20.0))
     raise ValueError(f"unknown solver {name}")
