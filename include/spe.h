@@ -224,6 +224,24 @@ int spe_forward_stages(spe_model* m, void* stream, const float* images, int batc
 int spe_forward_stages_u8(spe_model* m, void* stream, const uint8_t* crops, int channels, int batch, void* workspace,
                           int64_t workspace_bytes, const spe_forward_outputs* out, int stages);
 
+/* spe_forward that also exports attention maps: what the reference's visualize_features.py hooks
+ * (REV/visualize_features.py, output[1] of nn.MultiheadAttention: the probabilities averaged over the 8
+ * heads) from transformer.encoder.layers[enc_layer].self_attn into enc_map, device fp32 [B,T,T] (T =
+ * (input_size / 8)^2 tokens, row = query token, h * W + w order), and from
+ * transformer.decoder.layers[dec_layer].multihead_attn into dec_map, device fp32 [B,Q,T].  The same
+ * launch sequence as spe_forward (`out` is bit-identical) plus one launch of the map kernel (attn_map.hip)
+ * per map, on the q / k operands the tapped layer's own attention kernel reads, in that mode's storage.
+ * Either map may be NULL (that tap is skipped), not both.  Negative layer indices count from the end; the
+ * reference's choice is enc_layer = -1, dec_layer = -2.  Graph-capturable like spe_forward.  Model dtypes
+ * BF16_ (attn_dtype F16_ included) and F32_; SPE_E_ARG, before anything is launched, for the split-precision
+ * modes (F32X3_ / F32X6_ / F32H3_: their operands live as split planes), an RT-DETR handle, a layer index out
+ * of range, both maps NULL.  The workspace is spe_forward_attention_workspace_bytes (today equal to
+ * spe_model_workspace_bytes: every served mode leaves q and k in the forward's own workspace). */
+int64_t spe_forward_attention_workspace_bytes(const spe_model* m, int batch);
+int spe_forward_attention(spe_model* m, void* stream, const float* images, int batch, void* workspace,
+                          int64_t workspace_bytes, const spe_forward_outputs* out, int enc_layer, int dec_layer,
+                          float* enc_map, float* dec_map);
+
 /* spe_rtdetr_forward in stages, with the SPE_STAGE_* bits read for the RT-DETR model:
  *   BACKBONE     the backbone: images -> the stride 8 / 16 / 32 maps, kept in `workspace`
  *   TRANSFORMER  the HybridEncoder (input_proj, AIFI, FPN, PAN): the maps -> the three level outputs, kept
@@ -453,6 +471,11 @@ int spe_debug_gemm_planes(void* stream, int dtype, int mode, const void* A, int 
  * | 0x400 on top = the V^T planes as fp16 hi / lo (the fp32h3 model's form, here unscaled) (ABI 8) */
 int spe_debug_attention(void* stream, int dtype, const void* q, int ldq, const void* k, int ldk, const void* vt,
                         void* o, int ldo, int B, int H, int Tq, int Tk, float scale);
+/* the attention-map kernel (attn_map.hip) on caller operands: out[b][i][j] = (1/H) sum_h softmax_j(q_h[b][i] .
+ * k_h[b][j] / sqrt(32)), fp32 [B][Tq][Tk]; q [B][H][Tq][32], k [B][H][Tk][32] of dtype BF16_ / F16_ / F32_, H = 8.
+ * dtype BF16_ | 0x100: the bf16 decoder's folded cross-attention form, q' [B][Tq][8*256] already in the exp2
+ * domain against one k [B][Tk][256] for every head: softmax_j of exp2(q'_h[b][i] . k[b][j]). */
+int spe_debug_attn_map(void* stream, const void* q, const void* k, int B, int H, int Tq, int Tk, int dtype, float* out);
 int spe_debug_layernorm(void* stream, int dtype, const void* x, const float* gamma, const float* beta, void* out,
                         float* out_f32, int M, int D);
 /* ffn (bf16 only): y = LayerNorm(x + W2 relu(W1 x + b1) + b2), D == 256, F % 32 == 0; x and y may

@@ -4,6 +4,8 @@
 // tiles, strides) — the forward pass alone would hide a wrong-but-normalised intermediate.
 #include <hip/hip_runtime.h>
 
+#include <cmath>
+
 #include "../../include/spe.h"
 #include "model_state.h"
 
@@ -95,6 +97,27 @@ int spe_debug_attention(void* stream, int dtype, const void* q, int ldq, const v
   a.v_f16 = (dtype >> 10) & 1;                     // (unscaled fp16 V^T planes: v_amax null)
   int rc = spe_launch_attention(a, dtype & 255, (hipStream_t)stream);
   return rc < 0 ? spe_fail(SPE_E_LAUNCH, "attention launch rejected its arguments") : rc;
+}
+
+int spe_debug_attn_map(void* stream, const void* q, const void* k, int B, int H, int Tq, int Tk, int dtype, float* out) {
+  if (!q || !k || !out || B <= 0 || H != 8 || Tq <= 0 || Tk <= 0) return spe_fail(SPE_E_ARG, "bad argument");
+  const int dt = dtype & 255;
+  if (dt != SPE_DTYPE_BF16 && dt != SPE_DTYPE_F32 && dt != SPE_DTYPE_F16) return spe_fail(SPE_E_ARG, "attn_map: dtype bf16, fp16 or fp32");
+  AttnMapArgs a{};
+  a.q = q; a.k = k; a.out = out;
+  a.B = B; a.H = H; a.Tq = Tq; a.Tk = Tk;
+  if (dtype & 0x100) {                           // the folded decoder form: q' [B][Tq][8*256], k [B][Tk][256]
+    if (dt != SPE_DTYPE_BF16) return spe_fail(SPE_E_ARG, "attn_map: the folded form is bf16");
+    a.q_sb = (long long)Tq * H * 256; a.q_sh = 256; a.ldq = H * 256;
+    a.k_sb = (long long)Tk * 256; a.k_sh = 0; a.ldk = 256;
+    a.head_dim = 256; a.base2 = 1; a.scale = 1.f;
+  } else {                                       // q [B][H][Tq][32], k [B][H][Tk][32]
+    a.q_sb = (long long)H * Tq * 32; a.q_sh = (long long)Tq * 32; a.ldq = 32;
+    a.k_sb = (long long)H * Tk * 32; a.k_sh = (long long)Tk * 32; a.ldk = 32;
+    a.head_dim = 32; a.scale = 1.0f / std::sqrt(32.0f);   // (forward.cpp's)
+  }
+  const int rc = spe_launch_attn_map(a, dt, (hipStream_t)stream);
+  return rc < 0 ? spe_fail(SPE_E_LAUNCH, "attn_map launch rejected its arguments") : rc;
 }
 
 int spe_debug_layernorm(void* stream, int dtype, const void* x, const float* gamma, const float* beta, void* out,

@@ -21,6 +21,14 @@
 
 namespace {
 
+// spe_forward_attention's taps (attn_map.hip): the head-averaged attention probabilities of encoder layer
+// enc_layer's self-attention into enc_map [B][T][T] and of decoder layer dec_layer's cross-attention into
+// dec_map [B][Q][T]; a null map skips its tap.  Layer indices are resolved (>= 0) by the entry point.
+struct AttnTap {
+  int enc_layer, dec_layer;
+  float *enc_map, *dec_map;
+};
+
 // One forward call: the model, the workspace plan and the call's sizes.  What flows between stages flows
 // through the workspace (src, srcpos, ck / cvt, the activation-scale slots), never through this struct.
 struct Fwd {
@@ -36,6 +44,7 @@ struct Fwd {
   // [SPE_AMAX_BB, SPE_AMAX_SLOTS); each stage zeroes its own range first.
   float* amx;
   LedgerScope& ledger;
+  const AttnTap* tap;        // spe_forward_attention only, else null
   void* P(size_t off) const { return ws + off; }
   float* slot(int i) const { return amx ? amx + i : nullptr; }
 };
@@ -353,6 +362,23 @@ int enc_self_attention(Fwd& f, const Enc& e, const EncAttn& ea, const float* src
   return 0;
 }
 
+// spe_forward_attention: the map of the self-attention whose q / k enc_self_attention left in qkv (the
+// operands its attention kernel read: bf16, fp16 with attn_dtype fp16, or fp32)
+int enc_attn_map(Fwd& f, const EncAttn& ea, float* map) {
+  spe_model* m = f.m;
+  const int d = f.d, T = f.T;
+  AttnMapArgs a{};
+  a.q = f.P(f.w.qkv); a.q_sb = (long long)T * 3 * d; a.q_sh = 32; a.ldq = 3 * d;
+  a.k = (char*)f.P(f.w.qkv) + d * m->esz; a.k_sb = a.q_sb; a.k_sh = 32; a.ldk = 3 * d;
+  a.out = map;
+  a.B = f.B; a.H = m->cfg.nheads; a.Tq = T; a.Tk = T; a.head_dim = 32; a.scale = f.scale;
+  const double fl = 2.0 * 2.0 * f.B * 8.0 * T * (double)T * 32;
+  const double by = (double)f.B * T * (double)T * 4 + 2.0 * f.Mt * d * m->esz;
+  const int dt = ea.f16attn ? SPE_DTYPE_F16 : f.dt;
+  CK(run_other(m, "attn.map", fl, by, f.s, [&] { return spe_launch_attn_map(a, dt, f.s); }));
+  return 0;
+}
+
 // encoder layer li over src (in place); *src_amax: the scale input of src, before and after
 int encoder_layer(Fwd& f, const Enc& e, int li, const EncAttn& ea, const float** src_amax) {
   spe_model* m = f.m;
@@ -361,6 +387,7 @@ int encoder_layer(Fwd& f, const Enc& e, int li, const EncAttn& ea, const float**
   const int d = f.d, ff = f.ff, Mt = f.Mt;
   float* const o_amax = f.slot(SPE_AMAX_BB + 2 * li);
   TRY(enc_self_attention(f, e, ea, *src_amax, o_amax));
+  if (f.tap && f.tap->enc_map && f.tap->enc_layer == li) TRY(enc_attn_map(f, ea, f.tap->enc_map));
   {
     // out-proj + residual; bf16 large batches fuse norm1 into the GEMM epilogue, in place over src
     GemmArgs gf = linear_args(e.o, f.P(w.ao), d, Mt, f.P(w.src), d);
@@ -594,6 +621,32 @@ int dec_xattn(Fwd& f, const Dec& e, int l, const float* tgt_amax, const float** 
   return 0;
 }
 
+// spe_forward_attention: the map of layer l's cross-attention from the operands its attention kernel
+// read.  Against the memory (bf16, xattn.hip): the folded q' [B*Q][8*256] in xq, already in the exp2
+// domain, and memory + pos in srcpos as every head's key.  Else the projected q in dqc and layer l's
+// slice of the projected keys ck.
+int dec_attn_map(Fwd& f, int l, float* map) {
+  spe_model* m = f.m;
+  const Ws& w = f.w;
+  const int Q = f.Q, T = f.T, d = f.d, L = f.L;
+  AttnMapArgs a{};
+  a.out = map;
+  a.B = f.B; a.H = m->cfg.nheads; a.Tq = Q; a.Tk = T;
+  if (spe_use_xattn(m)) {
+    a.q = f.P(w.xq); a.q_sb = (long long)Q * 8 * d; a.q_sh = d; a.ldq = 8 * d;
+    a.k = f.P(w.srcpos); a.k_sb = (long long)T * d; a.k_sh = 0; a.ldk = d;
+    a.head_dim = d; a.base2 = 1; a.scale = 1.f;
+  } else {
+    a.q = f.P(w.dqc); a.q_sb = (long long)Q * d; a.q_sh = 32; a.ldq = d;
+    a.k = (char*)f.P(w.ck) + (size_t)l * d * m->esz; a.k_sb = (long long)T * L * d; a.k_sh = 32; a.ldk = L * d;
+    a.head_dim = 32; a.scale = f.scale;
+  }
+  const double fl = 2.0 * 2.0 * f.B * 8.0 * Q * (double)T * a.head_dim;
+  const double by = (double)f.B * Q * (double)T * 4 + (double)f.Mt * d * m->esz;
+  CK(run_other(m, "attn.map", fl, by, f.s, [&] { return spe_launch_attn_map(a, f.dt, f.s); }));
+  return 0;
+}
+
 // cross-attention block of layer l: attention against the memory or its projected K / V^T (ck / cvt),
 // out-projection, norm2 over tgt
 int dec_cross_block(Fwd& f, const Dec& e, int l, const float* tgt_amax) {
@@ -621,6 +674,7 @@ int dec_cross_block(Fwd& f, const Dec& e, int l, const float* tgt_amax) {
     a.B = B; a.H = m->cfg.nheads; a.Tq = Q; a.Tk = T; a.scale = f.scale;
     CK(run_attn(m, "attn.dec_cross", a, f.dt, s));
   }
+  if (f.tap && f.tap->dec_map && f.tap->dec_layer == l) TRY(dec_attn_map(f, l, f.tap->dec_map));
   if (!xtail) TRY(dec_proj_ln(f, e.co, e.fco, e.n2g, e.n2b, cross_o_amax));
   return 0;
 }
@@ -705,7 +759,7 @@ int decoder_stage(Fwd& f, const spe_forward_outputs& out) {
 }
 
 int forward_stages(spe_model* m, void* stream, const ImageSrc& images, int B, void* workspace, int64_t ws_bytes,
-                   const spe_forward_outputs* out, int stages) {
+                   const spe_forward_outputs* out, int stages, const AttnTap* tap = nullptr) {
   if (!m || !workspace || B <= 0 ||
       (stages & ~(SPE_STAGE_ENCODE | SPE_STAGE_DECODE | SPE_STAGE_BACKBONE | SPE_STAGE_TRANSFORMER)) || !stages)
     return fail(SPE_E_ARG, "bad argument");
@@ -721,7 +775,7 @@ int forward_stages(spe_model* m, void* stream, const ImageSrc& images, int B, vo
   float* const amx = m->h3 ? (float*)((char*)workspace + w.amax) : nullptr;
   LedgerScope ledger(amx);
   Fwd f{m, w, (char*)workspace, (hipStream_t)stream, B, c.input_size, F, F * F, c.hidden_dim, c.dim_feedforward,
-        c.num_queries, c.dec_layers, B * F * F, B * c.num_queries, c.dtype, 1.0f / std::sqrt(32.0f), amx, ledger};
+        c.num_queries, c.dec_layers, B * F * F, B * c.num_queries, c.dtype, 1.0f / std::sqrt(32.0f), amx, ledger, tap};
   // (the slot counts are checked before anything is launched: a slot handed out past its range would
   // be the encoder's input scale or a transformer slot, overwritten before an error could return)
   if (amx && (stages & SPE_STAGE_BACKBONE) && 2 + 3 * (int)m->blocks.size() + 2 > SPE_AMAX_BB - 1)
@@ -755,6 +809,28 @@ int spe_forward_stages_u8(spe_model* m, void* stream, const uint8_t* crops, int 
   if ((stages & (SPE_STAGE_ENCODE | SPE_STAGE_BACKBONE)) && (!crops || (channels != 1 && channels != 3)))
     return fail(SPE_E_ARG, "u8 crops: device pointer, 1 or 3 channels");
   return forward_stages(m, stream, ImageSrc{nullptr, crops, channels}, B, workspace, ws_bytes, out, stages);
+}
+
+int64_t spe_forward_attention_workspace_bytes(const spe_model* m, int B) {
+  // (every mode the taps serve reads operands the forward pass leaves in its own workspace)
+  return spe_model_workspace_bytes(m, B);
+}
+
+int spe_forward_attention(spe_model* m, void* stream, const float* images, int B, void* workspace, int64_t ws_bytes,
+                          const spe_forward_outputs* out, int enc_layer, int dec_layer, float* enc_map,
+                          float* dec_map) {
+  if (!m) return fail(SPE_E_ARG, "bad argument");
+  if (m->family != 0) return fail(SPE_E_ARG, "not a DETR model (attention maps: the DETR keypoint model only)");
+  if (m->x3)
+    return fail(SPE_E_ARG, "attention maps: supported modes are bf16 (attn_dtype fp16 included) and fp32; the "
+                           "split-precision modes (fp32x3 / fp32x6 / fp32h3) keep their operands as split planes");
+  if (!enc_map && !dec_map) return fail(SPE_E_ARG, "attention maps: enc_map and dec_map are both null");
+  const int EL = m->cfg.enc_layers, DL = m->cfg.dec_layers;
+  AttnTap tap{enc_layer < 0 ? enc_layer + EL : enc_layer, dec_layer < 0 ? dec_layer + DL : dec_layer, enc_map, dec_map};
+  if (enc_map && (tap.enc_layer < 0 || tap.enc_layer >= EL)) return fail(SPE_E_ARG, "attention maps: enc_layer out of range");
+  if (dec_map && (tap.dec_layer < 0 || tap.dec_layer >= DL)) return fail(SPE_E_ARG, "attention maps: dec_layer out of range");
+  return forward_stages(m, stream, ImageSrc{images, nullptr, 0}, B, workspace, ws_bytes, out,
+                        SPE_STAGE_ENCODE | SPE_STAGE_DECODE, &tap);
 }
 
 }  // extern "C"

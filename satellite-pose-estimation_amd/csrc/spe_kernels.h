@@ -121,6 +121,20 @@ struct AttnArgs {
 int spe_launch_attention_split(const AttnArgs& a, hipStream_t s);
 int spe_launch_attention(const AttnArgs& a, int dtype, hipStream_t s);
 
+// Head-averaged attention probabilities (attn_map.hip, the diagnostic tap of spe_forward_attention):
+// out[b][i][j] = (1/8) sum_h softmax_j(scale q_h[b][i] . k_h[b][j]), fp32 [B][Tq][Tk].  Strides in
+// elements; dtype SPE_DTYPE_BF16 / _F16 / _F32 is the storage of q and k.
+struct AttnMapArgs {
+  const void* q; long long q_sb, q_sh; int ldq;   // q_h[b][i] at q + b q_sb + h q_sh + i ldq, head_dim elements
+  const void* k; long long k_sb, k_sh; int ldk;   // k_h[b][j] likewise (k_sh = 0: one k for every head)
+  float* out;
+  int B, H, Tq, Tk;                // H == 8
+  int head_dim;                    // 32, or 256 (bf16, base2: the folded decoder cross-attention, xattn.hip)
+  float scale;                     // softmax scale (ignored with base2)
+  int base2;                       // q pre-scaled by scale . log2 e: softmax_j of exp2(q . k)
+};
+int spe_launch_attn_map(const AttnMapArgs& a, int dtype, hipStream_t s);   // -1: arguments outside the contract
+
 // Decoder cross-attention against the encoder memory (bf16 path, xattn.hip): per image b and
 // attention row r = q * 8 + h, u[b][q][h] = softmax(q'[b][q][h] . K^T) . V with K = memory +
 // pos [T][256], V = memory [T][256], q' pre-scaled into the exp2 domain.

@@ -55,7 +55,8 @@ EXPORTS = ["spe_abi_version", "spe_last_error", "spe_model_create", "spe_model_d
            "spe_rtdetr_forward_stages", "spe_rtdetr_forward_stages_u8",
            "spe_jpeg_workspace_bytes", "spe_jpeg_decode",
            "spe_debug_dwconv_tiles", "spe_debug_dwconv", "spe_debug_se_gate", "spe_debug_pwconv", "spe_debug_rtdetr_backbone",
-           "spe_debug_ghost_cheap", "spe_debug_dfc_gate", "spe_debug_se_gate_bias", "spe_debug_pool2"]
+           "spe_debug_ghost_cheap", "spe_debug_dfc_gate", "spe_debug_se_gate_bias", "spe_debug_pool2",
+           "spe_forward_attention", "spe_forward_attention_workspace_bytes", "spe_debug_attn_map"]
 
 
 class ModelConfig(ctypes.Structure):
@@ -112,6 +113,10 @@ def load(path: str):
     L.spe_forward.argtypes = [P, P, P, I, P, I64, ctypes.POINTER(ForwardOutputs)]
     L.spe_forward_stages.argtypes = [P, P, P, I, P, I64, ctypes.POINTER(ForwardOutputs), I]
     L.spe_forward_stages_u8.argtypes = [P, P, P, I, I, P, I64, ctypes.POINTER(ForwardOutputs), I]
+    L.spe_forward_attention.argtypes = [P, P, P, I, P, I64, ctypes.POINTER(ForwardOutputs), I, I, P, P]
+    L.spe_forward_attention_workspace_bytes.argtypes = [P, I]
+    L.spe_forward_attention_workspace_bytes.restype = I64
+    L.spe_debug_attn_map.argtypes = [P, P, P, I, I, I, I, I, P]
     L.spe_postprocess.argtypes = [P, P, P, P, I, I, P, P]
     L.spe_preprocess.argtypes = [P, P, I, I, I, I, P, I, P, P, P]
     L.spe_preprocess_submission.argtypes = [P, P, I, I, I, I, P, I, P, P, P, P]

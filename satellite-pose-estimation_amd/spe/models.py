@@ -206,6 +206,45 @@ class DETR(nn.Module):
                                           ws.numel(), ctypes.byref(o)), "spe_forward")
         return out
 
+    def forward_with_attention(self, images, enc_layer=-1, dec_layer=-2, clip_bbox=None, *, stream=None, maps=None):
+        """forward() plus the attention maps the reference's visualize_features.py hooks: the head-averaged
+        probabilities of transformer.encoder.layers[enc_layer].self_attn ("enc", [B,T,T], T = (S/8)^2
+        tokens) and transformer.decoder.layers[dec_layer].multihead_attn ("dec", [B,Q,T]), device fp32.
+        Returns (outputs, maps); `outputs` is forward()'s dict, bit for bit.  Model dtypes bf16 and fp32.
+        `maps` (optional): {"enc": tensor or None, "dec": tensor or None} of caller buffers to fill; None
+        skips that tap (spe_forward_attention's NULL map)."""
+        if self._handle is None:
+            raise RuntimeError("DETR: load_state_dict() with every parameter before forward_with_attention()")
+        if not images.is_cuda:
+            raise RuntimeError("DETR (HIP) expects device tensors; call samples.to('cuda')")
+        images = images.contiguous().float()
+        B, C, H, W = images.shape
+        S = self.cfg.input_size
+        if C != 3 or H != S or W != S:
+            raise ValueError(f"expected [B,3,{S},{S}] input, got {tuple(images.shape)}")
+        dev = images.device
+        if clip_bbox is not None:
+            clip_bbox = clip_bbox.to(device=dev, dtype=torch.float32).contiguous()
+        out, o = self._outputs(B, dev, clip_bbox, False)
+        T = (S // 8) ** 2
+        shapes = {"enc": (B, T, T), "dec": (B, self.cfg.num_queries, T)}
+        if maps is None:
+            maps = {k: torch.empty(*s, device=dev) for k, s in shapes.items()}
+        else:
+            maps = {k: maps.get(k) for k in shapes}
+            for k, t in maps.items():
+                if t is not None and (tuple(t.shape) != shapes[k] or t.dtype != torch.float32 or t.device != dev
+                                      or not t.is_contiguous()):
+                    raise ValueError(f"maps[{k!r}]: a contiguous fp32 {shapes[k]} tensor on {dev}")
+        L = _lib.lib()
+        ws = self.workspace(B, dev, stream)
+        if ws.numel() < int(L.spe_forward_attention_workspace_bytes(self._h, B)):
+            raise RuntimeError("forward_with_attention: the forward workspace no longer covers the taps")
+        _lib.check(L.spe_forward_attention(self._h, _lib.stream_ptr(stream), _lib.ptr(images), B, _lib.ptr(ws),
+                                           ws.numel(), ctypes.byref(o), int(enc_layer), int(dec_layer),
+                                           _lib.ptr(maps["enc"]), _lib.ptr(maps["dec"])), "spe_forward_attention")
+        return out, {k: t for k, t in maps.items() if t is not None}
+
     def __del__(self):
         try:
             if getattr(self, "_h", None):
