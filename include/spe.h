@@ -614,6 +614,46 @@ int spe_debug_se_gate_bias(void* stream, const float* pool_partials, int tiles, 
 /* pool2: 2 x 2 mean, NHWC x [B][H][W][C] -> y [B][H/2][W/2][C]; H, W even, C % 8 == 0. */
 int spe_debug_pool2(void* stream, int dtype, const void* x, void* y, int B, int H, int W, int C);
 
+/* RT-DETR kernels (rtdetr.hip, ABI 9 additions): each hook fills the kernel's argument struct and returns the
+ * launcher's own code: 0, a hipError_t, or -5 when the arguments are outside the kernel's contract (refused
+ * before any launch; spe_last_error is not set).  dtype BF16_ or F32_ is the type T of the buffers marked T;
+ * everything else is fp32.  A channel slice of a wider buffer is passed as the pointer of its first column.
+ * rt_resample2x: NHWC in [B][H][W][ldi] T -> out [B][Ho][Wo][ldo] T over C channels; mode 0 nearest x2, mode 1
+ * bicubic x0.5 (align_corners=False, a = -0.75, clamped taps; H and W even).  C, ldi, ldo multiples of the
+ * 16-byte chunk (8 bf16, 4 fp32). */
+int spe_debug_rt_resample2x(void* stream, int dtype, const void* in, int ldi, void* out, int ldo, int B, int H, int W,
+                            int C, int mode);
+/* rt_query_select: per image the Q tokens of highest max-over-classes logit, descending, the lower token index
+ * first among equal scores.  Rows are level-major: token t of level l of image b is row B*lvl_start[l] +
+ * b*hw_l + (t - lvl_start[l]); lvl_start (host) has levels + 1 entries, the last one L.  logits [rows][C],
+ * memory [rows][ldm] T (D columns gathered), anchors [L][2] -> topk [B][Q] int32, target [B*Q][ldt] T,
+ * sel_logits [B*Q][C], sel_anchors [B*Q][2].  1 <= levels <= 4, L <= 12288, 1 <= Q <= min(64, L), 1 <= C <= 256. */
+int spe_debug_rt_query_select(void* stream, int dtype, const float* logits, int C, const void* memory, int ldm,
+                              const float* anchors, int B, int Q, int D, int levels, const int* lvl_start, int* topk,
+                              void* target, int ldt, float* sel_logits, float* sel_anchors);
+/* rt_qpos_hidden: out [rows][H] T = relu(ref [rows][2] . w0 [H][2]^T + b0 [H]). */
+int spe_debug_rt_qpos_hidden(void* stream, int dtype, const float* ref, const float* w0, const float* b0, void* out,
+                             int rows, int H);
+/* rt_head_finish: the last layers of the score / box / sigma heads and the post-processor, per query row:
+ * logits = hs [rows][256] . cls_w [C][256]^T + cls_b, probs = softmax(logits) (cls_w null: no score head, both
+ * untouched; probs nullable); points = sigmoid(h2[:256] . box_w2 [2][256]^T + box_b2 + add), add = pt_add
+ * [rows][2] or inverse_sigmoid(pt_add) (pt_add_invsig 1); points_px = points * (x1 - x0, y1 - y0) + (x0, y0)
+ * with clip_bbox [rows / Q][4] (both nullable); log_sigmas = h2[256:512] . sig_w2 [256] + sig_b2 repeated to 2
+ * columns, sigmas = exp of it (sig_w2 null: no sigma head; both nullable).  h2 [rows][ld_h2] T.  C <= 16;
+ * points, pt_add, h2 required; a score head needs hs and logits. */
+int spe_debug_rt_head_finish(void* stream, int dtype, int rows, int Q, int C, const float* hs, const float* cls_w,
+                             const float* cls_b, const void* h2, int ld_h2, const float* box_w2, const float* box_b2,
+                             const float* sig_w2, const float* sig_b2, const float* pt_add, int pt_add_invsig,
+                             float* logits, float* probs, float* points, const float* clip_bbox, float* points_px,
+                             float* log_sigmas, float* sigmas);
+/* rt_msdeform: the multi-scale deformable attention core.  value T: level-major rows lvl_rows0[l] + b*H_l*W_l +
+ * y*W_l + x of ldv columns, 256 read (head h, channel c at h*32 + c); so_aw [rows][ld_so]: heads*levels*points
+ * (x, y) offsets, then heads*levels*points attention logits; ref [rows][2]; out [rows][ldo] T; image of a row =
+ * row / Q.  lvl_h, lvl_w, lvl_rows0 (host) have `levels` entries.  heads 8, levels <= 4, points <= 4. */
+int spe_debug_rt_msdeform(void* stream, int dtype, const void* value, int ldv, const float* so_aw, int ld_so,
+                          const float* ref, void* out, int ldo, int rows, int Q, int heads, int levels, int points,
+                          const int* lvl_h, const int* lvl_w, const int* lvl_rows0);
+
 #ifdef __cplusplus
 }
 #endif

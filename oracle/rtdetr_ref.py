@@ -253,6 +253,9 @@ def rtdetr_decoder(feats, w, cfg, trace=None):
         ff = F.linear(F.relu(F.linear(out, _t(w, f"{p}.linear1.weight"), _t(w, f"{p}.linear1.bias"))),
                       _t(w, f"{p}.linear2.weight"), _t(w, f"{p}.linear2.bias"))
         out = layer_norm(out + ff, w, f"{p}.norm3")
+        if trace is not None:           # what the layer's heads read: its output and the points it refines
+            trace.setdefault("dec_hs", []).append(out)
+            trace.setdefault("dec_ref", []).append(ref)
         new_ref = torch.sigmoid(mlp(out, w, f"decoder.dec_bbox_head.{i}", 3) + inverse_sigmoid(ref))
         logits.append(F.linear(out, _t(w, f"decoder.dec_score_head.{i}.weight"), _t(w, f"decoder.dec_score_head.{i}.bias")))
         pts.append(new_ref)

@@ -424,4 +424,56 @@ int spe_debug_pool2(void* stream, int dtype, const void* x, void* y, int B, int 
   return rc < 0 ? spe_fail(SPE_E_LAUNCH, "pool2 launch rejected its arguments") : rc;
 }
 
+// ---- RT-DETR kernels (rtdetr.hip).  The hooks fill the argument structs and return the launcher's own code
+// (0, a hipError_t, or -5 for arguments outside the kernel's contract, refused before any launch).
+int spe_debug_rt_resample2x(void* stream, int dtype, const void* in, int ldi, void* out, int ldo, int B, int H, int W,
+                            int C, int mode) {
+  return spe_launch_resample2x(in, ldi, out, ldo, B, H, W, C, mode, dtype, (hipStream_t)stream);
+}
+
+int spe_debug_rt_query_select(void* stream, int dtype, const float* logits, int C, const void* memory, int ldm,
+                              const float* anchors, int B, int Q, int D, int levels, const int* lvl_start, int* topk,
+                              void* target, int ldt, float* sel_logits, float* sel_anchors) {
+  RtSelectArgs a{};
+  a.logits = logits; a.C = C; a.memory = memory; a.ldm = ldm; a.anchors = anchors;
+  a.B = B; a.Q = Q; a.D = D; a.levels = levels;
+  for (int l = 0; l < 5 && l <= levels; ++l) a.lvl_start[l] = lvl_start[l];   // (levels > 4 is refused below)
+  a.topk = topk; a.target = target; a.ldt = ldt; a.sel_logits = sel_logits; a.sel_anchors = sel_anchors;
+  return spe_launch_query_select(a, dtype, (hipStream_t)stream);
+}
+
+int spe_debug_rt_qpos_hidden(void* stream, int dtype, const float* ref, const float* w0, const float* b0, void* out,
+                             int rows, int H) {
+  return spe_launch_qpos_hidden(ref, w0, b0, out, rows, H, dtype, (hipStream_t)stream);
+}
+
+int spe_debug_rt_head_finish(void* stream, int dtype, int rows, int Q, int C, const float* hs, const float* cls_w,
+                             const float* cls_b, const void* h2, int ld_h2, const float* box_w2, const float* box_b2,
+                             const float* sig_w2, const float* sig_b2, const float* pt_add, int pt_add_invsig,
+                             float* logits, float* probs, float* points, const float* clip_bbox, float* points_px,
+                             float* log_sigmas, float* sigmas) {
+  RtHeadArgs a{};
+  a.rows = rows; a.Q = Q; a.C = C;
+  a.hs = hs; a.cls_w = cls_w; a.cls_b = cls_b;
+  a.h2 = h2; a.ld_h2 = ld_h2;
+  a.box_w2 = box_w2; a.box_b2 = box_b2; a.sig_w2 = sig_w2; a.sig_b2 = sig_b2;
+  a.pt_add = pt_add; a.pt_add_invsig = pt_add_invsig;
+  a.logits = logits; a.probs = probs; a.points = points;
+  a.clip_bbox = clip_bbox; a.points_px = points_px;
+  a.log_sigmas = log_sigmas; a.sigmas = sigmas;
+  return spe_launch_head_finish(a, dtype, (hipStream_t)stream);
+}
+
+int spe_debug_rt_msdeform(void* stream, int dtype, const void* value, int ldv, const float* so_aw, int ld_so,
+                          const float* ref, void* out, int ldo, int rows, int Q, int heads, int levels, int points,
+                          const int* lvl_h, const int* lvl_w, const int* lvl_rows0) {
+  RtDeformArgs a{};
+  a.value = value; a.ldv = ldv; a.so_aw = so_aw; a.ld_so = ld_so; a.ref = ref; a.out = out; a.ldo = ldo;
+  a.rows = rows; a.Q = Q; a.heads = heads; a.levels = levels; a.points = points;
+  for (int l = 0; l < 4 && l < levels; ++l) {                                   // (levels > 4 is refused below)
+    a.lvl_h[l] = lvl_h[l]; a.lvl_w[l] = lvl_w[l]; a.lvl_rows0[l] = lvl_rows0[l];
+  }
+  return spe_launch_msdeform(a, dtype, (hipStream_t)stream);
+}
+
 }  // extern "C"

@@ -56,6 +56,8 @@ EXPORTS = ["spe_abi_version", "spe_last_error", "spe_model_create", "spe_model_d
            "spe_jpeg_workspace_bytes", "spe_jpeg_decode",
            "spe_debug_dwconv_tiles", "spe_debug_dwconv", "spe_debug_se_gate", "spe_debug_pwconv", "spe_debug_rtdetr_backbone",
            "spe_debug_ghost_cheap", "spe_debug_dfc_gate", "spe_debug_se_gate_bias", "spe_debug_pool2",
+           "spe_debug_rt_resample2x", "spe_debug_rt_query_select", "spe_debug_rt_qpos_hidden", "spe_debug_rt_head_finish",
+           "spe_debug_rt_msdeform",
            "spe_forward_attention", "spe_forward_attention_workspace_bytes", "spe_debug_attn_map"]
 
 
@@ -166,6 +168,12 @@ def load(path: str):
     L.spe_debug_dfc_gate.argtypes = [P, I, P, P, P, P, P, P, I, I, I, I]
     L.spe_debug_se_gate_bias.argtypes = [P, P, I, F, P, P, P, P, P, I, I, I]
     L.spe_debug_pool2.argtypes = [P, I, P, P, I, I, I, I]
+    IP = ctypes.POINTER(I)
+    L.spe_debug_rt_resample2x.argtypes = [P, I, P, I, P, I, I, I, I, I, I]
+    L.spe_debug_rt_query_select.argtypes = [P, I, P, I, P, I, P, I, I, I, I, IP, P, P, I, P, P]
+    L.spe_debug_rt_qpos_hidden.argtypes = [P, I, P, P, P, P, I, I]
+    L.spe_debug_rt_head_finish.argtypes = [P, I, I, I, I, P, P, P, P, I, P, P, P, P, P, I, P, P, P, P, P, P, P]
+    L.spe_debug_rt_msdeform.argtypes = [P, I, P, I, P, I, P, P, I, I, I, I, I, I, IP, IP, IP]
     L.spe_jpeg_workspace_bytes.argtypes = [I, I, I, I64]
     L.spe_jpeg_workspace_bytes.restype = I64
     L.spe_jpeg_decode.argtypes = [P, P, P, P, I, I, I, I64, P, P, P, I64]
