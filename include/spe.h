@@ -516,6 +516,15 @@ int spe_debug_upconv(void* stream, int dtype, const void* z, void* out, int ldo,
  * {(64, 64, r), (64, 128, r), (128, 64, null)}. */
 int spe_debug_btail(void* stream, const void* a, int lda, int k1, const void* r, const void* w3, int ld3,
                     const float* b3, void* y, const void* w1p, int ld1, const float* b1, void* z, int n2, int M);
+/* btail_wide (bf16, the layer-2 / layer-3 bottleneck tail fused with the next block's conv1,
+ * btail_wide.hip; additive, ABI 9): y [M][n1] (row stride ldy) = relu(a [M][k1] . w3^T + b3
+ * (+ r [M][n1], row stride ldr)), z [M][n2] (row stride ldz) = relu(y . w1p^T + b1) where w1p
+ * [n2][ld1] holds conv1's columns in spe_debug_btail_wide_perm(n1, .) order; (k1, n1, n2) in
+ * {(128, 512, 128), (128, 512, 256), (256, 1024, 256)}, r nullable.  Returns 0, or 1 = not served
+ * (another shape, or SPE_BTAIL_WIDE=0): nothing was launched. */
+int spe_debug_btail_wide(void* stream, const void* a, int lda, int k1, const void* r, int ldr, const void* w3, int ld3,
+                         const float* b3, void* y, int ldy, int n1, const void* w1p, int ld1, const float* b1, void* z,
+                         int ldz, int n2, int M);
 /* decsa (bf16 only, the decoder self-attention block, decsa.hip): in place over tgt [B*Q][ldt],
  * per image b: tgt = LayerNorm(tgt + MHA(q = k = tgt + query_pos, v = tgt) . wo^T + bo) with
  * 8 heads of 32 (d = 256), q|k = tgt . wqk^T + bqk + qpos ([Q][512] bf16, query_pos . wqk^T),
@@ -554,6 +563,8 @@ int spe_debug_decq(void* stream, const void* x, int ldx, int M, int N, const voi
                    const void* r, int ldr, int period, void* y, int ldy);
 /* the K-column order btail's second product expects: stored column k holds channel perm(k) */
 int spe_debug_btail_perm(int k);
+/* the same for btail_wide at block-output width n1 (512 / 1024); -1 outside [0, n1) */
+int spe_debug_btail_wide_perm(int n1, int k);
 /* stempool (bf16, stempool.hip): out [B][Po][Po] rows of stride ldo (Po = S/4 for S % 4 == 0) =
  * maxpool3x3/s2/p1(relu(conv7x7/s2/p3(image) + bias)) from x = the zero-bordered pair-packed
  * input [B][S+6][S+6][4] and w [64][ldw] with k = (kh*8 + kw)*4 + ci (registry.cpp's stem). */

@@ -194,6 +194,19 @@ int spe_debug_btail(void* stream, const void* a, int lda, int k1, const void* r,
   return rc != 0 ? spe_fail(SPE_E_LAUNCH, "btail launch rejected its arguments") : 0;
 }
 
+// 0 = launched, 1 = not served (nothing launched, y and z untouched), < 0 = bad argument
+int spe_debug_btail_wide(void* stream, const void* a, int lda, int k1, const void* r, int ldr, const void* w3, int ld3,
+                         const float* b3, void* y, int ldy, int n1, const void* w1p, int ld1, const float* b1, void* z,
+                         int ldz, int n2, int M) {
+  if (!a || !w3 || !b3 || !y || !w1p || !b1 || !z || M < 0) return spe_fail(SPE_E_ARG, "bad argument");
+  BtailArgs t{};
+  t.A = a; t.lda = lda; t.k1 = k1; t.R = r; t.ldr = ldr;
+  t.w3 = w3; t.ld3 = ld3; t.b3 = b3; t.y = y; t.ldy = ldy; t.n1 = n1;
+  t.w1 = w1p; t.ld1 = ld1; t.b1 = b1; t.z = z; t.ldz = ldz; t.n2 = n2; t.M = M;
+  const int rc = spe_launch_btail_wide(t, (hipStream_t)stream);
+  return rc != 0 && rc != 1 ? spe_fail(SPE_E_LAUNCH, "btail_wide launch failed") : rc;
+}
+
 // The decoder kernels read fragment-packed weights (spe_launch_wfrag_pack).  The hooks take
 // row-major rows (ld > 0) and pack them into scratch of their own, released after the launch has
 // completed, or already-packed weights (ld == 0, spe_debug_wfrag_pack: timing loops).
@@ -307,6 +320,7 @@ int spe_debug_decq(void* stream, const void* x, int ldx, int M, int N, const voi
 }
 
 int spe_debug_btail_perm(int k) { return spe_btail_perm(k); }
+int spe_debug_btail_wide_perm(int n1, int k) { return spe_btail_wide_perm(n1, k); }
 
 int spe_debug_stempool(void* stream, const void* x, const void* w, int ldw, const float* bias, void* out, int ldo,
                        int B, int S) {

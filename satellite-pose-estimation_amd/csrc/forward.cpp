@@ -93,8 +93,8 @@ struct BlockIn {
   bool t1_ready;             // this block's conv1 ran in the previous block's tail
 };
 
-// conv3 (+ residual R) + relu of a block: with the next block's conv1 as one launch (btail.hip) when the
-// next block carries permuted conv1 weights (layer-1 outputs, registry.cpp c1p) and the shapes are served
+// conv3 (+ residual R) + relu of a block: with the next block's conv1 as one launch (btail.hip, or
+// btail_wide.hip for layers 2 and 3) when the next block carries permuted conv1 weights (registry.cpp c1p) and the shapes are served
 // (*tailed), else the GEMM.  c3 over A is either Block::c3 over t2 or Block::c3ds over [t2 | x].
 int conv3_tail_or_gemm(Fwd& f, const Block* nb, const Conv& c3, const void* A, int lda, const float* a_amax,
                        const void* R, void* out, float* out_amax, int M, bool* tailed) {
@@ -108,7 +108,16 @@ int conv3_tail_or_gemm(Fwd& f, const Block* nb, const Conv& c3, const void* A, i
     t.M = M;
     const double flops = 2.0 * M * ((double)c3.N * c3.K + (double)nb->c1.N * c3.N);
     const double bytes = ((double)M * (c3.K + c3.N + nb->c1.N) + (R ? (double)M * c3.N : 0.0)) * m->esz;
-    rc = run_other(m, "conv.1x1", flops, bytes, f.s, [&] { return spe_launch_btail(t, f.s); });
+    if (c3.N == 256) {
+      rc = run_other(m, "conv.1x1", flops, bytes, f.s, [&] { return spe_launch_btail(t, f.s); });
+    } else if (spe_btail_wide_serves(t) && spe_btail_wide_tiles(t) >= spe_cu_count() / 2) {
+      // layers 2 and 3 (btail_wide.hip), every boundary measured faster than its two launches in the
+      // profiled B = 64 step (fused vs conv3 + conv1, ms): layer 2 inner 0.122 vs 0.170, layer 2 -> 3
+      // 0.162 vs 0.192, layer 3 block 0 -> 1 0.083 vs 0.111, layer 3 inner 0.082 vs 0.094
+      // (profiles/btail_wide_ab_ms_per_step.json).  Below half a tile per CU (not measured) the two
+      // GEMMs stay: they also split the columns over the chip.
+      rc = run_other(m, "conv.1x1", flops, bytes, f.s, [&] { return spe_launch_btail_wide(t, f.s); });
+    }
     if (rc != 0 && rc != 1) CK(rc);   // 1 = shapes not served: the GEMM below
   }
   if (rc == 1) {

@@ -504,17 +504,21 @@ int build_device(spe_model* m) {
       // conv1 of the blocks whose input is a layer-1 block output (blocks 1-3: layer 1 blocks 1
       // and 2, layer 2 block 0) as the second product of the previous block's fused tail:
       // columns permuted into spe_btail_perm order (btail.hip)
-      // (the layer-2 / layer-3 boundaries stay separate launches: their weights do not fit in
-      // LDS, and a split-N form streaming them through LDS measured slower)
+      // The blocks whose input is a layer-2 or layer-3 block output (K = 512 / 1024; the last block
+      // has no successor) get the same with spe_btail_wide_perm's order: btail_wide.hip streams the
+      // weights through LDS in chunks of the block output's channels.
       const int gi = li == 0 ? k : (li == 1 && k == 0 ? 3 : -1);
-      if (m->esz == 2 && spe_btail_enabled() && gi >= 1 && blk.c1.K == 256) {
+      const bool narrow = spe_btail_enabled() && gi >= 1 && blk.c1.K == 256;
+      const bool wide = spe_btail_wide_enabled() && li >= 1 && !m->blocks.empty() && m->blocks.back().c3.N == blk.c1.K &&
+                        (blk.c1.K == 512 || blk.c1.K == 1024);
+      if (m->esz == 2 && (narrow || wide)) {
         std::vector<float> w1, b1;
         fold_conv(m, p + ".conv1.weight", p + ".bn1", "", w1, b1);
         const int n = blk.c1.N, K = blk.c1.K;
         std::vector<float> rows((size_t)n * K, 0.f);
         if (m->dmem)
           for (int r = 0; r < n; ++r)
-            for (int c = 0; c < K; ++c) rows[(size_t)r * K + c] = w1[(size_t)r * K + spe_btail_perm(c)];
+            for (int c = 0; c < K; ++c) rows[(size_t)r * K + c] = w1[(size_t)r * K + (wide ? spe_btail_wide_perm(K, c) : spe_btail_perm(c))];
         Conv& f = blk.c1p;
         f.N = n; f.K = K; f.Kpad = pad64(K); f.Cin = K;
         f.w = upload_rows(m, rows, f.N, f.K, f.Kpad);

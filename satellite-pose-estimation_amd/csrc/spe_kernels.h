@@ -73,13 +73,14 @@ __device__ __forceinline__ void conv_k_decode(int k, int Cin, int KW, int taps, 
   kw = tap - kh * KW;
 }
 // Bottleneck tail + next conv1 (btail.hip): y = relu(A . W3^T + b3 (+ R)), z = relu(y . W1p^T + b1)
-// with W1p's columns in spe_btail_perm order.  bf16; N1 = n1 = 256 (layer 1), or the split-N
-// form for 512 / 1024 (layers 2 / 3, residual row stride ldr = n1).
+// with W1p's columns in spe_btail_perm order.  bf16; N1 = n1 = 256 (layer 1, btail.hip: both weight
+// matrices in LDS) or 512 / 1024 (layers 2 / 3, btail_wide.hip: weights streamed in chunks, W1p's
+// columns in spe_btail_wide_perm order).
 struct BtailArgs {
   const void* A; int lda; int k1;        // conv3 input [M][k1] (row stride lda)
   const void* R; int ldr;                // residual [M][n1] or null
-  const void* w3; int ld3; const float* b3;   // [256][ld3]
-  void* y; int ldy; int n1;              // block output [M][256]
+  const void* w3; int ld3; const float* b3;   // [n1][ld3]
+  void* y; int ldy; int n1;              // block output [M][n1]
   const void* w1; int ld1; const float* b1;   // next conv1, permuted columns [n2][ld1]
   void* z; int ldz; int n2;              // next conv1 output [M][n2]
   int M;
@@ -87,6 +88,13 @@ struct BtailArgs {
 int spe_launch_btail(const BtailArgs& a, hipStream_t s);   // 1 = not applicable
 int spe_btail_perm(int k);
 bool spe_btail_enabled();
+// the wide form: (k1, n1, n2) in {(128, 512, 128), (128, 512, 256), (256, 1024, 256)}; 1 = not served
+// (another shape, or SPE_BTAIL_WIDE=0)
+int spe_launch_btail_wide(const BtailArgs& a, hipStream_t s);
+int spe_btail_wide_perm(int n1, int k);
+bool spe_btail_wide_enabled();
+bool spe_btail_wide_serves(const BtailArgs& a);   // what spe_launch_btail_wide launches
+int spe_btail_wide_tiles(const BtailArgs& a);     // its grid (row tiles) for a served problem
 int spe_launch_gemm2(const GemmArgs& g, int mode, hipStream_t s);   // 1 = not applicable
 int spe_launch_sgemm(const GemmArgs& g, int mode, hipStream_t s);   // 1 = not applicable
 int spe_launch_lnproj(const GemmArgs& g, hipStream_t s);             // 1 = not applicable (lnproj.hip)
