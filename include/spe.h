@@ -191,6 +191,14 @@ const char* spe_last_error(void);
  * (REV/main.py:264-274): parameters are handed over by their reference state_dict key
  * (412 keys, e.g. "backbone.0.body.layer1.0.conv1.weight"), fp32, host memory. */
 int spe_model_create(const spe_model_config* cfg, spe_model** out);
+/* The same with the backbone named (additive, ABI 9; spe_model_create == SPE_BACKBONE_RESNET50_S8):
+ *   SPE_BACKBONE_RESNET50_S8   Backbone8s, the stride-8 fusion neck (REV/models/backbone.py:105-149); 412 keys
+ *   SPE_BACKBONE_RESNET50_S16  Backbone, ResNet-50 cut after layer3 (REV/models/backbone.py:57-102): no neck
+ *                              parameters (408 keys), input_proj.weight [256][1024][1][1] straight on the
+ *                              stride-16 map, T = (input_size / 16)^2 tokens
+ * Everything after src (stages, u8 crops, attention maps, outputs) is the same for both. */
+enum { SPE_BACKBONE_RESNET50_S8 = 0, SPE_BACKBONE_RESNET50_S16 = 1 };
+int spe_model_create_backbone(const spe_model_config* cfg, int backbone, spe_model** out);
 void spe_model_destroy(spe_model* m);
 int spe_model_set_param(spe_model* m, const char* key, const float* host_data, int64_t numel);
 int spe_model_num_params(const spe_model* m);                 /* number of required keys */
@@ -525,6 +533,13 @@ int spe_debug_btail(void* stream, const void* a, int lda, int k1, const void* r,
 int spe_debug_btail_wide(void* stream, const void* a, int lda, int k1, const void* r, int ldr, const void* w3, int ld3,
                          const float* b3, void* y, int ldy, int n1, const void* w1p, int ld1, const float* b1, void* z,
                          int ldz, int n2, int M);
+/* btail_wide's final form (additive, ABI 9): the same operands; relu_z = 0 leaves z = y . w1p^T + b1 without
+ * the ReLU (the stride-16 DETR's input_proj over the last bottleneck), and y may be null: then y is not
+ * stored at all (z is what it would be with y stored, bit for bit).  y null or relu_z = 0 are served for
+ * (k1, n1, n2) = (256, 1024, 256) only.  Returns as spe_debug_btail_wide. */
+int spe_debug_btail_wide_proj(void* stream, const void* a, int lda, int k1, const void* r, int ldr, const void* w3,
+                              int ld3, const float* b3, void* y, int ldy, int n1, const void* w1p, int ld1,
+                              const float* b1, void* z, int ldz, int n2, int M, int relu_z);
 /* decsa (bf16 only, the decoder self-attention block, decsa.hip): in place over tgt [B*Q][ldt],
  * per image b: tgt = LayerNorm(tgt + MHA(q = k = tgt + query_pos, v = tgt) . wo^T + bo) with
  * 8 heads of 32 (d = 256), q|k = tgt . wqk^T + bqk + qpos ([Q][512] bf16, query_pos . wqk^T),

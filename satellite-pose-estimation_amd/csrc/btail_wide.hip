@@ -95,8 +95,13 @@ struct WideDma {
   }
 };
 
-template <int K1, int N2, int MB, bool HAS_R>
+// STORE_Y / RELU_Z are compile-time (the defaults are the layer-2 / layer-3 tails; the final tail of the
+// stride-16 model below clears them): without STORE_Y the kernel holds no y store at all and never reads
+// a.y, so in every instantiation every path still issues the same memory instructions and the counted
+// waits count exactly what that instantiation issues.
+template <int K1, int N2, int MB, bool HAS_R, bool STORE_Y = true, bool RELU_Z = true>
 __global__ __launch_bounds__(NT, (N2 == 128 && MB <= 2) ? 2 : 1) void btail_wide_kernel(BtailArgs a) {
+  constexpr int YST = STORE_Y ? MB : 0;      // y stores a chunk step issues
   constexpr int KB1 = K1 * 2, KF1 = K1 / 32, NB2 = N2 / 16;
   constexpr int W3_BYTES = HC * KB1, W1_BYTES = N2 * HC * 2, R_BYTES = HAS_R ? 4 * MB * 1024 : 0;
   constexpr int STAGE = W3_BYTES + W1_BYTES + R_BYTES;
@@ -130,13 +135,14 @@ __global__ __launch_bounds__(NT, (N2 == 128 && MB <= 2) ? 2 : 1) void btail_wide
 #pragma unroll
     for (int mb = 0; mb < MB; ++mb) acc[nb][mb] = f32x4{0, 0, 0, 0};
 
-  const __amdgpu_buffer_rsrc_t ry =
-      __builtin_amdgcn_make_buffer_rsrc(a.y, (short)0, ((a.M - 1) * a.ldy + a.n1) * 2, 0x00020000);
+  // (without STORE_Y: an empty range that nothing stores to)
+  const __amdgpu_buffer_rsrc_t ry = __builtin_amdgcn_make_buffer_rsrc(
+      STORE_Y ? a.y : nullptr, (short)0, STORE_Y ? ((a.M - 1) * a.ldy + a.n1) * 2 : 0, 0x00020000);
   int voy[MB];
 #pragma unroll
   for (int mb = 0; mb < MB; ++mb) {
     const int m = m0 + 16 * mb + c16;
-    voy[mb] = m < a.M ? (m * a.ldy + 8 * g) * 2 : BAD;
+    voy[mb] = STORE_Y && m < a.M ? (m * a.ldy + 8 * g) * 2 : BAD;
   }
   WideDma<K1, N2, MB, HAS_R> dma;
   dma.init(a, m0, wid, lane);
@@ -154,10 +160,11 @@ __global__ __launch_bounds__(NT, (N2 == 128 && MB <= 2) ? 2 : 1) void btail_wide
   int slot = 0;
   for (int ch = 0; ch < nch; ++ch) {
     // Issue order: DMA(ch) [step ch-2], y stores(ch-2), DMA(ch+1), y stores(ch-1), this wait.  Chunk ch
-    // and the stores of step ch-2 retire; chunk ch+1 and the MB stores of step ch-1 may stay in flight.
+    // and the stores of step ch-2 retire; chunk ch+1 and the MB stores of step ch-1 may stay in flight
+    // (without STORE_Y there are no stores: YST = 0 and only chunk ch+1 stays in flight).
     if (ch == 0) wait_vmcnt<LOADS>();
-    else if (ch + 1 < nch) wait_vmcnt<LOADS + MB>();
-    else wait_vmcnt<MB>();
+    else if (ch + 1 < nch) wait_vmcnt<LOADS + YST>();
+    else wait_vmcnt<YST>();
     // raw barrier (__syncthreads' fence would drain the chunk in flight): every wave's part of chunk
     // ch is visible, and the slot of chunk ch+2 -- read in step ch-1 -- is free
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
@@ -219,7 +226,7 @@ __global__ __launch_bounds__(NT, (N2 == 128 && MB <= 2) ? 2 : 1) void btail_wide
 #pragma unroll
       for (int e = 0; e < 8; ++e) v[e] = fmaxf(v[e], 0.f);
       const u32x4 yw = pack16<bf16>(v);
-      __builtin_amdgcn_raw_buffer_store_b128(yw, ry, voy[mb], ch * HC * 2, 0);
+      if constexpr (STORE_Y) __builtin_amdgcn_raw_buffer_store_b128(yw, ry, voy[mb], ch * HC * 2, 0);
       yb[mb] = __builtin_bit_cast(bf16x8, yw);
     }
     // ---- z^T[n][m] += W1[n][chunk 8g .. 8g+7] . y^T[8g .. 8g+7][m]
@@ -232,7 +239,7 @@ __global__ __launch_bounds__(NT, (N2 == 128 && MB <= 2) ? 2 : 1) void btail_wide
     }
   }
 
-  // ---- z = relu(acc + b1) (b1 from LDS: loads from memory would be ordered against the z stores
+  // ---- z = relu(acc + b1), or acc + b1 without RELU_Z (b1 from LDS: loads from memory would be ordered against the z stores
   // one by one): the lane holds, for row m0 + 16mb + c16, columns 16nb + 4g + r
 #pragma unroll
   for (int mb = 0; mb < MB; ++mb) {
@@ -245,10 +252,27 @@ __global__ __launch_bounds__(NT, (N2 == 128 && MB <= 2) ? 2 : 1) void btail_wide
       const f32x4 bv = *reinterpret_cast<const f32x4*>(sb1 + n);
       float v[4];
 #pragma unroll
-      for (int r = 0; r < 4; ++r) v[r] = fmaxf(acc[nb][mb][r] + bv[r], 0.f);
+      for (int r = 0; r < 4; ++r) v[r] = RELU_Z ? fmaxf(acc[nb][mb][r] + bv[r], 0.f) : acc[nb][mb][r] + bv[r];
       st8(zr + n, u32x2{pack_bf16x2(v[0], v[1]), pack_bf16x2(v[2], v[3])});
     }
   }
+}
+
+// The final tail of the stride-16 model (K1 = 256, N1 = 1024, N2 = 256, 192-row tiles): the last bottleneck's
+// conv3 + identity + relu with input_proj as the second product -- z without the ReLU, and y, which nobody
+// else reads, not stored.
+// (explicit instantiations: left implicit, the host compiler emits the launch stubs of only some of them)
+#define SPE_BTAIL_WIDE_INST(R, Y, Z) template __global__ void btail_wide_kernel<256, 256, 3, R, Y, Z>(BtailArgs);
+SPE_BTAIL_WIDE_INST(false, false, false) SPE_BTAIL_WIDE_INST(false, false, true) SPE_BTAIL_WIDE_INST(false, true, false)
+SPE_BTAIL_WIDE_INST(false, true, true) SPE_BTAIL_WIDE_INST(true, false, false) SPE_BTAIL_WIDE_INST(true, false, true)
+SPE_BTAIL_WIDE_INST(true, true, false) SPE_BTAIL_WIDE_INST(true, true, true)
+#undef SPE_BTAIL_WIDE_INST
+
+template <bool HAS_R, bool STORE_Y, bool RELU_Z>
+int launch_proj(const BtailArgs& a, hipStream_t s) {
+  const int tiles = (a.M + 191) / 192;
+  hipLaunchKernelGGL((btail_wide_kernel<256, 256, 3, HAS_R, STORE_Y, RELU_Z>), dim3(tiles), dim3(NT), 0, s, a);
+  return (int)hipGetLastError();
 }
 
 template <int K1, int N2, int MB>
@@ -278,8 +302,46 @@ int tile_rows(const BtailArgs& a) { return a.n1 == 1024 ? 192 : 128; }
 
 int spe_btail_wide_tiles(const BtailArgs& a) { return (a.M + tile_rows(a) - 1) / tile_rows(a); }
 
+// y may be null for the final form (spe_launch_btail_wide_proj), which stores none
+static bool strides_served(const BtailArgs& a) {
+  const int ldy = a.y ? a.ldy : a.n1;
+  if (a.lda % 8 || ldy % 8 || a.ldz % 4 || (a.R && a.ldr % 8) || a.lda < a.k1 || ldy < a.n1 || a.ldz < a.n2 ||
+      (a.R && a.ldr < a.n1) || a.ld3 < a.k1 || a.ld1 < a.n1 || a.ld3 % 8 || a.ld1 % 8)
+    return false;
+  // 32-bit buffer offsets
+  return (double)a.M * std::max(a.y ? a.ldy : 0, a.R ? a.ldr : 0) * 2 < 2147483648.0;
+}
+
+// Off by default: in the measured B = 64, 448^2 step the fused launch was not faster than its two GEMMs
+// (backbone stage 3.605 against 3.600 ms, profiles/backbone_s16_vs_s8.json)
+bool spe_btail_wide_proj_enabled() {
+  static const int on = spe_env_int("SPE_BTAIL_PROJ", 0);
+  return on != 0;
+}
+
+bool spe_btail_wide_proj_serves(const BtailArgs& a) {
+  if (!spe_btail_wide_enabled() || !a.A || !a.w3 || !a.b3 || !a.w1 || !a.b1 || !a.z) return false;
+  return strides_served(a) && a.k1 == 256 && a.n1 == 1024 && a.n2 == 256;
+}
+
+// 1 = not a problem for this kernel
+int spe_launch_btail_wide_proj(const BtailArgs& a, bool relu_z, hipStream_t s) {
+  if (a.M <= 0) return 0;
+  if (!spe_btail_wide_proj_serves(a)) return 1;
+  if (a.y && relu_z) return spe_launch_btail_wide(a, s);
+  const int sel = (a.R ? 4 : 0) | (a.y ? 2 : 0) | (relu_z ? 1 : 0);
+  switch (sel) {
+    case 0: return launch_proj<false, false, false>(a, s);
+    case 1: return launch_proj<false, false, true>(a, s);
+    case 2: return launch_proj<false, true, false>(a, s);
+    case 4: return launch_proj<true, false, false>(a, s);
+    case 5: return launch_proj<true, false, true>(a, s);
+    default: return launch_proj<true, true, false>(a, s);
+  }
+}
+
 bool spe_btail_wide_serves(const BtailArgs& a) {
-  if (!spe_btail_wide_enabled()) return false;
+  if (!spe_btail_wide_enabled() || !a.y) return false;
   if (a.lda % 8 || a.ldy % 8 || a.ldz % 4 || (a.R && a.ldr % 8) || a.lda < a.k1 || a.ldy < a.n1 || a.ldz < a.n2 ||
       (a.R && a.ldr < a.n1) || a.ld3 < a.k1 || a.ld1 < a.n1 || a.ld3 % 8 || a.ld1 % 8)
     return false;

@@ -207,6 +207,18 @@ int spe_debug_btail_wide(void* stream, const void* a, int lda, int k1, const voi
   return rc != 0 && rc != 1 ? spe_fail(SPE_E_LAUNCH, "btail_wide launch failed") : rc;
 }
 
+int spe_debug_btail_wide_proj(void* stream, const void* a, int lda, int k1, const void* r, int ldr, const void* w3,
+                              int ld3, const float* b3, void* y, int ldy, int n1, const void* w1p, int ld1,
+                              const float* b1, void* z, int ldz, int n2, int M, int relu_z) {
+  if (!a || !w3 || !b3 || !w1p || !b1 || !z || M < 0) return spe_fail(SPE_E_ARG, "bad argument");
+  BtailArgs t{};
+  t.A = a; t.lda = lda; t.k1 = k1; t.R = r; t.ldr = ldr;
+  t.w3 = w3; t.ld3 = ld3; t.b3 = b3; t.y = y; t.ldy = ldy; t.n1 = n1;
+  t.w1 = w1p; t.ld1 = ld1; t.b1 = b1; t.z = z; t.ldz = ldz; t.n2 = n2; t.M = M;
+  const int rc = spe_launch_btail_wide_proj(t, relu_z != 0, (hipStream_t)stream);
+  return rc != 0 && rc != 1 ? spe_fail(SPE_E_LAUNCH, "btail_wide_proj launch failed") : rc;
+}
+
 // The decoder kernels read fragment-packed weights (spe_launch_wfrag_pack).  The hooks take
 // row-major rows (ld > 0) and pack them into scratch of their own, released after the launch has
 // completed, or already-packed weights (ld == 0, spe_debug_wfrag_pack: timing loops).

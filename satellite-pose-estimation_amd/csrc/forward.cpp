@@ -91,6 +91,7 @@ struct BlockIn {
   int ld, H;
   const float* amax;
   bool t1_ready;             // this block's conv1 ran in the previous block's tail
+  bool src_ready;            // stride-16 model: input_proj ran in the last block's tail (src is written, x is not)
 };
 
 // conv3 (+ residual R) + relu of a block: with the next block's conv1 as one launch (btail.hip, or
@@ -131,6 +132,31 @@ int conv3_tail_or_gemm(Fwd& f, const Block* nb, const Conv& c3, const void* A, i
   return 0;
 }
 
+// The stride-16 model's last bottleneck (bf16): conv3 + identity + relu with input_proj as the tail's second
+// product, straight into src; the 1024-channel block output, which nobody else reads, is never stored
+// (btail_wide.hip's final form).  Taken under the rule of layers 2 and 3 above: served, and at least half a
+// tile per CU; else *done stays false and the caller runs conv3 and input_proj as two GEMMs.
+// Behind SPE_BTAIL_PROJ=1 only: measured at B = 64, 448^2 (262 tiles) the fused launch was not faster than the
+// two GEMMs (backbone stage 3.605 against 3.600 ms, profiles/backbone_s16_vs_s8.json), so by the rule above
+// the two GEMMs are the default.
+int final_tail(Fwd& f, const Conv& c3, const void* A, int lda, const void* R, int M, bool* done) {
+  spe_model* m = f.m;
+  *done = false;
+  if (!m->ipp.w || !spe_btail_wide_proj_enabled()) return 0;
+  BtailArgs t{};
+  t.A = A; t.lda = lda; t.k1 = c3.K; t.R = R; t.ldr = c3.N;
+  t.w3 = c3.w; t.ld3 = c3.Kpad; t.b3 = c3.bias; t.y = nullptr; t.ldy = c3.N; t.n1 = c3.N;
+  t.w1 = m->ipp.w; t.ld1 = m->ipp.Kpad; t.b1 = m->ipp.bias; t.z = f.P(f.w.src); t.ldz = f.d; t.n2 = m->ipp.N;
+  t.M = M;
+  if (t.n2 != f.d || !spe_btail_wide_proj_serves(t) || spe_btail_wide_tiles(t) < spe_cu_count() / 2) return 0;
+  const double flops = 2.0 * M * ((double)c3.N * c3.K + (double)t.n2 * c3.N);
+  const double bytes = ((double)M * (c3.K + t.n2) + (R ? (double)M * c3.N : 0.0)) * m->esz;
+  const int rc = run_other(m, "conv.1x1", flops, bytes, f.s, [&] { return spe_launch_btail_wide_proj(t, false, f.s); });
+  if (rc != 0 && rc != 1) CK(rc);
+  *done = rc == 0;
+  return 0;
+}
+
 // bottleneck block bi over `in`, which becomes the block's output; activation-scale slots 2 + 3 bi ...
 int bottleneck(Fwd& f, size_t bi, BlockIn& in) {
   spe_model* m = f.m;
@@ -143,8 +169,10 @@ int bottleneck(Fwd& f, size_t bi, BlockIn& in) {
   // the max-pool wrote the right half (backbone_stage)
   const bool fused = bi == 0 && blk.c3ds.w != nullptr;
   const Block* nb = bi + 1 < m->blocks.size() && m->blocks[bi + 1].c1p.w ? &m->blocks[bi + 1] : nullptr;
-  // layer1: blocks 0-2, layer2: 3-6 (its output xs8 is kept for the neck), layer3: 7-12
-  const size_t outbuf = (bi == 6) ? w.xs8 : (in.x == w.bufA ? w.bufB : w.bufA);
+  // layer1: blocks 0-2, layer2: 3-6 (its output xs8 is kept for the neck; the stride-16 model has none),
+  // layer3: 7-12
+  const bool s16bb = m->backbone == SPE_BACKBONE_RESNET50_S16;
+  const size_t outbuf = (bi == 6 && !s16bb) ? w.xs8 : (in.x == w.bufA ? w.bufB : w.bufA);
   const int Ho = (H + 2 - 3) / blk.stride + 1;
   float* const t1_amax = f.slot(2 + 3 * (int)bi);
   float* const t2_amax = f.slot(2 + 3 * (int)bi + 1);
@@ -178,9 +206,13 @@ int bottleneck(Fwd& f, size_t bi, BlockIn& in) {
       }
       res = w.ds;
     }
-    // conv3 1x1 + bn3 + residual + relu (+ the next block's conv1, btail.hip)
-    TRY(conv3_tail_or_gemm(f, nb, blk.c3, f.P(w.t2), blk.c2.N, t2_amax, f.P(res), f.P(outbuf), out_amax, B * Ho * Ho,
-                           &in.t1_ready));
+    // conv3 1x1 + bn3 + residual + relu (+ the next block's conv1, btail.hip; + input_proj after the
+    // stride-16 model's last block)
+    if (s16bb && bi + 1 == m->blocks.size())
+      TRY(final_tail(f, blk.c3, f.P(w.t2), blk.c2.N, f.P(res), B * Ho * Ho, &in.src_ready));
+    if (!in.src_ready)
+      TRY(conv3_tail_or_gemm(f, nb, blk.c3, f.P(w.t2), blk.c2.N, t2_amax, f.P(res), f.P(outbuf), out_amax, B * Ho * Ho,
+                             &in.t1_ready));
     in.amax = out_amax;
   }
   in.ld = blk.c3.N;
@@ -288,13 +320,22 @@ int backbone_stage(Fwd& f, const ImageSrc& images) {
       return spe_launch_maxpool3s2(f.P(w.stem), f.P(pool_at), B, H, H, 64, Hp, Hp, dt, s, uld);
     }));
   }
-  BlockIn x{pool_at, uld, Hp, stem_amax, false};         // (the max-pool's maximum is the stem's)
+  BlockIn x{pool_at, uld, Hp, stem_amax, false, false};  // (the max-pool's maximum is the stem's)
   const float* xs8_amax = nullptr;
   for (size_t bi = 0; bi < m->blocks.size(); ++bi) {
     TRY(bottleneck(f, bi, x));
     if (bi == 6) xs8_amax = x.amax;
   }
-  return neck(f, x.x, xs8_amax, x.amax);                 // x: xs16 [B, S/16, S/16, 1024]
+  if (m->backbone != SPE_BACKBONE_RESNET50_S16)
+    return neck(f, x.x, xs8_amax, x.amax);               // x: xs16 [B, S/16, S/16, 1024]
+  // the plain ResNet-50 (REV/models/backbone.py:57-102): input_proj 1x1 1024->256 + bias straight over xs16
+  // -> src [B*T, 256] and its scale slot, unless the last block's tail already wrote src
+  if (!x.src_ready) {
+    GemmArgs g = linear_args(m->inproj, f.P(x.x), x.ld, f.Mt, f.P(w.src), f.d);
+    g.amax_a = x.amax; g.amax_c = f.slot(SPE_AMAX_BB - 1);
+    CK(run_gemm(m, "gemm.input_proj", g, GEMM_LINEAR, s));
+  }
+  return 0;
 }
 
 // ---------------- encoder (REV/models/transformer.py:154-167)
@@ -780,7 +821,7 @@ int forward_stages(spe_model* m, void* stream, const ImageSrc& images, int B, vo
   const Ws w = spe_plan(m, B);
   if ((int64_t)w.total > ws_bytes) return fail(SPE_E_WORKSPACE, "workspace too small");
   const auto& c = m->cfg;
-  const int F = c.input_size / 8;
+  const int F = c.input_size / spe_feat_stride(m);
   float* const amx = m->h3 ? (float*)((char*)workspace + w.amax) : nullptr;
   LedgerScope ledger(amx);
   Fwd f{m, w, (char*)workspace, (hipStream_t)stream, B, c.input_size, F, F * F, c.hidden_dim, c.dim_feedforward,

@@ -182,6 +182,7 @@ struct RtModel {
 
 struct spe_model {
   int family = 0;            // 0: DETR (REV), 1: RT-DETR (UNC)
+  int backbone = 0;          // DETR: SPE_BACKBONE_RESNET50_S8 (Backbone8s) or SPE_BACKBONE_RESNET50_S16 (Backbone)
   int x3 = 0;                // fp32 model computed with split-bf16 MFMA (SPE_DTYPE_F32X3_, _F32X6_)
   int x6 = 0;                // ... with the GEMMs / convs on the three-way split path (SPE_DTYPE_F32X6_)
   int h3 = 0;                // ... and the backbone / encoder GEMMs on the scaled fp16 split path (SPE_DTYPE_F32H3_)
@@ -204,6 +205,8 @@ struct spe_model {
   Conv stem, s8, s16, outc, inproj, crossK, crossV;
   Conv s16taps;            // bf16 models: s16_latern as 9 per-tap [256][1024] blocks (spe_use_upconv)
   Conv neckip;             // input_proj . output_conv as one 3x3 conv 512 -> hidden (spe_use_neckfold)
+  Conv ipp;                // bf16 stride-16 models: input_proj with its K columns in spe_btail_wide_perm order, the
+                           // second product of the last bottleneck's tail (btail_wide.hip's final form), or empty
   std::vector<Block> blocks;
   std::vector<Enc> enc;
   std::vector<Dec> dec;
@@ -216,6 +219,8 @@ struct spe_model {
 };
 
 int spe_fail(int code, const std::string& msg);
+// stride of the map input_proj reads: 8 behind Backbone8s' neck, 16 for the plain ResNet-50 cut after layer3
+inline int spe_feat_stride(const spe_model* m) { return m->backbone == SPE_BACKBONE_RESNET50_S16 ? 16 : 8; }
 // RT-DETR runtime hooks (rtdetr_model.cpp)
 int spe_rtdetr_build_device(spe_model* m);
 int64_t spe_rtdetr_workspace(const spe_model* m, int B);

@@ -33,7 +33,8 @@ int spe_fail(int code, const std::string& msg) {
 
 namespace {
 
-std::vector<std::pair<std::string, std::vector<int64_t>>> build_spec(const spe_model_config& c) {
+std::vector<std::pair<std::string, std::vector<int64_t>>> build_spec(const spe_model_config& c, int backbone) {
+  const bool s16 = backbone == SPE_BACKBONE_RESNET50_S16;   // no neck; input_proj over layer3's 1024 channels
   std::vector<std::pair<std::string, std::vector<int64_t>>> s;
   const int64_t d = c.hidden_dim, ff = c.dim_feedforward;
   auto add = [&](const std::string& k, std::vector<int64_t> sh) { s.emplace_back(k, std::move(sh)); };
@@ -64,7 +65,7 @@ std::vector<std::pair<std::string, std::vector<int64_t>>> build_spec(const spe_m
   add("point_embed.layers.1.weight", {d, d}); add("point_embed.layers.1.bias", {d});
   add("point_embed.layers.2.weight", {2, d}); add("point_embed.layers.2.bias", {2});
   add("query_embed.weight", {c.num_queries, d});
-  add("input_proj.weight", {d, 512, 1, 1}); add("input_proj.bias", {d});
+  add("input_proj.weight", {d, s16 ? 1024 : 512, 1, 1}); add("input_proj.bias", {d});
   const std::string b = "backbone.0.body";
   add(b + ".conv1.weight", {64, 3, 7, 7});
   bn(b + ".bn1", 64);
@@ -80,10 +81,12 @@ std::vector<std::pair<std::string, std::vector<int64_t>>> build_spec(const spe_m
       if (k == 0) { add(p + ".downsample.0.weight", {4 * w, cin, 1, 1}); bn(p + ".downsample.1", 4 * w); }
       cin = 4 * w;
     }
-  add("backbone.0.s8_latern.weight", {256, 512, 1, 1});
-  add("backbone.0.s16_latern.weight", {256, 1024, 3, 3});
-  add("backbone.0.output_conv.weight", {512, 512, 3, 3});
-  add("backbone.0.output_conv.bias", {512});
+  if (!s16) {
+    add("backbone.0.s8_latern.weight", {256, 512, 1, 1});
+    add("backbone.0.s16_latern.weight", {256, 1024, 3, 3});
+    add("backbone.0.output_conv.weight", {512, 512, 3, 3});
+    add("backbone.0.output_conv.bias", {512});
+  }
   if (c.sigma_head) {
     add("sigma_embed.layers.0.weight", {d, d}); add("sigma_embed.layers.0.bias", {d});
     add("sigma_embed.layers.1.weight", {d, d}); add("sigma_embed.layers.1.bias", {d});
@@ -526,55 +529,73 @@ int build_device(spe_model* m) {
       }
       m->blocks.push_back(blk);
     }
-  m->s8 = make_conv(m, "backbone.0.s8_latern.weight", "", "", 0, 1, 0);
-  m->s16 = make_conv(m, "backbone.0.s16_latern.weight", "", "", 0, 1, 1);
-  m->s16taps = Conv{};
-  if (spe_use_upconv(m)) {
-    // per-tap rows for the low-resolution form of s16_latern(up16sto8s(x)) (elementwise.hip
-    // upconv_combine): row t*256 + co = weight[co][:][kh][kw], t = kh*3 + kw
-    const auto sh = param_shape(m, "backbone.0.s16_latern.weight");
-    const int co_n = (int)sh[0], ci_n = (int)sh[1];
-    std::vector<float> rows;
-    if (m->dmem) {
-      const auto& src = m->host["backbone.0.s16_latern.weight"];
-      rows.assign((size_t)9 * co_n * ci_n, 0.f);
-      for (int t = 0; t < 9; ++t)
-        for (int co = 0; co < co_n; ++co)
-          for (int ci = 0; ci < ci_n; ++ci)
-            rows[((size_t)t * co_n + co) * ci_n + ci] = src[((size_t)co * ci_n + ci) * 9 + t];
+  m->s8 = m->s16 = m->s16taps = m->outc = m->neckip = m->ipp = Conv{};
+  if (m->backbone == SPE_BACKBONE_RESNET50_S16) {
+    m->inproj = make_conv(m, "input_proj.weight", "", "input_proj.bias", 0, 1, 0);   // K = 1024, over block 12's output
+    // Nobody but input_proj reads the last bottleneck's output, so bf16 models take input_proj as the
+    // second product of that block's tail (btail_wide.hip's final form): its weights like a c1p
+    if (m->esz == 2 && spe_btail_wide_enabled() && m->inproj.K == 1024 && m->blocks.back().c3.N == 1024) {
+      std::vector<float> w, bias;
+      fold_conv(m, "input_proj.weight", "", "input_proj.bias", w, bias);
+      const int n = m->inproj.N, K = m->inproj.K;
+      std::vector<float> rows((size_t)n * K, 0.f);
+      if (m->dmem)
+        for (int r = 0; r < n; ++r)
+          for (int c = 0; c < K; ++c) rows[(size_t)r * K + c] = w[(size_t)r * K + spe_btail_wide_perm(K, c)];
+      Conv& f = m->ipp;
+      f.N = n; f.K = K; f.Kpad = pad64(K); f.Cin = K;
+      f.w = upload_rows(m, rows, f.N, f.K, f.Kpad);
+      f.bias = upload_f32(m, bias.data(), bias.size());
     }
-    Conv& c = m->s16taps;
-    c.N = 9 * co_n; c.K = ci_n; c.Kpad = pad64(ci_n); c.Cin = ci_n;
-    c.w = upload_rows(m, rows, c.N, c.K, c.Kpad);
-  }
-  m->outc = make_conv(m, "backbone.0.output_conv.weight", "", "backbone.0.output_conv.bias", 0, 1, 1);
-  m->inproj = make_conv(m, "input_proj.weight", "", "input_proj.bias", 0, 1, 0);
-  m->neckip = Conv{};
-  if (spe_use_neckfold(m)) {
-    const auto so = param_shape(m, "backbone.0.output_conv.weight");   // [512][512][3][3]
-    const auto sp = param_shape(m, "input_proj.weight");                // [hidden][512][1][1]
-    const int cm = (int)so[0], ci_n = (int)so[1], co_n = (int)sp[0], taps = (int)(so[2] * so[3]);
-    std::vector<float> w((size_t)co_n * ci_n * taps, 0.f), bias(co_n, 0.f);
-    if (m->dmem) {
-      const auto& wo = m->host["backbone.0.output_conv.weight"];
-      const auto& bo = m->host["backbone.0.output_conv.bias"];
-      const auto& wp = m->host["input_proj.weight"];
-      const auto& bp = m->host["input_proj.bias"];
-      std::vector<double> acc((size_t)ci_n * taps);
-      for (int co = 0; co < co_n; ++co) {
-        std::fill(acc.begin(), acc.end(), 0.0);
-        double b = bp[co];
-        for (int j = 0; j < cm; ++j) {
-          const double a = wp[(size_t)co * cm + j];
-          const float* src = &wo[(size_t)j * ci_n * taps];
-          for (size_t k = 0; k < acc.size(); ++k) acc[k] += a * src[k];
-          b += a * bo[j];
-        }
-        for (size_t k = 0; k < acc.size(); ++k) w[(size_t)co * ci_n * taps + k] = (float)acc[k];
-        bias[co] = (float)b;
+  } else {
+    m->s8 = make_conv(m, "backbone.0.s8_latern.weight", "", "", 0, 1, 0);
+    m->s16 = make_conv(m, "backbone.0.s16_latern.weight", "", "", 0, 1, 1);
+    if (spe_use_upconv(m)) {
+      // per-tap rows for the low-resolution form of s16_latern(up16sto8s(x)) (elementwise.hip
+      // upconv_combine): row t*256 + co = weight[co][:][kh][kw], t = kh*3 + kw
+      const auto sh = param_shape(m, "backbone.0.s16_latern.weight");
+      const int co_n = (int)sh[0], ci_n = (int)sh[1];
+      std::vector<float> rows;
+      if (m->dmem) {
+        const auto& src = m->host["backbone.0.s16_latern.weight"];
+        rows.assign((size_t)9 * co_n * ci_n, 0.f);
+        for (int t = 0; t < 9; ++t)
+          for (int co = 0; co < co_n; ++co)
+            for (int ci = 0; ci < ci_n; ++ci)
+              rows[((size_t)t * co_n + co) * ci_n + ci] = src[((size_t)co * ci_n + ci) * 9 + t];
       }
+      Conv& c = m->s16taps;
+      c.N = 9 * co_n; c.K = ci_n; c.Kpad = pad64(ci_n); c.Cin = ci_n;
+      c.w = upload_rows(m, rows, c.N, c.K, c.Kpad);
     }
-    m->neckip = pack_conv(m, w, bias, co_n, ci_n, (int)so[2], (int)so[3], 0, 1, 1);
+    m->outc = make_conv(m, "backbone.0.output_conv.weight", "", "backbone.0.output_conv.bias", 0, 1, 1);
+    m->inproj = make_conv(m, "input_proj.weight", "", "input_proj.bias", 0, 1, 0);
+    if (spe_use_neckfold(m)) {
+      const auto so = param_shape(m, "backbone.0.output_conv.weight");   // [512][512][3][3]
+      const auto sp = param_shape(m, "input_proj.weight");                // [hidden][512][1][1]
+      const int cm = (int)so[0], ci_n = (int)so[1], co_n = (int)sp[0], taps = (int)(so[2] * so[3]);
+      std::vector<float> w((size_t)co_n * ci_n * taps, 0.f), bias(co_n, 0.f);
+      if (m->dmem) {
+        const auto& wo = m->host["backbone.0.output_conv.weight"];
+        const auto& bo = m->host["backbone.0.output_conv.bias"];
+        const auto& wp = m->host["input_proj.weight"];
+        const auto& bp = m->host["input_proj.bias"];
+        std::vector<double> acc((size_t)ci_n * taps);
+        for (int co = 0; co < co_n; ++co) {
+          std::fill(acc.begin(), acc.end(), 0.0);
+          double b = bp[co];
+          for (int j = 0; j < cm; ++j) {
+            const double a = wp[(size_t)co * cm + j];
+            const float* src = &wo[(size_t)j * ci_n * taps];
+            for (size_t k = 0; k < acc.size(); ++k) acc[k] += a * src[k];
+            b += a * bo[j];
+          }
+          for (size_t k = 0; k < acc.size(); ++k) w[(size_t)co * ci_n * taps + k] = (float)acc[k];
+          bias[co] = (float)b;
+        }
+      }
+      m->neckip = pack_conv(m, w, bias, co_n, ci_n, (int)so[2], (int)so[3], 0, 1, 1);
+    }
   }
 
   m->enc.clear();
@@ -651,7 +672,7 @@ int build_device(spe_model* m) {
   m->crossV.w = upload_rows(m, vall, m->crossV.N, d, m->crossV.Kpad);
   m->crossV.bias = upload_f32(m, vb.data(), vb.size());
 
-  const int fs = c.input_size / 8;
+  const int fs = c.input_size / spe_feat_stride(m);
   m->pos = upload_T(m, sine_pos(fs, fs, d));
   m->qpos = upload_T(m, m->host["query_embed.weight"]);
   if (m->esz == 2 || m->x6) {
@@ -693,7 +714,8 @@ Ws spe_plan(const spe_model* m, int B) {
   const auto& c = m->cfg;
   const size_t E = m->esz;
   const size_t S = c.input_size, H2 = S / 2, H4 = S / 4, H8 = S / 8, H16 = S / 16;
-  const size_t T = H8 * H8, Q = c.num_queries, d = c.hidden_dim, ff = c.dim_feedforward, L = c.dec_layers;
+  const bool s16bb = m->backbone == SPE_BACKBONE_RESNET50_S16;   // no xs8 keep, no neck regions
+  const size_t T = s16bb ? H16 * H16 : H8 * H8, Q = c.num_queries, d = c.hidden_dim, ff = c.dim_feedforward, L = c.dec_layers;
   Ws w{};
   size_t off = 0;
   auto take = [&](size_t bytes) { size_t o = off; off += (bytes + 255) & ~size_t(255); return o; };
@@ -706,10 +728,10 @@ Ws spe_plan(const spe_model* m, int B) {
   w.x0 = w.t1;                                       // consumed by the stem before t1 is used
   w.t2 = take((size_t)B * std::max(H4 * H4 * 64, std::max(H8 * H8 * 128, H16 * H16 * 256)) * E);
   w.ds = take((size_t)B * H4 * H4 * 256 * E);
-  w.xs8 = take((size_t)B * H8 * H8 * 512 * E);
-  w.up = take((size_t)B * H8 * H8 * 1024 * E);
-  w.cat = take((size_t)B * H8 * H8 * 512 * E);
-  w.neck = take((size_t)B * H8 * H8 * 512 * E);
+  w.xs8 = take(s16bb ? 0 : (size_t)B * H8 * H8 * 512 * E);
+  w.up = take(s16bb ? 0 : (size_t)B * H8 * H8 * 1024 * E);
+  w.cat = take(s16bb ? 0 : (size_t)B * H8 * H8 * 512 * E);
+  w.neck = take(s16bb ? 0 : (size_t)B * H8 * H8 * 512 * E);
   w.src = take((size_t)B * T * d * E);
   w.srcpos = take((size_t)B * T * d * E);   // memory + pos (bf16 fused path: cross-attention K input)
   w.qkv = take((size_t)B * T * 3 * d * E);
@@ -752,7 +774,13 @@ int spe_abi_version(void) { return SPE_ABI_VERSION; }
 const char* spe_last_error(void) { return g_err.c_str(); }
 
 int spe_model_create(const spe_model_config* cfg, spe_model** out) {
+  return spe_model_create_backbone(cfg, SPE_BACKBONE_RESNET50_S8, out);
+}
+
+int spe_model_create_backbone(const spe_model_config* cfg, int backbone, spe_model** out) {
   if (!cfg || !out) return fail(SPE_E_ARG, "null argument");
+  if (backbone != SPE_BACKBONE_RESNET50_S8 && backbone != SPE_BACKBONE_RESNET50_S16)
+    return fail(SPE_E_ARG, "backbone: SPE_BACKBONE_RESNET50_S8 or SPE_BACKBONE_RESNET50_S16");
   if (cfg->hidden_dim != 256 || cfg->nheads * 32 != cfg->hidden_dim)
     return fail(SPE_E_ARG, "only hidden_dim=256 with head_dim=32 is supported");
   if (cfg->input_size % 16 || cfg->input_size < 32) return fail(SPE_E_ARG, "input_size must be a multiple of 16");
@@ -773,7 +801,8 @@ int spe_model_create(const spe_model_config* cfg, spe_model** out) {
   m->x3 = cfg->dtype == SPE_DTYPE_F32X3_ || m->x6;
   if (m->x3) { m->cfg.dtype = SPE_DTYPE_F32_; if (m->cfg.attn_dtype) m->cfg.attn_dtype = SPE_DTYPE_F32_; }
   m->esz = cfg->dtype == SPE_DTYPE_BF16_ ? 2 : 4;
-  m->spec = build_spec(*cfg);
+  m->backbone = backbone;
+  m->spec = build_spec(*cfg, backbone);
   *out = m;
   return 0;
 }
@@ -826,7 +855,7 @@ int spe_model_finalize(spe_model* m) {
   e = hipDeviceSynchronize();
   if (e != hipSuccess || m->upload_err) return fail(e != hipSuccess ? (int)e : m->upload_err, "weight upload failed");
   if ((m->esz == 2 || m->x6) && m->family == 0) {
-    const int d = m->cfg.hidden_dim, fs = m->cfg.input_size / 8, T = fs * fs, Q = m->cfg.num_queries;
+    const int d = m->cfg.hidden_dim, fs = m->cfg.input_size / spe_feat_stride(m), T = fs * fs, Q = m->cfg.num_queries;
     auto proj = [&](const void* A, int rows, const Conv& w, void* out) {
       GemmArgs g{};
       g.A = A; g.lda = d; g.B = w.w; g.ldb = w.Kpad;

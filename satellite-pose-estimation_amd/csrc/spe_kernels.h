@@ -95,6 +95,11 @@ int spe_btail_wide_perm(int n1, int k);
 bool spe_btail_wide_enabled();
 bool spe_btail_wide_serves(const BtailArgs& a);   // what spe_launch_btail_wide launches
 int spe_btail_wide_tiles(const BtailArgs& a);     // its grid (row tiles) for a served problem
+// the final form, (k1, n1, n2) = (256, 1024, 256) only: z = y . W1p^T + b1 without the ReLU unless relu_z,
+// and y not stored when a.y is null (the stride-16 DETR's last bottleneck -> input_proj); 1 = not served
+int spe_launch_btail_wide_proj(const BtailArgs& a, bool relu_z, hipStream_t s);
+bool spe_btail_wide_proj_serves(const BtailArgs& a);
+bool spe_btail_wide_proj_enabled();               // SPE_BTAIL_PROJ=1: the model takes it (A/B knob; default 0)
 int spe_launch_gemm2(const GemmArgs& g, int mode, hipStream_t s);   // 1 = not applicable
 int spe_launch_sgemm(const GemmArgs& g, int mode, hipStream_t s);   // 1 = not applicable
 int spe_launch_lnproj(const GemmArgs& g, hipStream_t s);             // 1 = not applicable (lnproj.hip)

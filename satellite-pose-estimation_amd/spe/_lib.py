@@ -41,17 +41,18 @@ SPE_RTDETR_MBV3_LARGE = 1003     # spe_rtdetr_config.depth: MobileNetV3_Large in
 SPE_RTDETR_GHOSTNETV2 = 1004     # spe_rtdetr_config.depth: GhostNetV2
 GH_POST_NONE, GH_POST_GATE, GH_POST_RESIDUAL = 0, 1, 2
 MB_ACT_NONE, MB_ACT_RELU, MB_ACT_HSWISH = 0, 1, 4
+SPE_BACKBONE_RESNET50_S8, SPE_BACKBONE_RESNET50_S16 = 0, 1     # spe_model_create_backbone
 SPE_STAGE_ENCODE, SPE_STAGE_DECODE, SPE_STAGE_BACKBONE, SPE_STAGE_TRANSFORMER = 1, 2, 4, 8
 SPE_PNP_EPNP, SPE_PNP_RANSAC_P3P_LM, SPE_PNP_EPNP_RANSAC_SIGMA, SPE_PNP_EPNP_LM, SPE_PNP_EPNP_CERES = 0, 1, 2, 3, 4
 SPE_PNP_EXHAUSTIVE = 5           # spe_pnp_exhaustive only
 SPE_PNP_OK, SPE_PNP_NO_FG, SPE_PNP_CV_ERROR, SPE_PNP_RANSAC_FALLBACK, SPE_PNP_UNPINNED = 0, 1, 2, 3, 4
 
 # every symbol include/spe.h declares (checked by tests/test_capi.py)
-EXPORTS = ["spe_abi_version", "spe_last_error", "spe_model_create", "spe_model_destroy", "spe_model_set_param",
+EXPORTS = ["spe_abi_version", "spe_last_error", "spe_model_create", "spe_model_create_backbone", "spe_model_destroy", "spe_model_set_param",
            "spe_model_num_params", "spe_model_param_name", "spe_model_finalize", "spe_model_workspace_bytes",
            "spe_forward", "spe_forward_stages", "spe_forward_stages_u8", "spe_preprocess", "spe_preprocess_submission", "spe_criterion", "spe_criterion_sigma", "spe_ensemble_fuse", "spe_postprocess", "spe_pnp_batch", "spe_pnp_exhaustive", "spe_debug_pnp_exhaustive_stages", "spe_self_assess", "spe_speed_score", "spe_model_profile_begin",
            "spe_model_profile_end", "spe_model_profile_get", "spe_debug_gemm", "spe_debug_gemm_path", "spe_debug_gemm_h3", "spe_debug_ffn_h3", "spe_debug_ffn_h3_perm", "spe_debug_gemm_planes", "spe_debug_attention",
-           "spe_debug_layernorm", "spe_debug_ffn", "spe_debug_xattn", "spe_debug_xattn_h3", "spe_debug_upconv", "spe_debug_btail", "spe_debug_decsa", "spe_debug_decproj", "spe_debug_decxproj", "spe_debug_wfrag_pack", "spe_debug_decffn", "spe_debug_decq", "spe_debug_btail_perm", "spe_debug_btail_wide", "spe_debug_btail_wide_perm", "spe_debug_stempool", "spe_rtdetr_create", "spe_rtdetr_forward",
+           "spe_debug_layernorm", "spe_debug_ffn", "spe_debug_xattn", "spe_debug_xattn_h3", "spe_debug_upconv", "spe_debug_btail", "spe_debug_decsa", "spe_debug_decproj", "spe_debug_decxproj", "spe_debug_wfrag_pack", "spe_debug_decffn", "spe_debug_decq", "spe_debug_btail_perm", "spe_debug_btail_wide", "spe_debug_btail_wide_proj", "spe_debug_btail_wide_perm", "spe_debug_stempool", "spe_rtdetr_create", "spe_rtdetr_forward",
            "spe_rtdetr_forward_stages", "spe_rtdetr_forward_stages_u8",
            "spe_jpeg_workspace_bytes", "spe_jpeg_decode",
            "spe_debug_dwconv_tiles", "spe_debug_dwconv", "spe_debug_se_gate", "spe_debug_pwconv", "spe_debug_rtdetr_backbone",
@@ -103,6 +104,7 @@ def load(path: str):
         raise ImportError(f"{path}: ABI version {v}, this binding needs {ABI_VERSION}")
     L.spe_last_error.restype = ctypes.c_char_p
     L.spe_model_create.argtypes = [ctypes.POINTER(ModelConfig), ctypes.POINTER(P)]
+    L.spe_model_create_backbone.argtypes = [ctypes.POINTER(ModelConfig), I, ctypes.POINTER(P)]
     L.spe_model_destroy.argtypes = [P]
     L.spe_model_destroy.restype = None
     L.spe_model_set_param.argtypes = [P, ctypes.c_char_p, P, I64]
@@ -149,6 +151,7 @@ def load(path: str):
     L.spe_debug_btail.argtypes = [P, P, I, I, P, P, I, P, P, P, I, P, P, I, I]
     L.spe_debug_btail_perm.argtypes = [I]
     L.spe_debug_btail_wide.argtypes = [P, P, I, I, P, I, P, I, P, P, I, I, P, I, P, P, I, I, I]
+    L.spe_debug_btail_wide_proj.argtypes = L.spe_debug_btail_wide.argtypes + [I]
     L.spe_debug_btail_wide_perm.argtypes = [I, I]
     L.spe_debug_decsa.argtypes = [P, P, I, I, I, P, I, P, P, I, P, P, P, I, P, P, P, ctypes.c_float]
     L.spe_debug_decproj.argtypes = [P, P, I, P, I, I, I, P, I, P, P, P]

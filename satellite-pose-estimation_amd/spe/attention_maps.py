@@ -2,7 +2,8 @@
 DETR.forward_with_attention returns.  No plotting: each function returns the [feat, feat] arrays the
 reference hands to imshow, one per query, for a caller to draw.
 
-Tokens are in row-major order over the stride-8 feature map (token = y * feat + x), as the model flattens
+Tokens are in row-major order over the feature map (token = y * feat + x, feat = cfg.feat_size: stride 8, or 16
+behind the plain resnet50 backbone), as the model flattens
 them (REV/models/transformer.py:51-55).
 """
 from __future__ import annotations

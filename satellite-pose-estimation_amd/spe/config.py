@@ -14,6 +14,9 @@ import numpy as np
 _DATA = os.path.join(os.path.dirname(__file__), "data")
 
 
+BACKBONES = ("resnet50s8", "resnet50")
+
+
 @dataclass(frozen=True)
 class SpeConfig:
     input_size: int = 416          # --input_size (REV/main.py:99)
@@ -25,11 +28,21 @@ class SpeConfig:
     dim_feedforward: int = 2048    # --dim_feedforward (REV/main.py:127)
     num_classes: int = 11          # REV/models/detr_speed.py:305 (+1 no-object)
     sigma_head: bool = False       # UNC sigma head (UNC/src/zoo/rtdetr/rtdetr_decoder.py:295-297)
+    backbone: str = "resnet50s8"   # --backbone (REV/main.py): "resnet50s8" (Backbone8s) or "resnet50" (Backbone)
+
+    def __post_init__(self):
+        if self.backbone not in BACKBONES:
+            raise ValueError(f"backbone {self.backbone!r}: one of {BACKBONES}")
+
+    @property
+    def stride(self) -> int:
+        # Backbone8s: the stride-8 fusion neck (REV/models/backbone.py:140-142); Backbone: ResNet-50 cut
+        # after layer3, stride 16, no neck (REV/models/backbone.py:57-102)
+        return 16 if self.backbone == "resnet50" else 8
 
     @property
     def feat_size(self) -> int:
-        # ResNet-50 stride-8 feature map (REV/models/backbone.py:140-142)
-        return self.input_size // 8
+        return self.input_size // self.stride
 
     @property
     def tokens(self) -> int:
@@ -37,8 +50,16 @@ class SpeConfig:
 
     @classmethod
     def from_args(cls, args) -> "SpeConfig":
-        """Build from a reference-style argparse.Namespace (REV/main.py:90-187)."""
-        return cls(input_size=int(getattr(args, "input_size", 416)),
+        """Build from a reference-style argparse.Namespace (REV/main.py:90-187).  The backbone follows
+        build_backbone (REV/models/backbone.py:188-195): "resnet50" is the plain stride-16 Backbone, every
+        other name the stride-8 Backbone8s -- except resnet18 / resnet34, which the reference cannot run."""
+        name = str(getattr(args, "backbone", "resnet50s8"))
+        if name in ("resnet18", "resnet34"):
+            raise ValueError(f"backbone {name!r}: the reference declares num_channels 512 for it but returns "
+                             "layer3's 256 channels, so its input_proj mismatches (REV/models/backbone.py:71,100); "
+                             "not supported")
+        return cls(backbone="resnet50" if name == "resnet50" else "resnet50s8",
+                   input_size=int(getattr(args, "input_size", 416)),
                    num_queries=int(getattr(args, "num_queries", 11)),
                    enc_layers=int(getattr(args, "enc_layers", 6)),
                    dec_layers=int(getattr(args, "dec_layers", 6)),

@@ -2,7 +2,7 @@
 REV/models/detr_speed.py:32-100,264-336) over the HIP path in libspe.so.
 
     model, criterion, postprocessors = build_model(args)
-    model.load_state_dict(state_dict)      # the reference's 412 keys (checkpoint['model'])
+    model.load_state_dict(state_dict)      # the reference's 412 keys (checkpoint['model']; 408 for --backbone resnet50)
     out = model(samples)                   # NestedTensor | list[Tensor] | Tensor [B,3,S,S]
     results = postprocessors['points'](out, clip_bbox_list)
 
@@ -23,7 +23,9 @@ from .misc import NestedTensor, nested_tensor_from_tensor_list
 
 
 class DETR(nn.Module):
-    """Keypoint-set predictor (REV/models/detr_speed.py:32-100), HIP implementation.
+    """Keypoint-set predictor (REV/models/detr_speed.py:32-100), HIP implementation.  cfg.backbone
+    "resnet50s8": the stride-8 fusion neck (Backbone8s); "resnet50": ResNet-50 cut after layer3 with
+    input_proj straight on the stride-16 map (Backbone, REV/models/backbone.py:57-102).
 
     dtype "bf16": bf16 storage / MFMA with fp32 accumulation, softmax, LayerNorm and heads
     (throughput path).  dtype "fp32": exact-f32 MFMA everywhere (parity path).  dtype "fp32x3":
@@ -56,7 +58,8 @@ class DETR(nn.Module):
                               "fp32h3": _lib.SPE_DTYPE_F32H3}[dtype],
                              _lib.SPE_DTYPE_F16 if self.attn_dtype == "fp16" else 0)
         h = ctypes.c_void_p()
-        _lib.check(L.spe_model_create(ctypes.byref(c), ctypes.byref(h)), "spe_model_create")
+        bb = {"resnet50s8": _lib.SPE_BACKBONE_RESNET50_S8, "resnet50": _lib.SPE_BACKBONE_RESNET50_S16}[cfg.backbone]
+        _lib.check(L.spe_model_create_backbone(ctypes.byref(c), bb, ctypes.byref(h)), "spe_model_create_backbone")
         self._h = h
         self._keys = [L.spe_model_param_name(h, i).decode() for i in range(L.spe_model_num_params(h))]
 
@@ -133,7 +136,7 @@ class DETR(nn.Module):
         return out, o
 
     def encode(self, images, ws, stream=None, part=None, B=None):
-        """Encode stage (backbone, neck, input_proj, encoder): images -> memory kept in `ws`.
+        """Encode stage (backbone, neck (resnet50s8), input_proj, encoder): images -> memory kept in `ws`.
         part="backbone": up to input_proj (images -> src in `ws`); part="transformer": the
         encoder layers over the src a backbone part left in `ws` (images may be None, B given)."""
         stage = {None: _lib.SPE_STAGE_ENCODE, "backbone": _lib.SPE_STAGE_BACKBONE,
@@ -208,8 +211,8 @@ class DETR(nn.Module):
 
     def forward_with_attention(self, images, enc_layer=-1, dec_layer=-2, clip_bbox=None, *, stream=None, maps=None):
         """forward() plus the attention maps the reference's visualize_features.py hooks: the head-averaged
-        probabilities of transformer.encoder.layers[enc_layer].self_attn ("enc", [B,T,T], T = (S/8)^2
-        tokens) and transformer.decoder.layers[dec_layer].multihead_attn ("dec", [B,Q,T]), device fp32.
+        probabilities of transformer.encoder.layers[enc_layer].self_attn ("enc", [B,T,T], T = cfg.tokens:
+        (S/8)^2, or (S/16)^2 with the plain resnet50 backbone) and transformer.decoder.layers[dec_layer].multihead_attn ("dec", [B,Q,T]), device fp32.
         Returns (outputs, maps); `outputs` is forward()'s dict, bit for bit.  Model dtypes bf16 and fp32.
         `maps` (optional): {"enc": tensor or None, "dec": tensor or None} of caller buffers to fill; None
         skips that tap (spe_forward_attention's NULL map)."""
@@ -226,7 +229,7 @@ class DETR(nn.Module):
         if clip_bbox is not None:
             clip_bbox = clip_bbox.to(device=dev, dtype=torch.float32).contiguous()
         out, o = self._outputs(B, dev, clip_bbox, False)
-        T = (S // 8) ** 2
+        T = self.cfg.tokens
         shapes = {"enc": (B, T, T), "dec": (B, self.cfg.num_queries, T)}
         if maps is None:
             maps = {k: torch.empty(*s, device=dev) for k, s in shapes.items()}

@@ -1,8 +1,9 @@
 """Seeded synthetic inputs for the keypoint-set pose path.
 
 * `param_shapes(cfg)`  - the reference's state_dict key space (412 keys for the REV
-  DETR, REV/models/detr_speed.py:32-56, backbone.py:105-131, transformer.py:18-49),
-  plus the optional UNC-style sigma head.
+  DETR, REV/models/detr_speed.py:32-56, backbone.py:105-131, transformer.py:18-49; 408 with the
+  plain stride-16 backbone, backbone.py:57-102, which has no neck), plus the optional UNC-style
+  sigma head.
 * `random_weights(cfg, seed)` - deterministic random-init weights in that key space
   (there is no trained checkpoint in the reference tree), with non-trivial FrozenBN
   statistics so the BN folding path is exercised.
@@ -54,7 +55,10 @@ def param_shapes(cfg: SpeConfig):
             ("cls_embed.weight", (cfg.num_classes + 1, d)), ("cls_embed.bias", (cfg.num_classes + 1,))]
     for j, (o, i) in enumerate([(d, d), (d, d), (2, d)]):
         out += [(f"point_embed.layers.{j}.weight", (o, i)), (f"point_embed.layers.{j}.bias", (o,))]
-    out += [("query_embed.weight", (Q, d)), ("input_proj.weight", (d, 512, 1, 1)), ("input_proj.bias", (d,))]
+    # Backbone8s projects its 512-channel neck output, Backbone layer3's 1024 channels (REV/models/backbone.py:100,131)
+    s16 = cfg.backbone == "resnet50"
+    out += [("query_embed.weight", (Q, d)), ("input_proj.weight", (d, 1024 if s16 else 512, 1, 1)),
+            ("input_proj.bias", (d,))]
     b = "backbone.0.body"
     out += [(f"{b}.conv1.weight", (64, 3, 7, 7))] + _bn_keys(f"{b}.bn1", 64)
     cin = 64
@@ -67,10 +71,11 @@ def param_shapes(cfg: SpeConfig):
             if k == 0:
                 out += [(f"{p}.downsample.0.weight", (4 * w, cin, 1, 1))] + _bn_keys(f"{p}.downsample.1", 4 * w)
             cin = 4 * w
-    out += [("backbone.0.s8_latern.weight", (256, 512, 1, 1)),
-            ("backbone.0.s16_latern.weight", (256, 1024, 3, 3)),
-            ("backbone.0.output_conv.weight", (512, 512, 3, 3)),
-            ("backbone.0.output_conv.bias", (512,))]
+    if not s16:
+        out += [("backbone.0.s8_latern.weight", (256, 512, 1, 1)),
+                ("backbone.0.s16_latern.weight", (256, 1024, 3, 3)),
+                ("backbone.0.output_conv.weight", (512, 512, 3, 3)),
+                ("backbone.0.output_conv.bias", (512,))]
     if cfg.sigma_head:
         for j, (o, i) in enumerate([(d, d), (d, d), (1, d)]):
             out += [(f"sigma_embed.layers.{j}.weight", (o, i)), (f"sigma_embed.layers.{j}.bias", (o,))]

@@ -67,7 +67,7 @@ def main():
     args = ap.parse_args()
     dev = torch.device("cuda:0")
     cfg = SpeConfig()                                   # config 2: 416 / 11 queries / 6 + 6 layers
-    B, T, Q = args.batch, (cfg.input_size // 8) ** 2, cfg.num_queries
+    B, T, Q = args.batch, cfg.tokens, cfg.num_queries
     w = random_weights(cfg, 0)
     img = torch.from_numpy(synthetic_batch(cfg, B, 1)["images"]).to(dev)
     res = {"device": torch.cuda.get_device_name(0), "input_size": cfg.input_size, "batch": B, "tokens": T, "queries": Q,
