@@ -524,6 +524,16 @@ int spe_debug_upconv(void* stream, int dtype, const void* z, void* out, int ldo,
  * {(64, 64, r), (64, 128, r), (128, 64, null)}. */
 int spe_debug_btail(void* stream, const void* a, int lda, int k1, const void* r, const void* w3, int ld3,
                     const float* b3, void* y, const void* w1p, int ld1, const float* b1, void* z, int n2, int M);
+/* btail with every row stride and its two store forms chosen by the caller (additive, ABI 9; spe_debug_btail
+ * follows the SPE_BTAIL_ROWS knob).  rows: 0 = r, y and z move as 8-byte row pieces, 1 = as 16-byte pieces
+ * (strides then multiples of 8); w1p holds conv1's columns in spe_debug_btail_perm order either way.
+ * H > 0 and W > 0 request the compact y store for M = B * H * W pixels: only the pixels with even h and
+ * even w are stored, densely, as [B][H/2][W/2][256] with row stride ldy -- served for (k1, n2, r) = (64, 128, r),
+ * even H and W and M a multiple of H * W; otherwise y is stored whole.  Returns 0 = launched, y whole;
+ * 2 = launched, y compact; 1 = not served (nothing launched); < 0 = bad argument. */
+int spe_debug_btail_rows(void* stream, const void* a, int lda, int k1, const void* r, int ldr, const void* w3, int ld3,
+                         const float* b3, void* y, int ldy, const void* w1p, int ld1, const float* b1, void* z, int ldz,
+                         int n2, int M, int rows, int H, int W);
 /* btail_wide (bf16, the layer-2 / layer-3 bottleneck tail fused with the next block's conv1,
  * btail_wide.hip; additive, ABI 9): y [M][n1] (row stride ldy) = relu(a [M][k1] . w3^T + b3
  * (+ r [M][n1], row stride ldr)), z [M][n2] (row stride ldz) = relu(y . w1p^T + b1) where w1p
@@ -578,6 +588,10 @@ int spe_debug_decq(void* stream, const void* x, int ldx, int M, int N, const voi
                    const void* r, int ldr, int period, void* y, int ldy);
 /* the K-column order btail's second product expects: stored column k holds channel perm(k) */
 int spe_debug_btail_perm(int k);
+/* btail with 16-byte row pieces (additive, ABI 9): the weight row (output channel) that row p of the kernel's
+ * image of w3 / w1p holds, so that MFMA fragment j leaves lane group fg, register r with channel
+ * 32 (j / 2) + 8 sg + 4 (j % 2) + r, sg = (0, 2, 1, 3)[fg]; -1 for p < 0 */
+int spe_debug_btail_row_perm(int p);
 /* the same for btail_wide at block-output width n1 (512 / 1024); -1 outside [0, n1) */
 int spe_debug_btail_wide_perm(int n1, int k);
 /* stempool (bf16, stempool.hip): out [B][Po][Po] rows of stride ldo (Po = S/4 for S % 4 == 0) =

@@ -190,8 +190,26 @@ int spe_debug_btail(void* stream, const void* a, int lda, int k1, const void* r,
   t.A = a; t.lda = lda; t.k1 = k1; t.R = r; t.ldr = 256;
   t.w3 = w3; t.ld3 = ld3; t.b3 = b3; t.y = y; t.ldy = 256; t.n1 = 256;
   t.w1 = w1p; t.ld1 = ld1; t.b1 = b1; t.z = z; t.ldz = n2; t.n2 = n2; t.M = M;
+  t.rows = spe_btail_rows_enabled();
   const int rc = spe_launch_btail(t, (hipStream_t)stream);
   return rc != 0 ? spe_fail(SPE_E_LAUNCH, "btail launch rejected its arguments") : 0;
+}
+
+// btail.hip with every stride, the row-piece form (rows: 0 = 8-byte, 1 = 16-byte pieces) and, with H > 0 and W > 0, the compact y store requested for
+// M = B * H * W pixels.  0 = launched, y stored whole; 2 = launched, y stored as the even pixels
+// [B][H/2][W/2][256] (row stride ldy); 1 = not served (nothing launched); < 0 = bad argument
+int spe_debug_btail_rows(void* stream, const void* a, int lda, int k1, const void* r, int ldr, const void* w3, int ld3,
+                         const float* b3, void* y, int ldy, const void* w1p, int ld1, const float* b1, void* z, int ldz,
+                         int n2, int M, int rows, int H, int W) {
+  if (!a || !w3 || !b3 || !y || !w1p || !b1 || !z || M < 0 || H < 0 || W < 0) return spe_fail(SPE_E_ARG, "bad argument");
+  BtailArgs t{};
+  t.A = a; t.lda = lda; t.k1 = k1; t.R = r; t.ldr = ldr;
+  t.w3 = w3; t.ld3 = ld3; t.b3 = b3; t.y = y; t.ldy = ldy; t.n1 = 256;
+  t.w1 = w1p; t.ld1 = ld1; t.b1 = b1; t.z = z; t.ldz = ldz; t.n2 = n2; t.M = M;
+  t.rows = rows != 0; t.ycompact = H > 0 && W > 0; t.H = H; t.W = W;
+  const int rc = spe_launch_btail(t, (hipStream_t)stream);
+  if (rc != 0 && rc != 1) return spe_fail(SPE_E_LAUNCH, "btail launch failed");
+  return rc == 0 && spe_btail_ycompact_serves(t) ? 2 : rc;
 }
 
 // 0 = launched, 1 = not served (nothing launched, y and z untouched), < 0 = bad argument
@@ -332,6 +350,7 @@ int spe_debug_decq(void* stream, const void* x, int ldx, int M, int N, const voi
 }
 
 int spe_debug_btail_perm(int k) { return spe_btail_perm(k); }
+int spe_debug_btail_row_perm(int p) { return p >= 0 ? spe_btail_row_perm(p) : -1; }
 int spe_debug_btail_wide_perm(int n1, int k) { return spe_btail_wide_perm(n1, k); }
 
 int spe_debug_stempool(void* stream, const void* x, const void* w, int ldw, const float* bias, void* out, int ldo,

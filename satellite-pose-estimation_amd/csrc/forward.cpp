@@ -92,13 +92,17 @@ struct BlockIn {
   const float* amax;
   bool t1_ready;             // this block's conv1 ran in the previous block's tail
   bool src_ready;            // stride-16 model: input_proj ran in the last block's tail (src is written, x is not)
+  bool x_compact;            // x holds only the even pixels, [B][H/2][H/2][ld]: all this block's stride-2 downsample reads
 };
 
 // conv3 (+ residual R) + relu of a block: with the next block's conv1 as one launch (btail.hip, or
 // btail_wide.hip for layers 2 and 3) when the next block carries permuted conv1 weights (registry.cpp c1p) and the shapes are served
 // (*tailed), else the GEMM.  c3 over A is either Block::c3 over t2 or Block::c3ds over [t2 | x].
+// Ho > 0: the M = B * Ho * Ho rows of `out` have one more reader only, the next block's stride-2 downsample, so
+// the tail may store just the even pixels (*compact; btail.hip YC, behind SPE_BTAIL_YCOMPACT).
 int conv3_tail_or_gemm(Fwd& f, const Block* nb, const Conv& c3, const void* A, int lda, const float* a_amax,
-                       const void* R, void* out, float* out_amax, int M, bool* tailed) {
+                       const void* R, void* out, float* out_amax, int M, bool* tailed, int Ho = 0,
+                       bool* compact = nullptr) {
   spe_model* m = f.m;
   int rc = 1;
   if (nb) {
@@ -107,10 +111,17 @@ int conv3_tail_or_gemm(Fwd& f, const Block* nb, const Conv& c3, const void* A, i
     t.w3 = c3.w; t.ld3 = c3.Kpad; t.b3 = c3.bias; t.y = out; t.ldy = c3.N; t.n1 = c3.N;
     t.w1 = nb->c1p.w; t.ld1 = nb->c1p.Kpad; t.b1 = nb->c1p.bias; t.z = f.P(f.w.t1); t.ldz = nb->c1.N; t.n2 = nb->c1.N;
     t.M = M;
+    t.rows = m->btail_rows;
+    // (below one 16-row tile per wave of the persistent grid the launch is latency, not store traffic: y stays
+    // whole there, and the launch tables of the small golden cases stay as recorded)
+    t.ycompact = compact && Ho > 0 && m->btail_ycompact && M >= 16 * 8 * spe_cu_count(); t.H = t.W = Ho;
+    const bool yc = c3.N == 256 && spe_btail_ycompact_serves(t);
     const double flops = 2.0 * M * ((double)c3.N * c3.K + (double)nb->c1.N * c3.N);
-    const double bytes = ((double)M * (c3.K + c3.N + nb->c1.N) + (R ? (double)M * c3.N : 0.0)) * m->esz;
+    const double bytes = ((double)M * (c3.K + c3.N / (yc ? 4.0 : 1.0) + nb->c1.N) + (R ? (double)M * c3.N : 0.0)) * m->esz;
+    if (compact) *compact = false;
     if (c3.N == 256) {
       rc = run_other(m, "conv.1x1", flops, bytes, f.s, [&] { return spe_launch_btail(t, f.s); });
+      if (compact) *compact = rc == 0 && yc;
     } else if (spe_btail_wide_serves(t) && spe_btail_wide_tiles(t) >= spe_cu_count() / 2) {
       // layers 2 and 3 (btail_wide.hip), every boundary measured faster than its two launches in the
       // profiled B = 64 step (fused vs conv3 + conv1, ms): layer 2 inner 0.122 vs 0.170, layer 2 -> 3
@@ -199,6 +210,14 @@ int bottleneck(Fwd& f, size_t bi, BlockIn& in) {
         GemmArgs g = linear_args(blk.ds, f.P(in.x), in.ld, B * H * H, f.P(w.ds), blk.ds.N);
         g.amax_a = in.amax;
         CK(run_gemm(m, "conv.1x1", g, GEMM_LINEAR, s));
+      } else if (in.x_compact) {
+        // the previous tail stored exactly the pixels this conv reads, densely: the same conv kernel at stride 1
+        // over [B][Ho][Ho] (the same rows in the same K order, so the same bits; the streaming GEMM_LINEAR
+        // kernels sum K in another order and were not tried)
+        Conv d1 = blk.ds;
+        d1.stride = 1;
+        GemmArgs g = conv_args(d1, f.P(in.x), B, Ho, Ho, f.P(w.ds), blk.ds.N);
+        CK(run_gemm(m, "conv.1x1s2", g, GEMM_CONV, s));
       } else {
         GemmArgs g = conv_args(blk.ds, f.P(in.x), B, H, H, f.P(w.ds), blk.ds.N);
         g.amax_a = in.amax;
@@ -210,9 +229,16 @@ int bottleneck(Fwd& f, size_t bi, BlockIn& in) {
     // stride-16 model's last block)
     if (s16bb && bi + 1 == m->blocks.size())
       TRY(final_tail(f, blk.c3, f.P(w.t2), blk.c2.N, f.P(res), B * Ho * Ho, &in.src_ready));
+    // The block output has two readers, the next block's conv1 and its residual path.  When that path is a
+    // stride-2 downsample (and conv1 runs in the tail) nothing reads the odd pixels: every model (both
+    // backbones; only bf16 models have tails) walks its blocks through this function alone, the neck reads
+    // block 6's output (xs8, which is why that block is excluded) and the last block's, and the attention
+    // taps and the activation-scale slots (fp32h3 only) read no block output.
+    const bool ds_only = nb && nb->stride == 2 && nb->has_ds && outbuf != w.xs8;
+    in.x_compact = false;
     if (!in.src_ready)
       TRY(conv3_tail_or_gemm(f, nb, blk.c3, f.P(w.t2), blk.c2.N, t2_amax, f.P(res), f.P(outbuf), out_amax, B * Ho * Ho,
-                             &in.t1_ready));
+                             &in.t1_ready, ds_only ? Ho : 0, &in.x_compact));
     in.amax = out_amax;
   }
   in.ld = blk.c3.N;
@@ -320,7 +346,7 @@ int backbone_stage(Fwd& f, const ImageSrc& images) {
       return spe_launch_maxpool3s2(f.P(w.stem), f.P(pool_at), B, H, H, 64, Hp, Hp, dt, s, uld);
     }));
   }
-  BlockIn x{pool_at, uld, Hp, stem_amax, false, false};  // (the max-pool's maximum is the stem's)
+  BlockIn x{pool_at, uld, Hp, stem_amax, false, false, false};  // (the max-pool's maximum is the stem's)
   const float* xs8_amax = nullptr;
   for (size_t bi = 0; bi < m->blocks.size(); ++bi) {
     TRY(bottleneck(f, bi, x));

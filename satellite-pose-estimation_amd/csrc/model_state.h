@@ -208,6 +208,9 @@ struct spe_model {
   Conv ipp;                // bf16 stride-16 models: input_proj with its K columns in spe_btail_wide_perm order, the
                            // second product of the last bottleneck's tail (btail_wide.hip's final form), or empty
   std::vector<Block> blocks;
+  // layer-1 tails (btail.hip), read from SPE_BTAIL_ROWS / SPE_BTAIL_YCOMPACT at finalize: 16-byte row pieces,
+  // and the layer-1 -> layer-2 block output stored for its stride-2 downsample only
+  int btail_rows = 0, btail_ycompact = 0;
   std::vector<Enc> enc;
   std::vector<Dec> dec;
   void* pos = nullptr;     // [tokens][256] T

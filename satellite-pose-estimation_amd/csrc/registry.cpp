@@ -470,6 +470,8 @@ int build_device(spe_model* m) {
     m->stem = make_conv(m, b + ".conv1.weight", b + ".bn1", "", m->esz == 4 ? 4 : 8, 2, 3);
   }
   m->blocks.clear();
+  m->btail_rows = spe_btail_rows_enabled();
+  m->btail_ycompact = spe_btail_ycompact_enabled();
   const int nblk[3] = {3, 4, 6};
   for (int li = 0; li < 3; ++li)
     for (int k = 0; k < nblk[li]; ++k) {

@@ -84,10 +84,24 @@ struct BtailArgs {
   const void* w1; int ld1; const float* b1;   // next conv1, permuted columns [n2][ld1]
   void* z; int ldz; int n2;              // next conv1 output [M][n2]
   int M;
+  // btail.hip only.  rows: R, y and z move as 16-byte row pieces instead of 8-byte ones (same results).
+  // ycompact: y's only reader is a stride-2 1x1 conv over the M = B*H*W pixels, so y is stored as the dense [B][H/2][W/2][n1] of the even pixels (row stride ldy) where
+  // spe_btail_ycompact_serves, else whole.
+  int rows, ycompact, H, W;
 };
 int spe_launch_btail(const BtailArgs& a, hipStream_t s);   // 1 = not applicable
 int spe_btail_perm(int k);
+// rows: the weight row (output channel) that row p of W3's and W1's LDS image holds.  MFMA fragment j
+// (rows 16 j .. 16 j + 15) leaves lane group fg, register r with row 16 j + 4 fg + r, i.e. with channel
+// 32 (j / 2) + 8 sg + 4 (j % 2) + r, sg = fg with its two bits swapped (0, 2, 1, 3): the fragment pair
+// (2i, 2i + 1) gives a lane 8 consecutive channels (btail.hip's header: why sg and not fg)
+__host__ __device__ inline int spe_btail_row_perm(int p) {
+  return (p & ~31) | (((p >> 2) & 1) << 4) | (((p >> 3) & 1) << 3) | (((p >> 4) & 1) << 2) | (p & 3);
+}
 bool spe_btail_enabled();
+bool spe_btail_rows_enabled();                    // SPE_BTAIL_ROWS (default 1)
+bool spe_btail_ycompact_enabled();                // SPE_BTAIL_YCOMPACT (default 1)
+bool spe_btail_ycompact_serves(const BtailArgs& a);   // what spe_launch_btail stores compactly
 // the wide form: (k1, n1, n2) in {(128, 512, 128), (128, 512, 256), (256, 1024, 256)}; 1 = not served
 // (another shape, or SPE_BTAIL_WIDE=0)
 int spe_launch_btail_wide(const BtailArgs& a, hipStream_t s);

@@ -52,7 +52,7 @@ EXPORTS = ["spe_abi_version", "spe_last_error", "spe_model_create", "spe_model_c
            "spe_model_num_params", "spe_model_param_name", "spe_model_finalize", "spe_model_workspace_bytes",
            "spe_forward", "spe_forward_stages", "spe_forward_stages_u8", "spe_preprocess", "spe_preprocess_submission", "spe_criterion", "spe_criterion_sigma", "spe_ensemble_fuse", "spe_postprocess", "spe_pnp_batch", "spe_pnp_exhaustive", "spe_debug_pnp_exhaustive_stages", "spe_self_assess", "spe_speed_score", "spe_model_profile_begin",
            "spe_model_profile_end", "spe_model_profile_get", "spe_debug_gemm", "spe_debug_gemm_path", "spe_debug_gemm_h3", "spe_debug_ffn_h3", "spe_debug_ffn_h3_perm", "spe_debug_gemm_planes", "spe_debug_attention",
-           "spe_debug_layernorm", "spe_debug_ffn", "spe_debug_xattn", "spe_debug_xattn_h3", "spe_debug_upconv", "spe_debug_btail", "spe_debug_decsa", "spe_debug_decproj", "spe_debug_decxproj", "spe_debug_wfrag_pack", "spe_debug_decffn", "spe_debug_decq", "spe_debug_btail_perm", "spe_debug_btail_wide", "spe_debug_btail_wide_proj", "spe_debug_btail_wide_perm", "spe_debug_stempool", "spe_rtdetr_create", "spe_rtdetr_forward",
+           "spe_debug_layernorm", "spe_debug_ffn", "spe_debug_xattn", "spe_debug_xattn_h3", "spe_debug_upconv", "spe_debug_btail", "spe_debug_decsa", "spe_debug_decproj", "spe_debug_decxproj", "spe_debug_wfrag_pack", "spe_debug_decffn", "spe_debug_decq", "spe_debug_btail_perm", "spe_debug_btail_rows", "spe_debug_btail_row_perm", "spe_debug_btail_wide", "spe_debug_btail_wide_proj", "spe_debug_btail_wide_perm", "spe_debug_stempool", "spe_rtdetr_create", "spe_rtdetr_forward",
            "spe_rtdetr_forward_stages", "spe_rtdetr_forward_stages_u8",
            "spe_jpeg_workspace_bytes", "spe_jpeg_decode",
            "spe_debug_dwconv_tiles", "spe_debug_dwconv", "spe_debug_se_gate", "spe_debug_pwconv", "spe_debug_rtdetr_backbone",
@@ -150,6 +150,8 @@ def load(path: str):
     L.spe_debug_upconv.argtypes = [P, I, P, P, I, I, I, I, I]
     L.spe_debug_btail.argtypes = [P, P, I, I, P, P, I, P, P, P, I, P, P, I, I]
     L.spe_debug_btail_perm.argtypes = [I]
+    L.spe_debug_btail_rows.argtypes = [P, P, I, I, P, I, P, I, P, P, I, P, I, P, P, I, I, I, I, I, I]
+    L.spe_debug_btail_row_perm.argtypes = [I]
     L.spe_debug_btail_wide.argtypes = [P, P, I, I, P, I, P, I, P, P, I, I, P, I, P, P, I, I, I]
     L.spe_debug_btail_wide_proj.argtypes = L.spe_debug_btail_wide.argtypes + [I]
     L.spe_debug_btail_wide_perm.argtypes = [I, I]
