@@ -144,11 +144,19 @@ typedef struct {
  * hard-coded 64 x 64, so it too is accepted at input_size 256 only (SPE_E_ARG otherwise).  Its never-called
  * conv_head / classifier parameters are part of the key space (accepted and ignored). */
 #define SPE_RTDETR_GHOSTNETV2 1004
+/* spe_rtdetr_config.depth value that selects MobileNetV3_Small (UNC/nn/backbone/mobilenetv3.py:228-320, the
+ * commented alternative of UNC/configs/rtdetr_speed/include/rtdetr_mobilenet.yml): 11 blocks, block 0 at the
+ * full stem resolution with squeeze-excite and a depthwise-only skip, Conv1 / Conv2 bare convolutions.  The
+ * same hard-coded 64 x 64 resize: input_size 256 only (SPE_E_ARG otherwise).  Its never-called linear3 / bn3
+ * parameters are part of the key space (accepted and ignored).  Environment: SPE_MBS_ENTRY=0 runs block 0
+ * launch by launch instead of through the fused entry kernel (read once per process). */
+#define SPE_RTDETR_MBV3_SMALL 1005
 
 typedef struct {
   int depth;            /* backbone selector: 18 (BasicBlock) or 50 (BottleNeck) = PResNet variant d of that
-                         * depth; SPE_RTDETR_MBV3_LARGE = MobileNetV3_Large; SPE_RTDETR_GHOSTNETV2 = GhostNetV2 */
-  int input_size;       /* eval_spatial_size (256); multiple of 32; MobileNetV3_Large / GhostNetV2: 256 only */
+                         * depth; SPE_RTDETR_MBV3_LARGE = MobileNetV3_Large; SPE_RTDETR_GHOSTNETV2 = GhostNetV2;
+                         * SPE_RTDETR_MBV3_SMALL = MobileNetV3_Small */
+  int input_size;       /* eval_spatial_size (256); multiple of 32; MobileNetV3_Large / _Small / GhostNetV2: 256 only */
   int num_queries;      /* RTDETRTransformer.num_queries (30), <= 64 */
   int dec_layers;       /* num_decoder_layers (3) */
   int enc_ff;           /* HybridEncoder.dim_feedforward (1024, GELU) */
@@ -627,6 +635,21 @@ int spe_debug_pwconv(void* stream, int dtype, const void* a, int lda, const void
  * [B][C_l][S/8 .. S/32]^2 (C_l = 128, 256, 512, x 4 for depth 50). */
 int spe_debug_rtdetr_backbone(spe_model* m, void* stream, const float* images, int batch, void* workspace,
                               int64_t workspace_bytes, float* f0, float* f1, float* f2);
+/* mb_stem: the MobileNetV3 stem alone, conv1 3x3/s2/p1 3 -> 16 + bias + Hardswish -> NHWC y [B][S/2][S/2][16].
+ * Source: images (fp32 NCHW [B][3][S][S]) or, when crops is not null, 8-bit crops [B][S][S][channels]
+ * (channels 1 / 3; 4-byte aligned, S % 32 == 0).  w fp32 [27][16] with k = (ci*3 + kh)*3 + kw, bias fp32 [16]. */
+int spe_debug_mb_stem(void* stream, int dtype, const float* images, const void* crops, int channels, const float* w,
+                      const float* bias, void* y, int B, int S);
+/* mbs_entry (mbv3s.hip): the MobileNetV3_Small entry in one launch, from the same two sources (crops need no
+ * alignment here) to three NHWC maps [B][S/4][S/4][16] of dtype: pooled = the 2 x 2 mean of the stem map,
+ * skip = dw3x3/s2(stem) + bias, t2 = relu(dw3x3/s2(relu(stem . We + be)) + bias); the stem map and the expanded
+ * map are zero outside [0, S/2)^2 (the reference's padding).  pool_partials (nullable): fp32
+ * [B][spe_debug_mbs_entry_tiles(S)][16], per 8 x 8 tile the sum of the stored t2 values in a fixed order.
+ * weights: fp32 [1040], BatchNorm folded: stem [27][16], bias [16], expand [ci][co] 256, bias 16, depthwise
+ * [9][16], bias 16, skip depthwise [9][16], bias 16.  S a multiple of 16, 32 <= S <= 4096 (SPE_E_ARG otherwise). */
+int spe_debug_mbs_entry_tiles(int S);
+int spe_debug_mbs_entry(void* stream, int dtype, const float* images, const void* crops, int channels,
+                        const float* weights, void* pooled, void* skip, void* t2, float* pool_partials, int B, int S);
 
 /* GhostNetV2 backbone kernels (ghostv2.hip, ABI 9 additions).  Every refusal below is SPE_E_ARG before any
  * launch; dtype BF16_ (fp32 accumulation) or F32_.

@@ -419,6 +419,32 @@ int spe_debug_rtdetr_backbone(spe_model* m, void* stream, const float* images, i
   return 0;
 }
 
+int spe_debug_mb_stem(void* stream, int dtype, const float* images, const void* crops, int channels, const float* w,
+                      const float* bias, void* y, int B, int S) {
+  if ((!images && !crops) || !w || !bias || !y) return spe_fail(SPE_E_ARG, "null argument");
+  if (dtype != SPE_DTYPE_BF16 && dtype != SPE_DTYPE_F32) return spe_fail(SPE_E_ARG, "bad dtype");
+  const ImageSrc src{crops ? nullptr : images, (const uint8_t*)crops, crops ? channels : 0};
+  const int rc = spe_launch_mb_stem(src, w, bias, y, B, S, dtype, (hipStream_t)stream);
+  return rc < 0 ? spe_fail(SPE_E_ARG, "mb_stem: S even (crops: S % 32 == 0, 4-byte aligned, channels 1 / 3)") : rc;
+}
+
+// ---- MobileNetV3_Small entry (mbv3s.hip)
+int spe_debug_mbs_entry_tiles(int S) { return spe_mbs_entry_fits(1, S) ? spe_mbs_entry_tiles(S) : 0; }
+
+int spe_debug_mbs_entry(void* stream, int dtype, const float* images, const void* crops, int channels,
+                        const float* weights, void* pooled, void* skip, void* t2, float* pool_partials, int B, int S) {
+  if ((!images && !crops) || !weights || !pooled || !skip || !t2) return spe_fail(SPE_E_ARG, "null argument");
+  if (dtype != SPE_DTYPE_BF16 && dtype != SPE_DTYPE_F32) return spe_fail(SPE_E_ARG, "bad dtype");
+  if (!spe_mbs_entry_fits(B, S) || (crops && channels != 1 && channels != 3))
+    return spe_fail(SPE_E_ARG, "mbs_entry: S a multiple of 16 in [32, 4096], B <= 65535, crops of 1 or 3 channels");
+  MbsEntryArgs a{};
+  a.src = ImageSrc{crops ? nullptr : images, (const uint8_t*)crops, crops ? channels : 0};
+  a.w = weights; a.pooled = pooled; a.skip = skip; a.t2 = t2; a.pool = pool_partials;
+  a.B = B; a.S = S;
+  const int rc = spe_launch_mbs_entry(a, dtype, (hipStream_t)stream);
+  return rc < 0 ? spe_fail(SPE_E_LAUNCH, "mbs_entry launch rejected its arguments") : rc;
+}
+
 // ---- GhostNetV2 backbone kernels (ghostv2.hip)
 int spe_debug_ghost_cheap(void* stream, int dtype, const void* x1, int ldx, int xoff, const float* w, const float* bias,
                           void* y, const void* gate, const void* resid, float* pool_partials, int B, int H, int W,

@@ -126,6 +126,9 @@ struct MbBlock {             // Block (mobilenetv3.py:45-120)
 struct RtMbv3 {
   float *stem_w = nullptr, *stem_b = nullptr;   // conv1 + bn1: [27][16], [16]
   Conv conv_b, conv_c, last;   // Conv1 with the 2x2 mean folded in (6x6 / s4 / p2 over the stem output), Conv2, conv2
+  int side_act = 4;            // Conv1 / Conv2: MB_ACT_HSWISH behind Bn1 / Bn2 (Large), MB_ACT_NONE for Small's bare convs
+  Conv conv_b3;                // Small: Conv1 as the plain 3x3 / s2 over mbs_entry's pooled map
+  float* entry_w = nullptr;    // Small: mbs_entry's folded weights, fp32 [MBS_W_FLOATS]
   std::vector<MbBlock> blocks;
 };
 // GhostNetV2 backbone (UNC/nn/backbone/ghostnetv2.py:88-441), BatchNorm folded everywhere.  A ghost tensor of
@@ -156,7 +159,8 @@ struct RtGhost {
 };
 struct RtModel {
   spe_rtdetr_config cfg{};
-  bool mbv3 = false;                    // cfg.depth == SPE_RTDETR_MBV3_LARGE
+  bool mbv3 = false;                    // cfg.depth == SPE_RTDETR_MBV3_LARGE or SPE_RTDETR_MBV3_SMALL
+  bool mb_small = false;                // ... the latter
   RtMbv3 mb;
   bool ghost = false;                   // cfg.depth == SPE_RTDETR_GHOSTNETV2
   RtGhost gh;

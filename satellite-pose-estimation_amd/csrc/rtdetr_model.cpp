@@ -28,7 +28,8 @@ namespace {
 
 const int RESNET_CFG18[4] = {2, 2, 2, 2}, RESNET_CFG50[4] = {3, 4, 6, 3};
 
-inline bool is_mbv3(const spe_rtdetr_config& c) { return c.depth == SPE_RTDETR_MBV3_LARGE; }
+inline bool is_mbv3_small(const spe_rtdetr_config& c) { return c.depth == SPE_RTDETR_MBV3_SMALL; }
+inline bool is_mbv3(const spe_rtdetr_config& c) { return c.depth == SPE_RTDETR_MBV3_LARGE || is_mbv3_small(c); }
 inline bool is_ghost(const spe_rtdetr_config& c) { return c.depth == SPE_RTDETR_GHOSTNETV2; }
 inline bool is_presnet(const spe_rtdetr_config& c) { return !is_mbv3(c) && !is_ghost(c); }
 inline int resnet_expansion(const spe_rtdetr_config& c) { return is_presnet(c) && c.depth >= 50 ? 4 : 1; }
@@ -40,6 +41,15 @@ const MbRow MBV3_LARGE[15] = {
     {5, 40, 120, 40, 0, 1, 1},   {5, 40, 120, 40, 0, 1, 1},   {3, 40, 240, 80, 1, 0, 2},  {3, 80, 200, 80, 1, 0, 1},
     {3, 80, 184, 80, 1, 0, 1},   {3, 80, 184, 80, 1, 0, 1},   {3, 80, 480, 112, 1, 1, 1}, {3, 112, 672, 112, 1, 1, 1},
     {5, 112, 672, 160, 1, 1, 2}, {5, 160, 672, 160, 1, 1, 1}, {5, 160, 960, 160, 1, 1, 1}};
+// MobileNetV3_Small.bneck (mobilenetv3.py:248-260).  Block 0: full stem resolution, SE, stride 2 with in == out
+const MbRow MBV3_SMALL[11] = {
+    {3, 16, 16, 16, 0, 1, 2},  {3, 16, 72, 24, 0, 0, 2},  {3, 24, 88, 24, 0, 0, 1},  {5, 24, 96, 40, 1, 1, 2},
+    {5, 40, 240, 40, 1, 1, 1}, {5, 40, 240, 40, 1, 1, 1}, {5, 40, 120, 48, 1, 1, 1}, {5, 48, 144, 48, 1, 1, 1},
+    {5, 48, 288, 96, 1, 1, 2}, {5, 96, 576, 96, 1, 1, 1}, {5, 96, 576, 96, 1, 1, 1}};
+struct MbTable { const MbRow* rows; int n, last_in, head_in; };   // conv2's and linear3's input widths
+inline MbTable mb_table(const spe_rtdetr_config& c) {
+  return is_mbv3_small(c) ? MbTable{MBV3_SMALL, 11, 96, 576} : MbTable{MBV3_LARGE, 15, 160, 960};
+}
 inline int se_hidden(int c) { return c / 4 > 8 ? c / 4 : 8; }
 
 // GhostNetV2.cfgs at width 1.0 (ghostnetv2.py:297-319) in layer_id order: dw kernel, mid, out, SE, stride, and
@@ -88,14 +98,16 @@ std::vector<std::pair<std::string, std::vector<int64_t>>> rt_spec(const spe_rtde
     lin(p + ".out_proj", d, d);
   };
   add("temper_param", {1});
-  if (is_mbv3(c)) {     // registration order of MobileNetV3_Large.__init__ (mobilenetv3.py:136-173)
+  if (is_mbv3(c)) {     // registration order of MobileNetV3_{Large,Small}.__init__ (mobilenetv3.py:136-173, 241-270)
     const std::string b = "backbone.";
+    const MbTable t = mb_table(c);
     add(b + "conv1.weight", {16, 3, 3, 3});
-    bn(b + "bn1", 16); bn(b + "Bn1", 128); bn(b + "Bn2", 256);
+    if (!is_mbv3_small(c)) { bn(b + "bn1", 16); bn(b + "Bn1", 128); bn(b + "Bn2", 256); }
     add(b + "Conv1.weight", {128, 16, 3, 3});
     add(b + "Conv2.weight", {256, 128, 3, 3});
-    for (int i = 0; i < 15; ++i) {
-      const MbRow& r = MBV3_LARGE[i];
+    if (is_mbv3_small(c)) bn(b + "bn1", 16);       // Small: Conv1 / Conv2 are bare, bn1 is registered after them
+    for (int i = 0; i < t.n; ++i) {
+      const MbRow& r = t.rows[i];
       const std::string p = b + "bneck." + std::to_string(i);
       add(p + ".conv1.weight", {r.cexp, r.cin, 1, 1}); bn(p + ".bn1", r.cexp);
       add(p + ".conv2.weight", {r.cexp, 1, r.k, r.k}); bn(p + ".bn2", r.cexp);
@@ -114,8 +126,8 @@ std::vector<std::pair<std::string, std::vector<int64_t>>> rt_spec(const spe_rtde
         add(p + ".skip.0.weight", {r.cout, 1, 3, 3}); bn(p + ".skip.1", r.cout);
       }
     }
-    add(b + "conv2.weight", {512, 160, 1, 1}); bn(b + "bn2", 512);
-    add(b + "linear3.weight", {1280, 960}); bn(b + "bn3", 1280);     // built, never called
+    add(b + "conv2.weight", {512, t.last_in, 1, 1}); bn(b + "bn2", 512);
+    add(b + "linear3.weight", {1280, t.head_in}); bn(b + "bn3", 1280);     // built, never called
   }
   if (is_ghost(c)) {    // registration order of GhostNetV2.__init__ (ghostnetv2.py:331-387)
     const std::string b = "backbone.";
@@ -392,12 +404,13 @@ RtWs rt_plan(const spe_model* m, int B) {
 
 // ---- MobileNetV3_Large packing: eval BatchNorm (eps 1e-5) folded in double, like fold_conv
 void bn_fold(spe_model* m, const std::string& bn, int C, std::vector<double>& scale, std::vector<double>& shift) {
+  scale.assign(C, 1.0);
+  shift.assign(C, 0.0);
+  if (bn.empty()) return;            // a bare conv (MobileNetV3_Small's Conv1 / Conv2): identity
   const auto& g = m->host[bn + ".weight"];
   const auto& b = m->host[bn + ".bias"];
   const auto& rm = m->host[bn + ".running_mean"];
   const auto& rv = m->host[bn + ".running_var"];
-  scale.assign(C, 1.0);
-  shift.assign(C, 0.0);
   for (int c = 0; c < C; ++c) {
     scale[c] = (double)g[c] / std::sqrt((double)rv[c] + 1e-5);
     shift[c] = (double)b[c] - (double)rm[c] * scale[c];
@@ -453,6 +466,9 @@ MbDw mb_dw(spe_model* m, const std::string& wkey, const std::string& bn, int str
 void build_mbv3(spe_model* m) {
   RtMbv3& mb = m->rt->mb;
   const std::string b = "backbone.";
+  const bool small = m->rt->mb_small;
+  const MbTable tab = mb_table(m->rt->cfg);
+  std::vector<float> entry(MBS_W_FLOATS, 0.f);     // Small: mbs_entry's weights (spe_kernels.h, MBS_W_*)
   {   // conv1 + bn1: fp32 [27][16] with k = (ci*3 + kh)*3 + kw
     std::vector<double> scale, shift;
     bn_fold(m, b + "bn1", 16, scale, shift);
@@ -464,12 +480,17 @@ void build_mbv3(spe_model* m) {
     }
     mb.stem_w = upload_f32(m, wt.data(), wt.size());
     mb.stem_b = upload_f32(m, bias.data(), bias.size());
+    std::copy(wt.begin(), wt.end(), entry.begin() + MBS_W_STEM);
+    std::copy(bias.begin(), bias.end(), entry.begin() + MBS_W_STEM_B);
   }
-  mb.conv_b = mb_conv(m, b + "Conv1.weight", b + "Bn1", "", 2, 1, true);
-  mb.conv_c = mb_conv(m, b + "Conv2.weight", b + "Bn2", "", 2, 1);
+  // Small: Conv1 / Conv2 are bare convolutions (no BatchNorm, no activation)
+  mb.side_act = small ? MB_ACT_NONE : MB_ACT_HSWISH;
+  mb.conv_b = mb_conv(m, b + "Conv1.weight", small ? "" : b + "Bn1", "", 2, 1, true);
+  if (small) mb.conv_b3 = mb_conv(m, b + "Conv1.weight", "", "", 2, 1);     // over mbs_entry's pooled map
+  mb.conv_c = mb_conv(m, b + "Conv2.weight", small ? "" : b + "Bn2", "", 2, 1);
   mb.blocks.clear();
-  for (int i = 0; i < 15; ++i) {
-    const MbRow& r = MBV3_LARGE[i];
+  for (int i = 0; i < tab.n; ++i) {
+    const MbRow& r = tab.rows[i];
     const std::string p = b + "bneck." + std::to_string(i);
     MbBlock k;
     k.cin = r.cin; k.cexp = r.cexp; k.cout = r.cout; k.stride = r.stride;
@@ -511,6 +532,27 @@ void build_mbv3(spe_model* m) {
     mb.blocks.push_back(k);
   }
   mb.last = mb_conv(m, b + "conv2.weight", b + "bn2", "", 1, 0);
+  if (small) {     // block 0's expand [ci][co], depthwise and skip depthwise [9][16], fp32 with BatchNorm folded
+    const std::string p = b + "bneck.0";
+    std::vector<double> scale, shift;
+    bn_fold(m, p + ".bn1", 16, scale, shift);
+    const auto& w1 = m->host[p + ".conv1.weight"];
+    for (int co = 0; co < 16; ++co) {
+      entry[MBS_W_EXP_B + co] = (float)shift[co];
+      for (int ci = 0; ci < 16; ++ci) entry[MBS_W_EXP + ci * 16 + co] = (float)((double)w1[(size_t)co * 16 + ci] * scale[co]);
+    }
+    const char* dwk[2][2] = {{".conv2.weight", ".bn2"}, {".skip.0.weight", ".skip.1"}};
+    const int off[2][2] = {{MBS_W_DW, MBS_W_DW_B}, {MBS_W_SKIP, MBS_W_SKIP_B}};
+    for (int j = 0; j < 2; ++j) {
+      bn_fold(m, p + dwk[j][1], 16, scale, shift);
+      const auto& w = m->host[p + dwk[j][0]];
+      for (int c = 0; c < 16; ++c) {
+        entry[off[j][1] + c] = (float)shift[c];
+        for (int t = 0; t < 9; ++t) entry[off[j][0] + t * 16 + c] = (float)((double)w[(size_t)c * 9 + t] * scale[c]);
+      }
+    }
+    mb.entry_w = upload_f32(m, entry.data(), entry.size());
+  }
 }
 
 // bytes a backbone's first launch reads per input pixel: the fp32 batch's three channels or the crop's 1 / 3
@@ -583,9 +625,12 @@ int rt_backbone_presnet(spe_model* m, hipStream_t s, const ImageSrc& images, int
   return 0;
 }
 
-// MobileNetV3_Large.forward (mobilenetv3.py:206-225) at input 256: stem -> x0 [B][128][128][16]; Conv1 (2x2
+// MobileNetV3_Large.forward / MobileNetV3_Small.forward (mobilenetv3.py:206-225, 301-320) at input 256: stem -> x0 [B][128][128][16]; Conv1 (2x2
 // mean folded in) -> f0, Conv2 -> f1; the 15 blocks ping-pong bufA / bufB with the expanded tensor in t1,
-// the depthwise output in t2 and the skip branch in sc; conv2 -> f2
+// the depthwise output in t2 and the skip branch in sc; conv2 -> f2.  Small with the fused entry (mbs_entry,
+// SPE_MBS_ENTRY, default on): one launch leaves the 2x2 mean of the stem map in x0 [B][64][64][16] (Conv1 reads
+// it as a plain 3x3/s2), block 0's skip in sc and its depthwise output in t2 with the SE pool partials; the
+// block loop then starts at block 0's SE gate.
 int rt_backbone_mbv3(spe_model* m, hipStream_t s, const ImageSrc& images, int B, char* ws, const RtWs& w) {
   const RtModel& r = *m->rt;
   const RtMbv3& mb = r.mb;
@@ -619,25 +664,42 @@ int rt_backbone_mbv3(spe_model* m, hipStream_t s, const ImageSrc& images, int B,
                      (double)B * d.C * (Hin * Hin + Ho * Ho) * E, s, [&] { return spe_launch_mb_dwconv(a, dt, s); });
   };
   const int H0 = S / 2;
-  CK(run_other(m, "conv.stem.mb", 2.0 * B * H0 * H0 * 16 * 27,
-               (double)B * (S * S * image_px_bytes(images) + H0 * H0 * 16 * E), s,
-               [&] { return spe_launch_mb_stem(images, mb.stem_w, mb.stem_b, P(w.x0), B, S, dt, s); }));
-  CK(pw(mb.conv_b, P(w.x0), H0, P(w.f0), MB_ACT_HSWISH, nullptr, nullptr));
-  CK(pw(mb.conv_c, P(w.f0), r.lvl_s[0], P(w.f1), MB_ACT_HSWISH, nullptr, nullptr));
+  const bool fused = r.mb_small && spe_mbs_entry_enabled();
+  if (fused) {
+    if ((size_t)spe_mbs_entry_tiles(S) * 16 > MB_POOL_MAX) return fail(SPE_E_WORKSPACE, "SE pool partials exceed the plan");
+    MbsEntryArgs a{};
+    a.src = images; a.w = mb.entry_w;
+    a.pooled = P(w.x0); a.skip = P(w.sc); a.t2 = P(w.t2); a.pool = (float*)P(w.mbpool);
+    a.B = B; a.S = S;
+    const double px = (double)B * (S / 4) * (S / 4);
+    CK(run_other(m, "conv.entry.mbs", 2.0 * px * 16 * (4 * 27 + 4 * 16 + 9 + 9),
+                 (double)B * S * S * image_px_bytes(images) + 3.0 * px * 16 * E, s,
+                 [&] { return spe_launch_mbs_entry(a, dt, s); }));
+    CK(pw(mb.conv_b3, P(w.x0), S / 4, P(w.f0), mb.side_act, nullptr, nullptr));
+  } else {
+    CK(run_other(m, "conv.stem.mb", 2.0 * B * H0 * H0 * 16 * 27,
+                 (double)B * (S * S * image_px_bytes(images) + H0 * H0 * 16 * E), s,
+                 [&] { return spe_launch_mb_stem(images, mb.stem_w, mb.stem_b, P(w.x0), B, S, dt, s); }));
+    CK(pw(mb.conv_b, P(w.x0), H0, P(w.f0), mb.side_act, nullptr, nullptr));
+  }
+  CK(pw(mb.conv_c, P(w.f0), r.lvl_s[0], P(w.f1), mb.side_act, nullptr, nullptr));
   int H = H0;
   size_t cur = w.x0;
   const size_t sc_pw = w.sc + (((w.f0 - w.sc) / 2) & ~size_t(255));   // second half of sc: the skip branch's 1x1 output
+  bool entry_done = fused;             // block 0's expand, depthwise and skip are already in t2 / sc
   for (const MbBlock& k : mb.blocks) {
     const int Ho = H / k.stride;
     const size_t outbuf = cur == w.bufA ? w.bufB : w.bufA;
-    CK(pw(k.expand, P(cur), H, P(w.t1), k.act, nullptr, nullptr));
+    const bool head = entry_done;
+    entry_done = false;
+    if (!head) CK(pw(k.expand, P(cur), H, P(w.t1), k.act, nullptr, nullptr));
     float* pool = nullptr;
     const int tiles = spe_mb_dwconv_tiles(Ho, Ho);
     if (k.se) {
       if ((size_t)tiles * k.cexp > MB_POOL_MAX) return fail(SPE_E_WORKSPACE, "SE pool partials exceed the plan");
       pool = (float*)P(w.mbpool);      // rows [B][tiles][C]: B * tiles * C <= B * MB_POOL_MAX floats
     }
-    CK(dw(k.dw, P(w.t1), H, P(w.t2), k.act, pool));
+    if (!head) CK(dw(k.dw, P(w.t1), H, P(w.t2), k.act, pool));
     const float* scale = nullptr;
     if (k.se) {
       MbSeArgs a{};
@@ -651,7 +713,7 @@ int rt_backbone_mbv3(spe_model* m, hipStream_t s, const ImageSrc& images, int B,
     }
     const void* res = P(cur);
     if (k.has_skip_dw) {
-      CK(dw(k.skip_dw, P(cur), H, P(w.sc), MB_ACT_NONE, nullptr));
+      if (!head) CK(dw(k.skip_dw, P(cur), H, P(w.sc), MB_ACT_NONE, nullptr));
       res = P(w.sc);
     }
     if (k.has_skip_pw) {
@@ -1065,13 +1127,14 @@ extern "C" {
 int spe_rtdetr_create(const spe_rtdetr_config* cfg, spe_model** out) {
   if (!cfg || !out) return fail(SPE_E_ARG, "null argument");
   if (cfg->depth != 18 && cfg->depth != 50 && !is_mbv3(*cfg) && !is_ghost(*cfg))
-    return fail(SPE_E_ARG, "depth must be a PResNet depth (18 or 50), SPE_RTDETR_MBV3_LARGE or SPE_RTDETR_GHOSTNETV2");
+    return fail(SPE_E_ARG, "depth must be a PResNet depth (18 or 50), SPE_RTDETR_MBV3_LARGE, SPE_RTDETR_MBV3_SMALL or "
+                           "SPE_RTDETR_GHOSTNETV2");
   if (is_ghost(*cfg) && cfg->input_size != 256)
     return fail(SPE_E_ARG, "GhostNetV2 supports input_size 256 only: the backbone resizes its raw stem output to a "
                            "hard-coded 64x64, which is the stride-4 grid the stride-8 / 16 levels are built from "
                            "only at 256");
   if (is_mbv3(*cfg) && cfg->input_size != 256)
-    return fail(SPE_E_ARG, "MobileNetV3_Large supports input_size 256 only: the backbone resizes its stem output to "
+    return fail(SPE_E_ARG, "MobileNetV3_Large / _Small support input_size 256 only: the backbone resizes its stem output to "
                            "a hard-coded 64x64, which is the stride-4 grid the stride-8 / 16 levels are built from "
                            "only at 256");
   if (cfg->input_size % 32 || cfg->input_size < 64) return fail(SPE_E_ARG, "input_size must be a multiple of 32, >= 64");
@@ -1085,6 +1148,7 @@ int spe_rtdetr_create(const spe_rtdetr_config* cfg, spe_model** out) {
   m->rt = new RtModel();
   m->rt->cfg = *cfg;
   m->rt->mbv3 = is_mbv3(*cfg);
+  m->rt->mb_small = is_mbv3_small(*cfg);
   m->rt->ghost = is_ghost(*cfg);
   m->esz = cfg->dtype == SPE_DTYPE_BF16_ ? 2 : 4;
   m->cfg.dtype = cfg->dtype;

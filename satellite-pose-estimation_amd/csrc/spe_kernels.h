@@ -482,6 +482,26 @@ struct MbGemmArgs {
 };
 bool spe_mb_gemm_fits(const MbGemmArgs& g);
 int spe_launch_mb_gemm(const MbGemmArgs& g, int dtype, hipStream_t s);
+// MobileNetV3_Small entry (mbv3s.hip): image -> pooled / skip / t2, NHWC T [B][S/4][S/4][16] each, and t2's SE
+// pool partials fp32 [B][spe_mbs_entry_tiles(S)][16] (nullable; mb_dwconv's layout and fixed-order reduction).
+// w: fp32 [MBS_W_FLOATS], BatchNorm folded: conv1 [27][16] (k = (ci*3 + kh)*3 + kw) + bias, block 0's expand
+// [ci][co] + bias, its depthwise [9][16] + bias, its skip depthwise [9][16] + bias.  Contract: S % 16 == 0,
+// 32 <= S <= 4096, B <= 65535; a u8 source has ch 1 or 3 (no alignment demand: the patch is read by bytes).
+enum {
+  MBS_W_STEM = 0, MBS_W_STEM_B = 432, MBS_W_EXP = 448, MBS_W_EXP_B = 704, MBS_W_DW = 720, MBS_W_DW_B = 864,
+  MBS_W_SKIP = 880, MBS_W_SKIP_B = 1024, MBS_W_FLOATS = 1040
+};
+struct MbsEntryArgs {
+  ImageSrc src;
+  const float* w;
+  void* pooled; void* skip; void* t2;
+  float* pool;
+  int B, S;
+};
+bool spe_mbs_entry_enabled();                     // SPE_MBS_ENTRY (default 1): 0 = block 0 launch by launch
+bool spe_mbs_entry_fits(int B, int S);
+int spe_mbs_entry_tiles(int S);
+int spe_launch_mbs_entry(const MbsEntryArgs& a, int dtype, hipStream_t s);
 // NHWC T [B][HW][C] -> NCHW fp32
 int spe_launch_mb_to_nchw(const void* in, float* out, int B, int HW, int C, int dtype, hipStream_t s);
 

@@ -28,6 +28,13 @@ struct StemU8Lds {
   float x[3 * SU_PLANE];                   // the normalised patch, [c][py][parity][column / 2]
 };
 
+// One crop byte as channel c of the normalised batch: the expression stem_u8_stage evaluates, for kernels that
+// stage a patch of their own (mbv3s.hip)
+SPE_DEV float stem_u8_norm(uint8_t u, int c) {
+  const float mean[3] = {0.485f, 0.456f, 0.406f}, stdv[3] = {0.229f, 0.224f, 0.225f};
+  return ((float)u / 255.f - mean[c]) / stdv[c];
+}
+
 // Stage and normalise the patch of output tile (ty0, tx0) of image b.  Every thread of the work-group calls
 // it; the patch is complete on return.  Needs S % (2 SU_T) == 0 and crops 4-byte aligned (the launchers check).
 template <int CH>

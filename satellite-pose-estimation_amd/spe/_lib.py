@@ -39,6 +39,8 @@ D = ctypes.c_double
 SPE_DTYPE_BF16, SPE_DTYPE_F32, SPE_DTYPE_F16, SPE_DTYPE_F32X3, SPE_DTYPE_F32X6, SPE_DTYPE_F32H3 = 0, 1, 2, 4, 5, 6
 SPE_RTDETR_MBV3_LARGE = 1003     # spe_rtdetr_config.depth: MobileNetV3_Large instead of a PResNet depth
 SPE_RTDETR_GHOSTNETV2 = 1004     # spe_rtdetr_config.depth: GhostNetV2
+SPE_RTDETR_MBV3_SMALL = 1005     # spe_rtdetr_config.depth: MobileNetV3_Small
+MBS_W_FLOATS = 1040              # spe_debug_mbs_entry's folded weights (include/spe.h)
 GH_POST_NONE, GH_POST_GATE, GH_POST_RESIDUAL = 0, 1, 2
 MB_ACT_NONE, MB_ACT_RELU, MB_ACT_HSWISH = 0, 1, 4
 SPE_BACKBONE_RESNET50_S8, SPE_BACKBONE_RESNET50_S16 = 0, 1     # spe_model_create_backbone
@@ -56,6 +58,7 @@ EXPORTS = ["spe_abi_version", "spe_last_error", "spe_model_create", "spe_model_c
            "spe_rtdetr_forward_stages", "spe_rtdetr_forward_stages_u8",
            "spe_jpeg_workspace_bytes", "spe_jpeg_decode",
            "spe_debug_dwconv_tiles", "spe_debug_dwconv", "spe_debug_se_gate", "spe_debug_pwconv", "spe_debug_rtdetr_backbone",
+           "spe_debug_mb_stem", "spe_debug_mbs_entry_tiles", "spe_debug_mbs_entry",
            "spe_debug_ghost_cheap", "spe_debug_dfc_gate", "spe_debug_se_gate_bias", "spe_debug_pool2",
            "spe_debug_rt_resample2x", "spe_debug_rt_query_select", "spe_debug_rt_qpos_hidden", "spe_debug_rt_head_finish",
            "spe_debug_rt_msdeform",
@@ -171,6 +174,9 @@ def load(path: str):
     L.spe_debug_se_gate.argtypes = [P, P, I, F, P, P, P, P, I, I, I]
     L.spe_debug_pwconv.argtypes = [P, I, P, I, P, I, P, P, I, P, I, P, I, I, I, I, I]
     L.spe_debug_rtdetr_backbone.argtypes = [P, P, P, I, P, I64, P, P, P]
+    L.spe_debug_mb_stem.argtypes = [P, I, P, P, I, P, P, P, I, I]
+    L.spe_debug_mbs_entry_tiles.argtypes = [I]
+    L.spe_debug_mbs_entry.argtypes = [P, I, P, P, I, P, P, P, P, P, I, I]
     L.spe_debug_ghost_cheap.argtypes = [P, I, P, I, I, P, P, P, P, P, P, I, I, I, I, I, I]
     L.spe_debug_dfc_gate.argtypes = [P, I, P, P, P, P, P, P, I, I, I, I]
     L.spe_debug_se_gate_bias.argtypes = [P, P, I, F, P, P, P, P, P, I, I, I]

@@ -25,8 +25,9 @@ from .rtdetr_spec import RtdetrConfig, rtdetr_param_shapes, random_rtdetr_weight
 
 
 class RTDETR(nn.Module):
-    """RTDETR(PResNet-vd | MobileNetV3_Large | GhostNetV2, HybridEncoder, RTDETRTransformer) with the sigma
-    head, eval forward; cfg.backbone picks the backbone ("mobilenetv3_large", "ghostnetv2": input_size 256 only).
+    """RTDETR(PResNet-vd | MobileNetV3_Large | MobileNetV3_Small | GhostNetV2, HybridEncoder, RTDETRTransformer)
+    with the sigma head, eval forward; cfg.backbone picks the backbone ("mobilenetv3_large", "MobileNetV3_Small",
+    "ghostnetv2": input_size 256 only).
     dtype "bf16": bf16 storage / MFMA with fp32 accumulation, LayerNorm, softmax and heads;
     "fp32": exact-f32 MFMA everywhere (parity path)."""
 
@@ -37,7 +38,7 @@ class RTDETR(nn.Module):
         self._pending = {}
         self._ready = False
         self._ws = {}
-        selector = {"mobilenetv3_large": _lib.SPE_RTDETR_MBV3_LARGE,
+        selector = {"mobilenetv3_large": _lib.SPE_RTDETR_MBV3_LARGE, "MobileNetV3_Small": _lib.SPE_RTDETR_MBV3_SMALL,
                     "ghostnetv2": _lib.SPE_RTDETR_GHOSTNETV2}.get(cfg.backbone, cfg.depth)
         c = _lib.RtdetrConfig(selector, cfg.input_size, cfg.num_queries, cfg.dec_layers, cfg.enc_ff, cfg.dec_ff,
                               cfg.csp_hidden, cfg.num_classes,

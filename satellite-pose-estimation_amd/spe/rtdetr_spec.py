@@ -18,7 +18,9 @@ from dataclasses import dataclass, asdict
 
 import numpy as np
 
-BACKBONES = ("presnet", "mobilenetv3_large", "ghostnetv2")
+# "MobileNetV3_Small" is spelled as the reference registers the class (`backbone: MobileNetV3_Small` in its
+# configs): the lower-case "mobilenetv3_small" is the name tests/test_rtdetr_mbv3.py pins as refused.
+BACKBONES = ("presnet", "mobilenetv3_large", "ghostnetv2", "MobileNetV3_Small")
 # MobileNetV3_Large.bneck (UNC/nn/backbone/mobilenetv3.py:148-164): kernel, in, expand, out, hardswish, SE, stride
 MBV3_LARGE_BLOCKS = [
     (3, 16, 16, 16, False, False, 1), (3, 16, 64, 24, False, False, 2), (3, 24, 72, 24, False, False, 1),
@@ -26,6 +28,14 @@ MBV3_LARGE_BLOCKS = [
     (3, 40, 240, 80, True, False, 2), (3, 80, 200, 80, True, False, 1), (3, 80, 184, 80, True, False, 1),
     (3, 80, 184, 80, True, False, 1), (3, 80, 480, 112, True, True, 1), (3, 112, 672, 112, True, True, 1),
     (5, 112, 672, 160, True, True, 2), (5, 160, 672, 160, True, True, 1), (5, 160, 960, 160, True, True, 1),
+]
+# MobileNetV3_Small.bneck (mobilenetv3.py:248-260), same columns.  Block 0 is the one row of either table with
+# stride 2 and in == out: its skip is depthwise 3x3/2 + BatchNorm alone (the third Block.skip form).
+MBV3_SMALL_BLOCKS = [
+    (3, 16, 16, 16, False, True, 2), (3, 16, 72, 24, False, False, 2), (3, 24, 88, 24, False, False, 1),
+    (5, 24, 96, 40, True, True, 2), (5, 40, 240, 40, True, True, 1), (5, 40, 240, 40, True, True, 1),
+    (5, 40, 120, 48, True, True, 1), (5, 48, 144, 48, True, True, 1), (5, 48, 288, 96, True, True, 2),
+    (5, 96, 576, 96, True, True, 1), (5, 96, 576, 96, True, True, 1),
 ]
 # GhostNetV2.cfgs at width 1.0 (UNC/nn/backbone/ghostnetv2.py:297-319), one row a block in layer_id order:
 # dw kernel, mid (expansion) width, out width, SE ratio, stride.  Blocks 0-1 build ghost1 in mode "original",
@@ -75,7 +85,7 @@ class RtdetrConfig:
     num_levels: int = 3
     num_points: int = 4             # num_decoder_points
     num_classes: int = 11           # + 1 no-object logit
-    backbone: str = "presnet"       # "presnet" (depth 18 / 50), "mobilenetv3_large" or "ghostnetv2" (depth unused, 256 input only)
+    backbone: str = "presnet"       # "presnet" (depth 18 / 50), or "mobilenetv3_large" / "MobileNetV3_Small" / "ghostnetv2" (depth unused, 256 input only)
 
     def __post_init__(self):
         if self.backbone not in BACKBONES:
@@ -83,8 +93,8 @@ class RtdetrConfig:
 
     @property
     def backbone_channels(self):
-        if self.backbone == "mobilenetv3_large":
-            return [128, 256, 512]                  # Conv1 / Conv2 / conv2 outputs (mobilenetv3.py:215-225)
+        if self.backbone in ("mobilenetv3_large", "MobileNetV3_Small"):
+            return [128, 256, 512]                  # Conv1 / Conv2 / conv2 outputs (mobilenetv3.py:215-225, 301-320)
         if self.backbone == "ghostnetv2":
             return [128, 256, 512]                  # Conv1 / Conv2 / Conv3 outputs (ghostnetv2.py:339-341)
         e = 1 if self.depth < 50 else 4
@@ -130,13 +140,10 @@ def _mha(p, d):
     return [(f"{p}.in_proj_weight", (3 * d, d)), (f"{p}.in_proj_bias", (3 * d,))] + _lin(f"{p}.out_proj", d, d)
 
 
-def mbv3_large_param_shapes():
-    """MobileNetV3_Large's parameters in registration order (mobilenetv3.py:136-173); linear3 / bn3 are
-    built and never called, their keys are part of the state_dict all the same."""
-    b = "backbone"
-    out = [(f"{b}.conv1.weight", (16, 3, 3, 3))] + _bn(f"{b}.bn1", 16) + _bn(f"{b}.Bn1", 128) + _bn(f"{b}.Bn2", 256)
-    out += [(f"{b}.Conv1.weight", (128, 16, 3, 3)), (f"{b}.Conv2.weight", (256, 128, 3, 3))]
-    for i, (k, cin, ce, cout, _hs, se, stride) in enumerate(MBV3_LARGE_BLOCKS):
+def _mbv3_block_shapes(b, blocks):
+    """The bneck Sequential of either MobileNetV3 (Block.__init__, mobilenetv3.py:48-108)."""
+    out = []
+    for i, (k, cin, ce, cout, _hs, se, stride) in enumerate(blocks):
         p = f"{b}.bneck.{i}"
         out += [(f"{p}.conv1.weight", (ce, cin, 1, 1))] + _bn(f"{p}.bn1", ce)
         out += [(f"{p}.conv2.weight", (ce, 1, k, k))] + _bn(f"{p}.bn2", ce)
@@ -152,8 +159,31 @@ def mbv3_large_param_shapes():
             out += [(f"{p}.skip.2.weight", (cout, cin, 1, 1)), (f"{p}.skip.2.bias", (cout,))] + _bn(f"{p}.skip.3", cout)
         elif stride == 2:
             out += [(f"{p}.skip.0.weight", (cout, 1, 3, 3))] + _bn(f"{p}.skip.1", cout)
+    return out
+
+
+def mbv3_large_param_shapes():
+    """MobileNetV3_Large's parameters in registration order (mobilenetv3.py:136-173); linear3 / bn3 are
+    built and never called, their keys are part of the state_dict all the same."""
+    b = "backbone"
+    out = [(f"{b}.conv1.weight", (16, 3, 3, 3))] + _bn(f"{b}.bn1", 16) + _bn(f"{b}.Bn1", 128) + _bn(f"{b}.Bn2", 256)
+    out += [(f"{b}.Conv1.weight", (128, 16, 3, 3)), (f"{b}.Conv2.weight", (256, 128, 3, 3))]
+    out += _mbv3_block_shapes(b, MBV3_LARGE_BLOCKS)
     out += [(f"{b}.conv2.weight", (512, 160, 1, 1))] + _bn(f"{b}.bn2", 512)
     out += [(f"{b}.linear3.weight", (1280, 960))] + _bn(f"{b}.bn3", 1280)
+    return out
+
+
+def mbv3_small_param_shapes():
+    """MobileNetV3_Small's parameters in registration order (mobilenetv3.py:241-270): conv1, the bare Conv1 /
+    Conv2 (no BatchNorm of their own), bn1, bneck, conv2, bn2; linear3 / bn3 are built and never called, their
+    keys are part of the state_dict all the same."""
+    b = "backbone"
+    out = [(f"{b}.conv1.weight", (16, 3, 3, 3)), (f"{b}.Conv1.weight", (128, 16, 3, 3)),
+           (f"{b}.Conv2.weight", (256, 128, 3, 3))] + _bn(f"{b}.bn1", 16)
+    out += _mbv3_block_shapes(b, MBV3_SMALL_BLOCKS)
+    out += [(f"{b}.conv2.weight", (512, 96, 1, 1))] + _bn(f"{b}.bn2", 512)
+    out += [(f"{b}.linear3.weight", (1280, 576))] + _bn(f"{b}.bn3", 1280)
     return out
 
 
@@ -203,6 +233,8 @@ def rtdetr_param_shapes(cfg: RtdetrConfig):
         out += mbv3_large_param_shapes()
     elif cfg.backbone == "ghostnetv2":
         out += ghostv2_param_shapes()
+    elif cfg.backbone == "MobileNetV3_Small":
+        out += mbv3_small_param_shapes()
     else:
         out += _presnet_param_shapes(cfg)
     out += _rtdetr_tail_shapes(cfg, d, C)
@@ -278,9 +310,9 @@ def _rtdetr_tail_shapes(cfg, d, C):
     return out
 
 
-def _draw_mbv3(rng, key, shape):
-    """One MobileNetV3_Large backbone parameter: He-normal convs (depthwise: fan-in k*k), non-trivial
-    BatchNorm statistics, the projection norm bn3 damped (gain 0.3) so the residual stream stays O(1)
+def _draw_mbv3(rng, key, shape, hs_from=6):
+    """One MobileNetV3 backbone parameter (hs_from: the first Hardswish block, 6 Large / 3 Small): He-normal
+    convs (depthwise: fan-in k*k), non-trivial BatchNorm statistics, the projection norm bn3 damped (gain 0.3) so the residual stream stays O(1)
     through 15 blocks, norms in front of a Hardswish widened (gain 0.75 .. 1.5) so its inputs reach
     past -3 and 3, the SE gate's first conv halved and its second doubled so most gate pre-activations
     stay in (-3, 3) while a few saturate."""
@@ -303,12 +335,30 @@ def _draw_mbv3(rng, key, shape):
         if blk is not None and name == "bn3":
             return 0.3 * rng.uniform(0.5, 1.0, shape)
         hswish = (blk is None and name in ("bn1", "Bn1", "Bn2", "bn2")) or \
-                 (blk is not None and blk >= 6 and name in ("bn1", "bn2"))
+                 (blk is not None and blk >= hs_from and name in ("bn1", "bn2"))
         return rng.uniform(0.75, 1.5, shape) if hswish else rng.uniform(0.5, 1.0, shape)
     return rng.normal(0.0, 0.05, shape)
 
 
-GH_RES_GAIN = 0.6      # gain of ghost2's norms and of the shortcut's last norm (see _draw_ghostv2)
+def _draw_mbv3s(rng, key, shape):
+    """One MobileNetV3_Small backbone parameter.  _draw_mbv3's gains let the activations decay through these 11
+    blocks (|x| <= 0.1 behind block 10: two Hardswishes of small inputs halve the expanded tensor, every block
+    from 3 on has an SE gate near 0.5, most blocks have no identity skip), so: Hardswish norms (bn1 / bn2 of
+    blocks >= 3) widened to gain 1.5 .. 3, bn3 gain 0.4 x (0.5 .. 1), the SE gate's second conv tripled.  The
+    golden generator's report then shows block output maxima of 0.6 .. 8.5 and up to 32 % saturated gates."""
+    a = _draw_mbv3(rng, key, shape, hs_from=3)
+    if len(shape) == 4 and ".se.se.4." in key:
+        return a * 1.5
+    part = key.split(".")
+    if len(shape) == 1 and key.endswith("weight") and part[1] == "bneck":
+        if part[-2] == "bn3":
+            return a * (0.4 / 0.3)
+        if int(part[2]) >= 3 and part[-2] in ("bn1", "bn2"):
+            return a * 2.0
+    return a
+
+
+GH_RES_GAIN = 0.6     # gain of ghost2's norms and of the shortcut's last norm (see _draw_ghostv2)
 
 
 def _draw_ghostv2(rng, key, shape):
@@ -356,6 +406,8 @@ def random_rtdetr_weights(cfg: RtdetrConfig, seed: int = 0):
     for key, shape in rtdetr_param_shapes(cfg):
         if mbv3 and key.startswith("backbone."):
             a = _draw_mbv3(rng, key, shape)
+        elif cfg.backbone == "MobileNetV3_Small" and key.startswith("backbone."):
+            a = _draw_mbv3s(rng, key, shape)
         elif cfg.backbone == "ghostnetv2" and key.startswith("backbone."):
             a = _draw_ghostv2(rng, key, shape)
         elif key.endswith("running_mean"):
