@@ -207,6 +207,14 @@ int spe_model_create(const spe_model_config* cfg, spe_model** out);
  * Everything after src (stages, u8 crops, attention maps, outputs) is the same for both. */
 enum { SPE_BACKBONE_RESNET50_S8 = 0, SPE_BACKBONE_RESNET50_S16 = 1 };
 int spe_model_create_backbone(const spe_model_config* cfg, int backbone, spe_model** out);
+/* The same with a flags word (additive, ABI 9; flags == 0 is spe_model_create_backbone):
+ *   SPE_MODEL_PRE_NORM  the reference's --pre_norm transformer (REV/models/transformer.py forward_pre of both layer
+ *                       classes): every LayerNorm in front of its sub-block, the encoder closed by
+ *                       transformer.encoder.norm.{weight,bias} (two more keys, after the encoder layers': 414 / 410).
+ *                       dtypes BF16_ (attn_dtype F16_ included), F32_, F32X3_ and F32X6_; F32H3_ is refused with
+ *                       SPE_E_ARG (its activation-scale ledger rests on post-norm LayerNorm output bounds). */
+enum { SPE_MODEL_PRE_NORM = 1 };
+int spe_model_create_flags(const spe_model_config* cfg, int backbone, int flags, spe_model** out);
 void spe_model_destroy(spe_model* m);
 int spe_model_set_param(spe_model* m, const char* key, const float* host_data, int64_t numel);
 int spe_model_num_params(const spe_model* m);                 /* number of required keys */
@@ -501,6 +509,18 @@ int spe_debug_layernorm(void* stream, int dtype, const void* x, const float* gam
 int spe_debug_ffn(void* stream, const void* x, int ldx, const void* w1, int ld1, const float* b1, const void* w2,
                   int ld2, const float* b2, const float* gamma, const float* beta, void* y, int ldy, int M, int D,
                   int F, float* partial, int splits);
+/* the pre-norm forms of the two fused bf16 encoder kernels (SPE_MODEL_PRE_NORM).
+ * ffn_pre: n = LayerNorm(x; gamma, beta) on chip (fp32 statistics, n rounded to bf16), y = x + W2 relu(W1 n + b1)
+ * + b2 (bf16; x and y may alias), and beside it y2 = LayerNorm(y as stored; gamma2, beta2) (y2 nullable; row
+ * stride ldy; not x) and, with pos ([pos_period][256] bf16) and ypos, ypos = y2 + pos[m % pos_period] (needs y2).
+ * Other arguments as spe_debug_ffn.
+ * oproj_pre: C = R + A . W^T + bias, bf16, K = N = 256, W [256][ldb], no LayerNorm; C may alias R. */
+int spe_debug_ffn_pre(void* stream, const void* x, int ldx, const void* w1, int ld1, const float* b1, const void* w2,
+                      int ld2, const float* b2, const float* gamma, const float* beta, void* y, int ldy, int M, int D,
+                      int F, float* partial, int splits, const float* gamma2, const float* beta2, void* y2,
+                      const void* pos, int pos_period, void* ypos);
+int spe_debug_oproj_pre(void* stream, const void* A, int lda, const void* W, int ldb, const float* bias, const void* R,
+                        int ldr, void* C, int ldc, int M);
 /* xattn (bf16 only, the decoder cross-attention against the memory): for image b, query q and
  * head h, u[b*Q+q][h*256 .. +256] = softmax_t(q'[b*Q+q][h*256 ..] . k[b*T+t]) . v[b*T+t] with the
  * scores already in the exp2 domain (k = memory + pos, v = memory, rows of 256).  wv non-null

@@ -126,6 +126,34 @@ int spe_debug_layernorm(void* stream, int dtype, const void* x, const float* gam
   return rc < 0 ? spe_fail(SPE_E_LAUNCH, "layernorm launch rejected its arguments") : rc;
 }
 
+int spe_debug_ffn_pre(void* stream, const void* x, int ldx, const void* w1, int ld1, const float* b1, const void* w2,
+                      int ld2, const float* b2, const float* gamma, const float* beta, void* y, int ldy, int M, int D,
+                      int F, float* partial, int splits, const float* gamma2, const float* beta2, void* y2,
+                      const void* pos, int pos_period, void* ypos) {
+  FfnArgs a{};
+  a.x = x; a.ldx = ldx; a.w1 = w1; a.ld1 = ld1; a.b1 = b1; a.w2 = w2; a.ld2 = ld2; a.b2 = b2;
+  a.gamma = gamma; a.beta = beta; a.y = y; a.ldy = ldy; a.M = M; a.D = D; a.F = F;
+  if (ld2 == 0) {                               // w2 chunk-packed [F/32][256][32]
+    a.w2_chunked = 1;
+    a.ld2 = F;
+  }
+  a.partial = partial; a.splits = splits;
+  a.gamma2 = gamma2; a.beta2 = beta2; a.y2 = y2;
+  a.pos = pos; a.pos_period = pos_period; a.ypos = ypos;
+  const int rc = spe_launch_ffn_pre(a, (hipStream_t)stream);
+  return rc < 0 ? spe_fail(SPE_E_ARG, "ffn_pre launch rejected its arguments") : rc;
+}
+
+int spe_debug_oproj_pre(void* stream, const void* A, int lda, const void* W, int ldb, const float* bias, const void* R,
+                        int ldr, void* C, int ldc, int M) {
+  GemmArgs g{};
+  g.A = A; g.lda = lda; g.B = W; g.ldb = ldb; g.M = M; g.N = 256; g.K = 256;
+  g.bias = bias; g.R = R; g.ldr = ldr; g.C = C; g.ldc = ldc;
+  const int rc = spe_launch_lnproj_pre(g, (hipStream_t)stream);
+  if (rc == 1) return spe_fail(SPE_E_LAUNCH, "shape not served by the pre-norm out-projection kernel");
+  return rc < 0 ? spe_fail(SPE_E_LAUNCH, "oproj_pre launch rejected its arguments") : rc;
+}
+
 int spe_debug_ffn(void* stream, const void* x, int ldx, const void* w1, int ld1, const float* b1, const void* w2,
                   int ld2, const float* b2, const float* gamma, const float* beta, void* y, int ldy, int M, int D,
                   int F, float* partial, int splits) {

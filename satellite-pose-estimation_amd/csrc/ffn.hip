@@ -177,9 +177,127 @@ SPE_DEV void ffn_epilogue(const FfnArgs& a, f32x4 (&acc)[16][MB], int m0, int g,
   }
 }
 
+// Pre-norm prologue (REV/models/transformer.py forward_pre): the wave's x rows, already held as B fragments,
+// become n = LayerNorm(x) with (a.gamma, a.beta): fp32 statistics over the row's 256 columns (64 in this lane,
+// the rest in the three lanes c16 + 16 g'), n rounded to bf16 as a LayerNorm launch would store it.  Rows past
+// M hold zeros and normalise to beta (finite; never stored).
+template <int MB>
+SPE_DEV void ffn_prenorm_rows(const FfnArgs& a, bf16x8 (&xf)[MB][8], int g) {
+#pragma unroll
+  for (int mb = 0; mb < MB; ++mb) {
+    float v[8][8];
+    float s = 0.f;
+#pragma unroll
+    for (int ks = 0; ks < 8; ++ks) {
+      const u32x4 u = __builtin_bit_cast(u32x4, xf[mb][ks]);
+#pragma unroll
+      for (int p = 0; p < 4; ++p) {
+        v[ks][2 * p] = __uint_as_float(u[p] << 16);
+        v[ks][2 * p + 1] = __uint_as_float(u[p] & 0xffff0000u);
+        s += v[ks][2 * p] + v[ks][2 * p + 1];
+      }
+    }
+    s += __shfl_xor(s, 16, 64);
+    s += __shfl_xor(s, 32, 64);
+    const float mean = s * (1.f / D);
+    float q = 0.f;
+#pragma unroll
+    for (int ks = 0; ks < 8; ++ks)
+#pragma unroll
+      for (int e = 0; e < 8; ++e) q += (v[ks][e] - mean) * (v[ks][e] - mean);
+    q += __shfl_xor(q, 16, 64);
+    q += __shfl_xor(q, 32, 64);
+    const float rs = rsqrtf(q * (1.f / D) + 1e-5f);
+#pragma unroll
+    for (int ks = 0; ks < 8; ++ks) {
+      const int n = 32 * ks + 8 * g;
+      const f32x4 ga = *reinterpret_cast<const f32x4*>(a.gamma + n), gb = *reinterpret_cast<const f32x4*>(a.gamma + n + 4);
+      const f32x4 ba = *reinterpret_cast<const f32x4*>(a.beta + n), bb = *reinterpret_cast<const f32x4*>(a.beta + n + 4);
+      float o[8];
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        o[e] = (v[ks][e] - mean) * rs * ga[e] + ba[e];
+        o[4 + e] = (v[ks][4 + e] - mean) * rs * gb[e] + bb[e];
+      }
+      xf[mb][ks] = __builtin_bit_cast(bf16x8, u32x4{pack_bf16x2(o[0], o[1]), pack_bf16x2(o[2], o[3]),
+                                                    pack_bf16x2(o[4], o[5]), pack_bf16x2(o[6], o[7])});
+    }
+  }
+}
+
+// Pre-norm epilogue: y = s' = x + acc + b2 (the residual stream, bf16), and beside it y2 = LayerNorm(s') with
+// the second affine (a.gamma2, a.beta2) -- the next layer's norm1, or encoder.norm after the last layer -- over
+// the ROUNDED s', as a LayerNorm launch reading y would compute it; ypos = y2 + pos (before y2's rounding, as the
+// post-norm form).  y == x is safe: a lane reads all of its row's residual before its first store.
+template <int MB>
+SPE_DEV void ffn_epilogue_pre(const FfnArgs& a, f32x4 (&acc)[16][MB], int m0, int g, int c16) {
+#pragma unroll
+  for (int mb = 0; mb < MB; ++mb) {
+    const int m = m0 + 16 * mb + c16;
+    const bool live = m < a.M;
+    const bf16* xr = (const bf16*)a.x + (size_t)(live ? m : 0) * a.ldx;
+    float s = 0.f;
+#pragma unroll
+    for (int nb = 0; nb < 16; ++nb) {
+      const int n = 16 * nb + 4 * g;
+      const f32x4 b2 = *reinterpret_cast<const f32x4*>(a.b2 + n);
+      const u32x2 rv = live ? ld8(xr + n) : u32x2{0, 0};
+      const float r0 = __uint_as_float(rv.x << 16), r1 = __uint_as_float(rv.x & 0xffff0000u);
+      const float r2 = __uint_as_float(rv.y << 16), r3 = __uint_as_float(rv.y & 0xffff0000u);
+      // s' rounded to bf16 here and kept as floats (packing them again for the store is exact)
+      const uint32_t s01 = pack_bf16x2(acc[nb][mb][0] + (b2[0] + r0), acc[nb][mb][1] + (b2[1] + r1));
+      const uint32_t s23 = pack_bf16x2(acc[nb][mb][2] + (b2[2] + r2), acc[nb][mb][3] + (b2[3] + r3));
+      acc[nb][mb][0] = __uint_as_float(s01 << 16);
+      acc[nb][mb][1] = __uint_as_float(s01 & 0xffff0000u);
+      acc[nb][mb][2] = __uint_as_float(s23 << 16);
+      acc[nb][mb][3] = __uint_as_float(s23 & 0xffff0000u);
+      s += acc[nb][mb][0] + acc[nb][mb][1] + acc[nb][mb][2] + acc[nb][mb][3];
+    }
+    s += __shfl_xor(s, 16, 64);
+    s += __shfl_xor(s, 32, 64);
+    const float mean = s * (1.f / D);
+    float q = 0.f;
+#pragma unroll
+    for (int nb = 0; nb < 16; ++nb)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const float dv = acc[nb][mb][r] - mean;
+        q += dv * dv;
+      }
+    q += __shfl_xor(q, 16, 64);
+    q += __shfl_xor(q, 32, 64);
+    const float rs = rsqrtf(q * (1.f / D) + 1e-5f);
+    if (!live) continue;
+    bf16* yr = (bf16*)a.y + (size_t)m * a.ldy;
+#pragma unroll
+    for (int nb = 0; nb < 16; ++nb)
+      st8(yr + 16 * nb + 4 * g, u32x2{pack_bf16x2(acc[nb][mb][0], acc[nb][mb][1]), pack_bf16x2(acc[nb][mb][2], acc[nb][mb][3])});
+    if (!a.y2) continue;
+    bf16* y2r = (bf16*)a.y2 + (size_t)m * a.ldy;
+    const bf16* pr = a.ypos ? (const bf16*)a.pos + (size_t)(m % a.pos_period) * D : nullptr;
+    bf16* ypr = a.ypos ? (bf16*)a.ypos + (size_t)m * a.ldy : nullptr;
+#pragma unroll
+    for (int nb = 0; nb < 16; ++nb) {
+      const int n = 16 * nb + 4 * g;
+      const f32x4 ga = *reinterpret_cast<const f32x4*>(a.gamma2 + n);
+      const f32x4 be = *reinterpret_cast<const f32x4*>(a.beta2 + n);
+      float o[4];
+#pragma unroll
+      for (int r = 0; r < 4; ++r) o[r] = (acc[nb][mb][r] - mean) * rs * ga[r] + be[r];
+      st8(y2r + n, u32x2{pack_bf16x2(o[0], o[1]), pack_bf16x2(o[2], o[3])});
+      if (ypr) {
+        const u32x2 pv = ld8(pr + n);
+        st8(ypr + n, u32x2{pack_bf16x2(o[0] + __uint_as_float(pv.x << 16), o[1] + __uint_as_float(pv.x & 0xffff0000u)),
+                           pack_bf16x2(o[2] + __uint_as_float(pv.y << 16), o[3] + __uint_as_float(pv.y & 0xffff0000u))});
+      }
+    }
+  }
+}
+
 // MB = 16-row MFMA blocks per wave (rows per wave = 16 MB, per block = 64 MB): more rows per
 // wave = more MFMA work per byte of weights read from LDS (every wave reads the whole chunk).
-template <int MB, int NSTAGE = 3>
+// PN: the pre-norm form (ffn_prenorm_rows in front, ffn_epilogue_pre behind)
+template <int MB, int NSTAGE = 3, bool PN = false>
 __global__ __launch_bounds__(NT, 1) void ffn_ln_kernel(FfnArgs a) {
   constexpr int RB = 64 * MB;           // rows per block
   // one LDS array (a second __shared__ object beside in-flight global_load_lds can make the
@@ -207,6 +325,7 @@ __global__ __launch_bounds__(NT, 1) void ffn_ln_kernel(FfnArgs a) {
     for (int ks = 0; ks < 8; ++ks)
       xf[mb][ks] = __builtin_bit_cast(bf16x8, m < a.M ? ld16(xr + 32 * ks + 8 * g) : u32x4{0, 0, 0, 0});
   }
+  if constexpr (PN) ffn_prenorm_rows<MB>(a, xf, g);
   f32x4 acc[16][MB];
 #pragma unroll
   for (int nb = 0; nb < 16; ++nb)
@@ -304,7 +423,8 @@ __global__ __launch_bounds__(NT, 1) void ffn_ln_kernel(FfnArgs a) {
     return;
   }
 
-  ffn_epilogue<MB>(a, acc, m0, g, c16);
+  if constexpr (PN) ffn_epilogue_pre<MB>(a, acc, m0, g, c16);
+  else ffn_epilogue<MB>(a, acc, m0, g, c16);
 }
 
 // Cross-chunk software pipeline (encoder FFN, many rows): step c multiplies phase 2 of chunk c
@@ -317,7 +437,7 @@ __global__ __launch_bounds__(NT, 1) void ffn_ln_kernel(FfnArgs a) {
 // pinned by sched_barrier: otherwise the compiler hoists every read to the top of the step and
 // the one wave per SIMD waits for all 32 KiB of them before its MFMAs can run.
 // PRE = reads issued ahead of the first MFMA (then one per MFMA triple).
-template <int MB, bool SCHED = false, int PRE = 6>
+template <int MB, bool SCHED = false, int PRE = 6, bool PN = false>
 __global__ __launch_bounds__(NT, 1) void ffn_pipe_kernel(FfnArgs a) {
   constexpr int NST = 4;
   __shared__ __attribute__((aligned(1024))) char lds[NST * STAGE + FMAX * 4];
@@ -338,6 +458,7 @@ __global__ __launch_bounds__(NT, 1) void ffn_pipe_kernel(FfnArgs a) {
     for (int ks = 0; ks < 8; ++ks)
       xf[mb][ks] = __builtin_bit_cast(bf16x8, m < a.M ? ld16(xr + 32 * ks + 8 * g) : u32x4{0, 0, 0, 0});
   }
+  if constexpr (PN) ffn_prenorm_rows<MB>(a, xf, g);
   f32x4 acc[16][MB];
 #pragma unroll
   for (int nb = 0; nb < 16; ++nb)
@@ -511,7 +632,8 @@ __global__ __launch_bounds__(NT, 1) void ffn_pipe_kernel(FfnArgs a) {
 #pragma unroll
   for (int i = 0; i < 16 * MB; ++i) p2(i);
 
-  ffn_epilogue<MB>(a, acc, m0, g, c16);
+  if constexpr (PN) ffn_epilogue_pre<MB>(a, acc, m0, g, c16);
+  else ffn_epilogue<MB>(a, acc, m0, g, c16);
 }
 
 // split-F finish: y = LN(x + sum_s partial[s] + b2) (+ pos copy), one wave per row
@@ -534,6 +656,40 @@ __global__ __launch_bounds__(256) void ffn_reduce_ln_kernel(FfnArgs a) {
 #pragma unroll
   for (int r = 0; r < 4; ++r) o[r] = (v[r] - mean) * rs * ga[r] + be[r];
   st8((bf16*)a.y + (size_t)m * a.ldy + n, u32x2{pack_bf16x2(o[0], o[1]), pack_bf16x2(o[2], o[3])});
+  if (a.ypos) {
+    const u32x2 pv = ld8((const bf16*)a.pos + (size_t)(m % a.pos_period) * D + n);
+    st8((bf16*)a.ypos + (size_t)m * a.ldy + n,
+        u32x2{pack_bf16x2(o[0] + __uint_as_float(pv.x << 16), o[1] + __uint_as_float(pv.x & 0xffff0000u)),
+              pack_bf16x2(o[2] + __uint_as_float(pv.y << 16), o[3] + __uint_as_float(pv.y & 0xffff0000u))});
+  }
+}
+
+// split-F finish of the pre-norm form: y = s' = x + sum_s partial[s] + b2, y2 = LN(s' as stored) with
+// (gamma2, beta2), ypos = y2 + pos; one wave per row
+__global__ __launch_bounds__(256) void ffn_reduce_pre_kernel(FfnArgs a) {
+  const int lane = threadIdx.x & 63, m = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (m >= a.M) return;
+  const int n = 4 * lane;
+  f32x4 v = *reinterpret_cast<const f32x4*>(a.b2 + n);
+  for (int s = 0; s < a.splits; ++s) v += *reinterpret_cast<const f32x4*>(a.partial + ((size_t)s * a.M + m) * D + n);
+  const u32x2 rv = ld8((const bf16*)a.x + (size_t)m * a.ldx + n);
+  v[0] += __uint_as_float(rv.x << 16); v[1] += __uint_as_float(rv.x & 0xffff0000u);
+  v[2] += __uint_as_float(rv.y << 16); v[3] += __uint_as_float(rv.y & 0xffff0000u);
+  const u32x2 sv{pack_bf16x2(v[0], v[1]), pack_bf16x2(v[2], v[3])};
+  st8((bf16*)a.y + (size_t)m * a.ldy + n, sv);
+  if (!a.y2) return;
+  v[0] = __uint_as_float(sv.x << 16); v[1] = __uint_as_float(sv.x & 0xffff0000u);
+  v[2] = __uint_as_float(sv.y << 16); v[3] = __uint_as_float(sv.y & 0xffff0000u);
+  const float mean = wave_sum(v[0] + v[1] + v[2] + v[3]) * (1.f / D);
+  float q = 0.f;
+#pragma unroll
+  for (int r = 0; r < 4; ++r) q += (v[r] - mean) * (v[r] - mean);
+  const float rs = rsqrtf(wave_sum(q) * (1.f / D) + 1e-5f);
+  const f32x4 ga = *reinterpret_cast<const f32x4*>(a.gamma2 + n), be = *reinterpret_cast<const f32x4*>(a.beta2 + n);
+  float o[4];
+#pragma unroll
+  for (int r = 0; r < 4; ++r) o[r] = (v[r] - mean) * rs * ga[r] + be[r];
+  st8((bf16*)a.y2 + (size_t)m * a.ldy + n, u32x2{pack_bf16x2(o[0], o[1]), pack_bf16x2(o[2], o[3])});
   if (a.ypos) {
     const u32x2 pv = ld8((const bf16*)a.pos + (size_t)(m % a.pos_period) * D + n);
     st8((bf16*)a.ypos + (size_t)m * a.ldy + n,
@@ -630,6 +786,50 @@ int spe_launch_ffn_ln(const FfnArgs& a0, hipStream_t s) {
     else if (mb == 3) hipLaunchKernelGGL(ffn_ln_kernel<3>, dim3((a.M + 191) / 192), dim3(NT), 0, s, a);
     else if (mb == 4) hipLaunchKernelGGL(ffn_ln_kernel<4>, dim3((a.M + 255) / 256), dim3(NT), 0, s, a);
     else hipLaunchKernelGGL(ffn_ln_kernel<2>, dim3((a.M + 127) / 128), dim3(NT), 0, s, a);
+  }
+  return (int)hipGetLastError();
+}
+
+// The pre-norm form (FfnArgs::pre): the same launch forms as spe_launch_ffn_ln -- whole rounds of 192-row tiles
+// with a 128-row tail launch, the 128- and 256-row kernels behind SPE_FFN_MB, split-F + reduce for few rows --
+// on the PN instantiations, with the pinned schedule (SCHED, 6 reads ahead) only.
+int spe_launch_ffn_pre(const FfnArgs& a0, hipStream_t s) {
+  FfnArgs a = a0;
+  a.row0 = 0;
+  a.pre = 1;
+  if (a.M <= 0) return 0;
+  if (!a.gamma || !a.beta || !a.y || (a.y2 && (!a.gamma2 || !a.beta2)) || a.y2 == a.x || a.ypos == a.x) return -5;
+  if (a.ypos && (!a.y2 || !a.pos || a.pos_period <= 0)) return -5;
+  if (a.D != D || a.F % HC || a.F > FMAX || (a.ldx % 8) || (a.ldy % 8) || (a.ld1 % 8) || (a.ld2 % 8)) return -5;
+  if (!a.partial) a.splits = 1;
+  if (a.partial && (a.splits < 1 || (a.F / HC) % a.splits)) return -5;
+  if (a.partial && a.splits > 1) {
+    const int tiles = (a.M + BM - 1) / BM;
+    hipLaunchKernelGGL((ffn_ln_kernel<2, 3, true>), dim3(tiles * a.splits), dim3(NT), 0, s, a);
+    hipLaunchKernelGGL(ffn_reduce_pre_kernel, dim3((a.M + 3) / 4), dim3(256), 0, s, a);
+    return (int)hipGetLastError();
+  }
+  a.partial = nullptr;
+  static const int mb = spe_env_int("SPE_FFN_MB", 3);
+  if (mb == 3 && a.F / HC >= 2) {
+    static const int tail = spe_env_int("SPE_FFN_TAIL", 1);
+    const int tiles = (a.M + 191) / 192, ncu = spe_cu_count();
+    const int full = ncu > 0 ? tiles / ncu * ncu : 0, rest = a.M - full * 192;
+    if (tail && full > 0 && rest > 0 && (rest + 127) / 128 <= ncu) {
+      hipLaunchKernelGGL((ffn_pipe_kernel<3, true, 6, true>), dim3(full), dim3(NT), 0, s, a);
+      a.row0 = full * 192;
+      hipLaunchKernelGGL((ffn_pipe_kernel<2, true, 6, true>), dim3((rest + 127) / 128), dim3(NT), 0, s, a);
+    } else {
+      hipLaunchKernelGGL((ffn_pipe_kernel<3, true, 6, true>), dim3(tiles), dim3(NT), 0, s, a);
+    }
+  } else if (mb == 2 && a.F / HC >= 2) {
+    hipLaunchKernelGGL((ffn_pipe_kernel<2, true, 6, true>), dim3((a.M + 127) / 128), dim3(NT), 0, s, a);
+  } else if (mb == 4) {
+    hipLaunchKernelGGL((ffn_ln_kernel<4, 3, true>), dim3((a.M + 255) / 256), dim3(NT), 0, s, a);
+  } else if (mb == 3) {
+    hipLaunchKernelGGL((ffn_ln_kernel<3, 4, true>), dim3((a.M + 191) / 192), dim3(NT), 0, s, a);
+  } else {
+    hipLaunchKernelGGL((ffn_ln_kernel<2, 3, true>), dim3((a.M + 127) / 128), dim3(NT), 0, s, a);
   }
   return (int)hipGetLastError();
 }

@@ -401,14 +401,15 @@ EncAttn enc_attn_forms(const Fwd& f) {
   return a;
 }
 
-// q/k and V^T projections + self-attention of src into ao; the attention output's scale slot is o_amax
-int enc_self_attention(Fwd& f, const Enc& e, const EncAttn& ea, const float* src_amax, float* o_amax) {
+// q/k and V^T projections + self-attention of x (src; a pre-norm model's norm1(src)) into ao; the attention
+// output's scale slot is o_amax
+int enc_self_attention(Fwd& f, const Enc& e, const EncAttn& ea, const void* x, const float* src_amax, float* o_amax) {
   spe_model* m = f.m;
   const Ws& w = f.w;
   hipStream_t s = f.s;
   const int B = f.B, T = f.T, d = f.d, Mt = f.Mt;
   {
-    GemmArgs g = linear_args(e.qk, f.P(w.src), d, Mt, f.P(w.qkv), 3 * d);
+    GemmArgs g = linear_args(e.qk, x, d, Mt, f.P(w.qkv), 3 * d);
     g.out_f16 = ea.f16attn;
     g.amax_a = src_amax;
     if (ea.presplit) { g.S = f.P(w.kpl); g.s_col0 = d; }
@@ -416,7 +417,7 @@ int enc_self_attention(Fwd& f, const Enc& e, const EncAttn& ea, const float* src
     CK(run_gemm(m, "gemm.enc.qk", g, mode, s));
   }
   {
-    GemmArgs g = linear_args(e.v, f.P(w.src), d, Mt, f.P(w.vt), 8);
+    GemmArgs g = linear_args(e.v, x, d, Mt, f.P(w.vt), 8);
     g.vt_T = T; g.vt_B = B; g.vt_swz = ea.vt_swz;
     // the attention output is a convex combination of V rows: max |V| bounds it
     g.amax_a = src_amax; g.amax_c = o_amax;
@@ -462,7 +463,7 @@ int encoder_layer(Fwd& f, const Enc& e, int li, const EncAttn& ea, const float**
   hipStream_t s = f.s;
   const int d = f.d, ff = f.ff, Mt = f.Mt;
   float* const o_amax = f.slot(SPE_AMAX_BB + 2 * li);
-  TRY(enc_self_attention(f, e, ea, *src_amax, o_amax));
+  TRY(enc_self_attention(f, e, ea, f.P(w.src), *src_amax, o_amax));
   if (f.tap && f.tap->enc_map && f.tap->enc_layer == li) TRY(enc_attn_map(f, ea, f.tap->enc_map));
   {
     // out-proj + residual; bf16 large batches fuse norm1 into the GEMM epilogue, in place over src
@@ -502,6 +503,85 @@ int encoder_layer(Fwd& f, const Enc& e, int li, const EncAttn& ea, const float**
                     f.slot(SPE_AMAX_BB + 2 * li + 1), f.P(w.tmp), e.n2g, e.n2b));
   }
   *src_amax = e.n2_bound;
+  return 0;
+}
+
+// ---------------- pre-norm encoder (REV/models/transformer.py forward_pre, TransformerEncoder.forward)
+//
+// The residual stream s lives in src (the backbone writes it there); its normed copy n lives in nrm.  Per layer
+//     n = norm1(s); q = k = n + pos; s += out_proj(attn(q, k, n)); s += linear2(relu(linear1(norm2(s))))
+// and after the last layer memory = encoder.norm(s), again in nrm: every reader of the memory (the cross K / V
+// projections, xattn.hip) takes nrm in a pre-norm model where it takes src in a post-norm one.
+//   bf16: per layer the post-norm model's five kinds -- gemm.enc.qk, gemm.enc.v, attn.enc, gemm.enc.o (lnproj.hip's
+//         form without the LayerNorm, in place over s) and ffn.enc (ffn.hip's pre form: norm2 on chip, and the NEXT
+//         consumer's LayerNorm -- the next layer's norm1 or encoder.norm -- stored beside s, so only layer 0's norm1
+//         is a launch of its own, one ln.enc in front).
+//   fp32 modes: GEMM + LayerNorm launches; the out-projection writes s into tmp, linear2 back into src.
+int encoder_layer_pre(Fwd& f, const Enc& e, int li, const EncAttn& ea) {
+  spe_model* m = f.m;
+  const Ws& w = f.w;
+  hipStream_t s = f.s;
+  const int d = f.d, Mt = f.Mt;
+  const bool last = &e == &m->enc.back();
+  const float* ng = last ? m->eng : m->enc[li + 1].n1g;   // the LayerNorm the next reader of s applies
+  const float* nb = last ? m->enb : m->enc[li + 1].n1b;
+  TRY(enc_self_attention(f, e, ea, f.P(w.nrm), nullptr, nullptr));
+  if (f.tap && f.tap->enc_map && f.tap->enc_layer == li) TRY(enc_attn_map(f, ea, f.tap->enc_map));
+  size_t cur = w.src;
+  {
+    GemmArgs g = linear_args(e.o, f.P(w.ao), d, Mt, f.P(w.src), d);
+    g.R = f.P(w.src); g.ldr = d;
+    if (m->esz == 2 && spe_lnproj_pre_applies(g)) {
+      const double by = ((double)Mt * d * 3 + (double)d * d) * m->esz;
+      CK(run_other(m, "gemm.enc.o", 2.0 * Mt * d * d, by, s, [&] { return spe_launch_lnproj_pre(g, s); }));
+    } else {
+      g.C = f.P(w.tmp);
+      CK(run_gemm(m, "gemm.enc.o", g, GEMM_LINEAR, s));
+      cur = w.tmp;
+    }
+  }
+  if (use_fused_ffn(m)) {
+    CK(run_ffn_pre(m, "ffn.enc", e.l1, e.l2, e.n2g, e.n2b, f.P(cur), f.P(w.src), ng, nb, f.P(w.nrm), Mt, s,
+                   last ? m->pos : nullptr, last ? f.P(w.srcpos) : nullptr, f.T, nullptr, e.ffn_w2c));
+    return 0;
+  }
+  CK(run_layernorm(m, "ln.enc", f.P(cur), e.n2g, e.n2b, f.P(w.nrm), nullptr, Mt, d, f.dt, s));
+  {
+    GemmArgs g = linear_args(e.l1, f.P(w.nrm), d, Mt, f.P(w.ffn), f.ff);
+    g.act = ACT_RELU;
+    CK(run_gemm(m, "gemm.enc.ffn1", g, GEMM_LINEAR, s));
+  }
+  {
+    // (cur is tmp here: only a bf16 model takes the in-place out-projection, and every bf16 model the fused FFN)
+    GemmArgs g = linear_args(e.l2, f.P(w.ffn), f.ff, Mt, f.P(w.src), d);
+    g.R = f.P(cur); g.ldr = d;
+    CK(run_gemm(m, "gemm.enc.ffn2", g, GEMM_LINEAR, s));
+  }
+  CK(run_layernorm(m, "ln.enc", f.P(w.src), ng, nb, f.P(w.nrm), nullptr, Mt, d, f.dt, s));
+  return 0;
+}
+
+int encoder_stage_pre(Fwd& f) {
+  spe_model* m = f.m;
+  const Ws& w = f.w;
+  hipStream_t s = f.s;
+  const int B = f.B, T = f.T, d = f.d, L = f.L, Mt = f.Mt;
+  const EncAttn ea = enc_attn_forms(f);
+  // layer 0's norm1(src); without encoder layers the memory is encoder.norm(src)
+  CK(run_layernorm(m, "ln.enc", f.P(w.src), m->enc.empty() ? m->eng : m->enc[0].n1g,
+                   m->enc.empty() ? m->enb : m->enc[0].n1b, f.P(w.nrm), nullptr, Mt, d, f.dt, s));
+  int li = 0;
+  for (const Enc& e : m->enc) TRY(encoder_layer_pre(f, e, li++, ea));
+  if (spe_use_xattn(m)) return 0;               // (bf16: the last FFN wrote memory + pos into srcpos)
+  {
+    const bool have_srcpos = use_fused_ffn(m) && !m->enc.empty();
+    GemmArgs g = linear_args(m->crossK, f.P(have_srcpos ? w.srcpos : w.nrm), d, Mt, f.P(w.ck), L * d);
+    const int mode = have_srcpos ? GEMM_LINEAR : add_pos(m, g, m->pos, d, T, m->pos_crossK, L * d);
+    CK(run_gemm(m, "gemm.cross_kv", g, mode, s));
+  }
+  GemmArgs g = linear_args(m->crossV, f.P(w.nrm), d, Mt, f.P(w.cvt), 8);
+  g.vt_T = T; g.vt_B = B;
+  CK(run_gemm(m, "gemm.cross_kv", g, GEMM_LINEAR, s));
   return 0;
 }
 
@@ -790,9 +870,10 @@ int dec_ffn_block(Fwd& f, const Dec& e, int l, const float* tgt_amax) {
 // the shared decoder_norm (REV/models/transformer.py:117-124) of tgt into hs, then the heads
 // (REV/models/detr_speed.py:83-99); the final call also runs the sigma head and the fused PostProcess
 // (REV/models/detr_speed.py:83-92,266-293), an aux layer's writes logits and points only
-int run_heads(Fwd& f, float* hs, float* logits, float* points, bool final, const spe_forward_outputs& out) {
+int run_heads(Fwd& f, const void* tgt, float* hs, float* logits, float* points, bool final,
+              const spe_forward_outputs& out) {
   spe_model* m = f.m;
-  CK(run_layernorm(m, "ln.dec", f.P(f.w.tgt), m->dng, m->dnb, nullptr, hs, f.Mq, f.d, f.dt, f.s));
+  CK(run_layernorm(m, "ln.dec", tgt, m->dng, m->dnb, nullptr, hs, f.Mq, f.d, f.dt, f.s));
   HeadArgs h = m->head;
   h.hs = hs; h.B = f.B; h.Q = f.Q;
   h.logits = logits; h.points = points;
@@ -827,10 +908,118 @@ int decoder_stage(Fwd& f, const spe_forward_outputs& out) {
     TRY(dec_ffn_block(f, e, l, tgt_amax));
     if (m->h3) tgt_amax = e.n3_bound;
     if (out.aux_logits && out.aux_points && l + 1 < L)   // aux output of layer l, into the aux slices
-      TRY(run_heads(f, (float*)f.P(f.w.hs), out.aux_logits + (size_t)l * Mq * 12, out.aux_points + (size_t)l * Mq * 2,
-                    false, out));
+      TRY(run_heads(f, f.P(f.w.tgt), (float*)f.P(f.w.hs), out.aux_logits + (size_t)l * Mq * 12,
+                    out.aux_points + (size_t)l * Mq * 2, false, out));
   }
-  CK(run_heads(f, out.hs ? out.hs : (float*)f.P(f.w.hs), out.logits, out.points, true, out));
+  CK(run_heads(f, f.P(f.w.tgt), out.hs ? out.hs : (float*)f.P(f.w.hs), out.logits, out.points, true, out));
+  return 0;
+}
+
+// ---------------- pre-norm decoder (REV/models/transformer.py forward_pre of TransformerDecoderLayer)
+//
+//     n = norm1(t); q = k = n + query_pos; t += self_attn(q, k, n)
+//     t += cross_attn(norm2(t) + query_pos, memory + pos, memory);  t += ffn(norm3(t))
+// from kernels that exist, in every mode: a LayerNorm launch into dnrm in front of each sub-block, the
+// projections as GEMMs (the bf16 folded cross-attention query projection keeps decsa.hip's kernel), the
+// attention kernels on the normed rows, and each out-projection / linear2 as a GEMM with the stream as its
+// residual.  The stream alternates between tgt and dtmp (three residual adds a layer); *cur names the buffer
+// that holds it.  The post-norm model's fused bf16 decoder kernels (decsa.hip) end in a LayerNorm and do not fit.
+int dec_residual_gemm(Fwd& f, const Conv& c, const void* a, int lda, size_t* cur) {
+  const Ws& w = f.w;
+  const size_t out = *cur == w.tgt ? w.dtmp : w.tgt;
+  GemmArgs g = linear_args(c, a, lda, f.Mq, f.P(out), f.d);
+  g.R = f.P(*cur); g.ldr = f.d;
+  CK(run_gemm(f.m, "gemm.dec", g, GEMM_LINEAR, f.s));
+  *cur = out;
+  return 0;
+}
+
+int decoder_layer_pre(Fwd& f, const Dec& e, int l, size_t* cur) {
+  spe_model* m = f.m;
+  const Ws& w = f.w;
+  hipStream_t s = f.s;
+  const int B = f.B, Q = f.Q, T = f.T, d = f.d, L = f.L, Mq = f.Mq;
+  void* const n = f.P(w.dnrm);
+  // ---- self-attention
+  CK(run_layernorm(m, "ln.dec", f.P(*cur), e.n1g, e.n1b, n, nullptr, Mq, d, f.dt, s));
+  {
+    GemmArgs g = linear_args(e.sqk, n, d, Mq, f.P(w.dqkv), 3 * d);
+    const int mode = add_pos(m, g, m->qpos, d, Q, e.qpos_sqk, 2 * d);
+    CK(run_gemm(m, "gemm.dec", g, mode, s));
+  }
+  {
+    GemmArgs g = linear_args(e.sv, n, d, Mq, f.P(w.dvt), 8);
+    g.vt_T = Q; g.vt_B = B;
+    CK(run_gemm(m, "gemm.dec", g, GEMM_LINEAR, s));
+  }
+  {
+    AttnArgs a{};
+    a.q = f.P(w.dqkv); a.ldq = 3 * d;
+    a.k = (char*)f.P(w.dqkv) + d * m->esz; a.ldk = 3 * d;
+    a.vt = f.P(w.dvt);
+    a.o = f.P(w.dao); a.ldo = d;
+    a.B = B; a.H = m->cfg.nheads; a.Tq = Q; a.Tk = Q; a.scale = f.scale;
+    CK(run_attn(m, "attn.dec_self", a, f.dt, s));
+  }
+  TRY(dec_residual_gemm(f, e.so, f.P(w.dao), d, cur));
+  // ---- cross-attention
+  CK(run_layernorm(m, "ln.dec", f.P(*cur), e.n2g, e.n2b, n, nullptr, Mq, d, f.dt, s));
+  if (spe_use_xattn(m)) {
+    // bf16, against the memory itself: q' = (n + query_pos) . Wqk^T + bqk, the memory in nrm, memory + pos in srcpos
+    if (e.fxq && decffn_on()) {
+      DecQArgs qa{};
+      qa.x = n; qa.ldx = d; qa.M = Mq; qa.N = 8 * d;
+      qa.w = e.fxq; qa.bias = e.xq.bias; qa.R = e.xq_r; qa.ldr = 8 * d; qa.period = Q;
+      qa.y = f.P(w.xq); qa.ldy = 8 * d;
+      CK(run_other(m, "gemm.dec", 2.0 * Mq * d * 8.0 * d, 2.0 * Mq * (d + 8.0 * d) * m->esz + 2.0 * 8 * d * d * m->esz, s,
+                   [&] { return spe_launch_decq(qa, s); }));
+    } else {
+      GemmArgs g = linear_args(e.xq, n, d, Mq, f.P(w.xq), 8 * d);
+      g.R = e.xq_r; g.ldr = 8 * d; g.r_period = Q;
+      CK(run_gemm(m, "gemm.dec", g, GEMM_LINEAR, s));
+    }
+    XattnArgs x = xattn_args(f, e, f.P(w.srcpos), d, f.P(w.nrm), d);
+    const double fl = 4.0 * B * 8.0 * Q * (double)T * d + 2.0 * Mq * 8.0 * d * 32;
+    const double by = 2.0 * B * (double)T * d * m->esz + 2.0 * Mq * 8.0 * d * m->esz;
+    CK(run_other(m, "attn.dec_cross", fl, by, s, [&] { return spe_launch_xattn(x, s); }));
+  } else {
+    {
+      GemmArgs g = linear_args(e.cq, n, d, Mq, f.P(w.dqc), d);
+      const int mode = add_pos(m, g, m->qpos, d, Q, e.qpos_cq, d);
+      CK(run_gemm(m, "gemm.dec", g, mode, s));
+    }
+    AttnArgs a{};
+    a.q = f.P(w.dqc); a.ldq = d;
+    a.k = (char*)f.P(w.ck) + (size_t)l * d * m->esz; a.ldk = L * d;
+    a.vt = (char*)f.P(w.cvt) + (size_t)l * B * d * T * m->esz;
+    a.o = f.P(w.dao); a.ldo = d;
+    a.B = B; a.H = m->cfg.nheads; a.Tq = Q; a.Tk = T; a.scale = f.scale;
+    CK(run_attn(m, "attn.dec_cross", a, f.dt, s));
+  }
+  if (f.tap && f.tap->dec_map && f.tap->dec_layer == l) TRY(dec_attn_map(f, l, f.tap->dec_map));
+  TRY(dec_residual_gemm(f, e.co, f.P(w.dao), d, cur));
+  // ---- FFN
+  CK(run_layernorm(m, "ln.dec", f.P(*cur), e.n3g, e.n3b, n, nullptr, Mq, d, f.dt, s));
+  {
+    GemmArgs g = linear_args(e.l1, n, d, Mq, f.P(w.dffn), f.ff);
+    g.act = ACT_RELU;
+    CK(run_gemm(m, "gemm.dec", g, GEMM_LINEAR, s));
+  }
+  return dec_residual_gemm(f, e.l2, f.P(w.dffn), f.ff, cur);
+}
+
+int decoder_stage_pre(Fwd& f, const spe_forward_outputs& out) {
+  spe_model* m = f.m;
+  const int L = f.L, Mq = f.Mq;
+  CK((int)hipMemsetAsync(f.P(f.w.tgt), 0, (size_t)Mq * f.d * m->esz, f.s));
+  size_t cur = f.w.tgt;
+  for (int l = 0; l < L; ++l) {
+    TRY(decoder_layer_pre(f, m->dec[l], l, &cur));
+    if (out.aux_logits && out.aux_points && l + 1 < L)
+      TRY(run_heads(f, f.P(cur), (float*)f.P(f.w.hs), out.aux_logits + (size_t)l * Mq * 12,
+                    out.aux_points + (size_t)l * Mq * 2, false, out));
+  }
+  CK(run_heads(f, f.P(cur), out.hs ? out.hs : (float*)f.P(f.w.hs), out.logits, out.points, true, out));
   return 0;
 }
 
@@ -861,8 +1050,8 @@ int forward_stages(spe_model* m, void* stream, const ImageSrc& images, int B, vo
   if (amx && (stages & SPE_STAGE_DECODE) && 3 * c.dec_layers > SPE_AMAX_SLOTS - SPE_AMAX_DEC)
     return fail(SPE_E_STATE, "fp32h3: decoder activation-scale slots exhausted");
   if (stages & SPE_STAGE_BACKBONE) TRY(backbone_stage(f, images));
-  if (stages & SPE_STAGE_TRANSFORMER) TRY(encoder_stage(f));
-  if (stages & SPE_STAGE_DECODE) TRY(decoder_stage(f, *out));
+  if (stages & SPE_STAGE_TRANSFORMER) TRY(m->pre_norm ? encoder_stage_pre(f) : encoder_stage(f));
+  if (stages & SPE_STAGE_DECODE) TRY(m->pre_norm ? decoder_stage_pre(f, *out) : decoder_stage(f, *out));
   return 0;
 }
 

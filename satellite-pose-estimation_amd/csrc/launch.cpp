@@ -184,6 +184,28 @@ int run_ffn(spe_model* m, const char* kind, const Conv& l1, const Conv& l2, cons
   return run_other(m, kind, flops, bytes, s, [&] { return spe_launch_ffn_ln(a, s); });
 }
 
+// The pre-norm form (ffn.hip spe_launch_ffn_pre): y = x + W2 relu(W1 LN(x; g, b) + b1) + b2 and y2 = LN(y; g2, b2n)
+// beside it (y2 null: not stored), ypos = y2 + pos.  x and y may alias.
+int run_ffn_pre(spe_model* m, const char* kind, const Conv& l1, const Conv& l2, const float* g, const float* b,
+                const void* x, void* y, const float* g2, const float* b2n, void* y2, int M, hipStream_t s, const void* pos,
+                void* ypos, int period, float* partial, const void* w2_chunked) {
+  FfnArgs a{};
+  a.pos = pos; a.ypos = ypos; a.pos_period = period;
+  a.splits = partial ? spe_ffn_splits(M, l1.N) : 1;
+  a.partial = a.splits > 1 ? partial : nullptr;
+  a.x = x; a.ldx = l1.K;
+  a.w1 = l1.w; a.ld1 = l1.Kpad; a.b1 = l1.bias;
+  a.w2 = w2_chunked ? w2_chunked : l2.w; a.ld2 = l2.Kpad; a.b2 = l2.bias;
+  a.w2_chunked = w2_chunked != nullptr;
+  a.gamma = g; a.beta = b;
+  a.gamma2 = g2; a.beta2 = b2n; a.y2 = y2;
+  a.y = y; a.ldy = l1.K;
+  a.M = M; a.D = l1.K; a.F = l1.N;
+  const double flops = 4.0 * M * (double)l1.K * l1.N;
+  const double bytes = (2.0 + (y2 ? 1.0 : 0.0) + (ypos ? 1.0 : 0.0)) * M * l1.K * m->esz + 2.0 * (double)l1.K * l1.N * m->esz;
+  return run_other(m, kind, flops, bytes, s, [&] { return spe_launch_ffn_pre(a, s); });
+}
+
 extern "C" {
 
 int spe_model_profile_begin(spe_model* m, const char* kind_prefix) {

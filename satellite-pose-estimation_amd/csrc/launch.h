@@ -43,3 +43,8 @@ int add_pos(const spe_model* m, GemmArgs& g, const void* pos, int ldp, int perio
 int run_ffn(spe_model* m, const char* kind, const Conv& l1, const Conv& l2, const float* g, const float* b, void* x,
             int M, hipStream_t s, const void* pos = nullptr, void* ypos = nullptr, int period = 0,
             float* partial = nullptr, const void* w2_chunked = nullptr);
+// the pre-norm form: y = x + FFN(LN(x; g, b)), y2 = LN(y; g2, b2n) beside it (null: not stored), ypos = y2 + pos
+int run_ffn_pre(spe_model* m, const char* kind, const Conv& l1, const Conv& l2, const float* g, const float* b,
+                const void* x, void* y, const float* g2, const float* b2n, void* y2, int M, hipStream_t s,
+                const void* pos = nullptr, void* ypos = nullptr, int period = 0, float* partial = nullptr,
+                const void* w2_chunked = nullptr);

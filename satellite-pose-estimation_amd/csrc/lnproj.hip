@@ -19,6 +19,9 @@ namespace {
 typedef __attribute__((address_space(3))) void* lds_ptr_t;
 constexpr int D = 256, NT = 512, NW = 8, KB = D * 2, KF = D / 32, JF = D / 16;
 
+// LN = false: the pre-norm form, C = R + A . Wo^T + bo with no LayerNorm (REV/models/transformer.py forward_pre:
+// the residual stream itself), same LDS-resident Wo and 16-row streaming tiles
+template <bool LN>
 __global__ __launch_bounds__(NT, 1) void lnproj_kernel(GemmArgs g, int row_tiles) {
   __shared__ __attribute__((aligned(1024))) char wl[D * KB];
   __shared__ __attribute__((aligned(16))) float sb[D], sg[D], sbt[D];
@@ -36,8 +39,10 @@ __global__ __launch_bounds__(NT, 1) void lnproj_kernel(GemmArgs g, int row_tiles
     }
     for (int i = tid; i < D; i += NT) {
       sb[i] = g.bias ? g.bias[i] : 0.f;
-      sg[i] = g.ln_g[i];
-      sbt[i] = g.ln_b[i];
+      if constexpr (LN) {
+        sg[i] = g.ln_g[i];
+        sbt[i] = g.ln_b[i];
+      }
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
@@ -80,6 +85,22 @@ __global__ __launch_bounds__(NT, 1) void lnproj_kernel(GemmArgs g, int row_tiles
       for (int j = 0; j < JF; ++j)
         acc[j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
             __builtin_bit_cast(bf16x8, ld16(wl + wb[kf & 3][j >> 3] + (j & 7) * 8192 + (kf >> 2) * 256)), av, acc[j], 0, 0, 0);
+    }
+    if constexpr (!LN) {
+#pragma unroll
+      for (int j = 0; j < JF; ++j) {
+        acc[j][0] += __uint_as_float(r[j].x << 16);
+        acc[j][1] += __uint_as_float(r[j].x & 0xffff0000u);
+        acc[j][2] += __uint_as_float(r[j].y << 16);
+        acc[j][3] += __uint_as_float(r[j].y & 0xffff0000u);
+      }
+      const int m = t * 16 + fr;
+      if (m < g.M) {
+        char* cp = (char*)g.C + ((size_t)m * g.ldc + 4 * fg) * 2;
+#pragma unroll
+        for (int j = 0; j < JF; ++j) st8(cp + j * 32, u32x2{pack_bf16x2(acc[j][0], acc[j][1]), pack_bf16x2(acc[j][2], acc[j][3])});
+      }
+      return;
     }
     // lane: row m = fr, columns 16j + 4fg + e
     float s = 0.f;
@@ -153,7 +174,25 @@ int spe_launch_lnproj(const GemmArgs& g, hipStream_t s) {
   // one workgroup per CU, but no more than the tiles need (each workgroup stages all of W first:
   // the decoder's 704-row launches take 6 workgroups, not 256 that would load W and exit)
   const int grid = std::min(spe_cu_count(), (row_tiles + NW - 1) / NW);
-  hipLaunchKernelGGL(lnproj_kernel, dim3(grid), dim3(NT), 0, s, g, row_tiles);
+  hipLaunchKernelGGL(lnproj_kernel<true>, dim3(grid), dim3(NT), 0, s, g, row_tiles);
+  spe_gemm_last_path = 4;
+  return (int)hipGetLastError();
+}
+
+// the pre-norm form: bf16, K = N = 256, residual, no LayerNorm, no activation (SPE_LNPROJ=0 disables it too)
+bool spe_lnproj_pre_applies(const GemmArgs& g) {
+  static const int on = spe_env_int("SPE_LNPROJ", 1);
+  return on && g.M > 0 && g.K == D && g.N == D && !g.ln_g && !g.ln_b && g.R && !g.act && !g.res_post && !g.out_f32 &&
+         !g.out_f16 && g.vt_T == 0 && g.r_period == 0 && !g.P && g.lda % 8 == 0 && g.ldb >= D && g.ldc % 4 == 0 &&
+         g.ldr % 4 == 0;
+}
+
+// 1 = not a problem for this kernel
+int spe_launch_lnproj_pre(const GemmArgs& g, hipStream_t s) {
+  if (!spe_lnproj_pre_applies(g)) return 1;
+  const int row_tiles = (g.M + 15) / 16;
+  const int grid = std::min(spe_cu_count(), (row_tiles + NW - 1) / NW);
+  hipLaunchKernelGGL(lnproj_kernel<false>, dim3(grid), dim3(NT), 0, s, g, row_tiles);
   spe_gemm_last_path = 4;
   return (int)hipGetLastError();
 }

@@ -71,6 +71,7 @@ struct Ws {                // workspace layout (byte offsets)
   size_t tgt, dtmp, dqkv, dvt, dao, dqc, dffn, dffnpart, hs;
   size_t xq, xu, xpm, xpl, xpu;           // cross-attention against the memory (xattn.hip)
   size_t xvp;                // fp32h3: the memory's fp16 value planes (xattn_h3.hip; the key planes go to srcpos)
+  size_t nrm, dnrm;          // pre-norm models: the normed copies of the encoder / decoder residual stream (else 0 bytes)
   size_t amax;               // fp32h3: max |activation| slots (SPE_AMAX_SLOTS floats; backbone, then transformer)
   size_t total;
 };
@@ -186,6 +187,7 @@ struct RtModel {
 
 struct spe_model {
   int family = 0;            // 0: DETR (REV), 1: RT-DETR (UNC)
+  int pre_norm = 0;          // DETR: SPE_MODEL_PRE_NORM (REV/models/transformer.py normalize_before)
   int backbone = 0;          // DETR: SPE_BACKBONE_RESNET50_S8 (Backbone8s) or SPE_BACKBONE_RESNET50_S16 (Backbone)
   int x3 = 0;                // fp32 model computed with split-bf16 MFMA (SPE_DTYPE_F32X3_, _F32X6_)
   int x6 = 0;                // ... with the GEMMs / convs on the three-way split path (SPE_DTYPE_F32X6_)
@@ -221,6 +223,7 @@ struct spe_model {
   void* qpos = nullptr;    // [Q][256] T
   void* pos_crossK = nullptr;  // bf16 / fp32x6 models: pos . W_crossK^T [tokens][L*256]
   float *dng = nullptr, *dnb = nullptr;
+  float *eng = nullptr, *enb = nullptr;   // pre-norm models: transformer.encoder.norm
   HeadArgs head{};
   Profiler prof;
 };

@@ -33,7 +33,7 @@ int spe_fail(int code, const std::string& msg) {
 
 namespace {
 
-std::vector<std::pair<std::string, std::vector<int64_t>>> build_spec(const spe_model_config& c, int backbone) {
+std::vector<std::pair<std::string, std::vector<int64_t>>> build_spec(const spe_model_config& c, int backbone, bool pre_norm) {
   const bool s16 = backbone == SPE_BACKBONE_RESNET50_S16;   // no neck; input_proj over layer3's 1024 channels
   std::vector<std::pair<std::string, std::vector<int64_t>>> s;
   const int64_t d = c.hidden_dim, ff = c.dim_feedforward;
@@ -49,6 +49,8 @@ std::vector<std::pair<std::string, std::vector<int64_t>>> build_spec(const spe_m
     add(p + ".linear2.weight", {d, ff}); add(p + ".linear2.bias", {d});
     for (const char* n : {"norm1", "norm2"}) { add(p + "." + n + ".weight", {d}); add(p + "." + n + ".bias", {d}); }
   }
+  // (TransformerEncoder registers its closing LayerNorm after its layers, with normalize_before only)
+  if (pre_norm) { add("transformer.encoder.norm.weight", {d}); add("transformer.encoder.norm.bias", {d}); }
   for (int i = 0; i < c.dec_layers; ++i) {
     std::string p = "transformer.decoder.layers." + std::to_string(i);
     for (const char* a : {"self_attn", "multihead_attn"}) {
@@ -690,6 +692,10 @@ int build_device(spe_model* m) {
       e.qpos_cq = spe_use_xattn(m) ? nullptr : dalloc(m, Q * d * es);
     }
   }
+  if (m->pre_norm) {
+    m->eng = upload_key(m, "transformer.encoder.norm.weight");
+    m->enb = upload_key(m, "transformer.encoder.norm.bias");
+  }
   m->dng = upload_key(m, "transformer.decoder.norm.weight");
   m->dnb = upload_key(m, "transformer.decoder.norm.bias");
 
@@ -765,6 +771,8 @@ Ws spe_plan(const spe_model* m, int B) {
   const int fsplit = std::max(spe_ffn_splits((int)(B * Q), (int)ff), m->esz == 2 && d == 256 && ff % 256 == 0 ? (int)ff / 256 : 1);
   w.dffnpart = take((size_t)std::max(1, fsplit) * B * Q * d * 4);
   w.hs = take((size_t)B * Q * d * 4);
+  w.nrm = take(m->pre_norm ? (size_t)B * T * d * E : 0);
+  w.dnrm = take(m->pre_norm ? (size_t)B * Q * d * E : 0);
   w.amax = take(m->h3 ? SPE_AMAX_SLOTS * 4 : 0);
   w.total = off;
   return w;
@@ -780,7 +788,16 @@ int spe_model_create(const spe_model_config* cfg, spe_model** out) {
 }
 
 int spe_model_create_backbone(const spe_model_config* cfg, int backbone, spe_model** out) {
+  return spe_model_create_flags(cfg, backbone, 0, out);
+}
+
+int spe_model_create_flags(const spe_model_config* cfg, int backbone, int flags, spe_model** out) {
   if (!cfg || !out) return fail(SPE_E_ARG, "null argument");
+  if (flags & ~SPE_MODEL_PRE_NORM) return fail(SPE_E_ARG, "flags: SPE_MODEL_PRE_NORM or 0");
+  if ((flags & SPE_MODEL_PRE_NORM) && cfg->dtype == SPE_DTYPE_F32H3_)
+    return fail(SPE_E_ARG, "pre_norm: fp32h3 is not served (its activation-scale ledger takes static bounds from "
+                           "post-norm LayerNorm outputs, which the pre-norm residual stream does not have); use "
+                           "fp32, fp32x3, fp32x6 or bf16");
   if (backbone != SPE_BACKBONE_RESNET50_S8 && backbone != SPE_BACKBONE_RESNET50_S16)
     return fail(SPE_E_ARG, "backbone: SPE_BACKBONE_RESNET50_S8 or SPE_BACKBONE_RESNET50_S16");
   if (cfg->hidden_dim != 256 || cfg->nheads * 32 != cfg->hidden_dim)
@@ -804,7 +821,8 @@ int spe_model_create_backbone(const spe_model_config* cfg, int backbone, spe_mod
   if (m->x3) { m->cfg.dtype = SPE_DTYPE_F32_; if (m->cfg.attn_dtype) m->cfg.attn_dtype = SPE_DTYPE_F32_; }
   m->esz = cfg->dtype == SPE_DTYPE_BF16_ ? 2 : 4;
   m->backbone = backbone;
-  m->spec = build_spec(*cfg, backbone);
+  m->pre_norm = (flags & SPE_MODEL_PRE_NORM) != 0;
+  m->spec = build_spec(*cfg, backbone, m->pre_norm);
   *out = m;
   return 0;
 }

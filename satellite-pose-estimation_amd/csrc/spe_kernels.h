@@ -118,6 +118,9 @@ int spe_launch_gemm2(const GemmArgs& g, int mode, hipStream_t s);   // 1 = not a
 int spe_launch_sgemm(const GemmArgs& g, int mode, hipStream_t s);   // 1 = not applicable
 int spe_launch_lnproj(const GemmArgs& g, hipStream_t s);             // 1 = not applicable (lnproj.hip)
 bool spe_lnproj_applies(const GemmArgs& g);
+// the pre-norm form C = R + A . W^T + b (no LayerNorm; in place over R allowed), same return convention
+int spe_launch_lnproj_pre(const GemmArgs& g, hipStream_t s);
+bool spe_lnproj_pre_applies(const GemmArgs& g);
 // bf16 GEMM + residual + LayerNorm in one launch: lnproj.hip at any row count, else the large-tile kernel
 inline bool spe_ln_fusable(const GemmArgs& g) { return spe_lnproj_applies(g) || spe_gemm_ln_fusable(g); }
 int spe_launch_pconv(const GemmArgs& g, hipStream_t s);             // 1 = not applicable (pconv.hip)
@@ -253,10 +256,16 @@ struct FfnArgs {
   int splits; float* partial;      // optional split over F for few rows: fp32 [splits][M][256] workspace
   int row0;                        // first row of this launch's tiles (internal: the FFN tail launch)
   int w2_chunked;                  // w2 stored chunk-packed [F/32][256][32] (spe_launch_ffn_w2_chunk_pack); ld2 unused
+  // pre-norm form (spe_launch_ffn_pre): n = LN(x; gamma, beta) on chip, y = x + W2 relu(W1 n + b1) + b2, and
+  // beside it y2 = LN(y; gamma2, beta2) [M][ldy] bf16 (null: not stored); ypos = y2 + pos
+  int pre;
+  const float* gamma2; const float* beta2;
+  void* y2;
 };
 // W2 [256][ld2] bf16 -> [F/32][256][32]: each 32-unit hidden chunk's columns as one contiguous block
 int spe_launch_ffn_w2_chunk_pack(const void* w2, int ld2, int F, void* dst, hipStream_t s);
 int spe_launch_ffn_ln(const FfnArgs& a, hipStream_t s);
+int spe_launch_ffn_pre(const FfnArgs& a, hipStream_t s);
 // y = LN(x + sum_s partial[s] + b2) over a.splits fp32 partials [splits][M][256] (ffn.hip)
 int spe_launch_ffn_reduce_ln(const FfnArgs& a, hipStream_t s);
 // fp32h3 encoder FFN + residual + LayerNorm in one pass (ffn_h3.hip): fp32 x / y [M][256], W1 as its

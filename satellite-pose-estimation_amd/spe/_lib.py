@@ -44,13 +44,14 @@ MBS_W_FLOATS = 1040              # spe_debug_mbs_entry's folded weights (include
 GH_POST_NONE, GH_POST_GATE, GH_POST_RESIDUAL = 0, 1, 2
 MB_ACT_NONE, MB_ACT_RELU, MB_ACT_HSWISH = 0, 1, 4
 SPE_BACKBONE_RESNET50_S8, SPE_BACKBONE_RESNET50_S16 = 0, 1     # spe_model_create_backbone
+SPE_MODEL_PRE_NORM = 1           # spe_model_create_flags
 SPE_STAGE_ENCODE, SPE_STAGE_DECODE, SPE_STAGE_BACKBONE, SPE_STAGE_TRANSFORMER = 1, 2, 4, 8
 SPE_PNP_EPNP, SPE_PNP_RANSAC_P3P_LM, SPE_PNP_EPNP_RANSAC_SIGMA, SPE_PNP_EPNP_LM, SPE_PNP_EPNP_CERES = 0, 1, 2, 3, 4
 SPE_PNP_EXHAUSTIVE = 5           # spe_pnp_exhaustive only
 SPE_PNP_OK, SPE_PNP_NO_FG, SPE_PNP_CV_ERROR, SPE_PNP_RANSAC_FALLBACK, SPE_PNP_UNPINNED = 0, 1, 2, 3, 4
 
 # every symbol include/spe.h declares (checked by tests/test_capi.py)
-EXPORTS = ["spe_abi_version", "spe_last_error", "spe_model_create", "spe_model_create_backbone", "spe_model_destroy", "spe_model_set_param",
+EXPORTS = ["spe_abi_version", "spe_last_error", "spe_model_create", "spe_model_create_backbone", "spe_model_create_flags", "spe_model_destroy", "spe_model_set_param",
            "spe_model_num_params", "spe_model_param_name", "spe_model_finalize", "spe_model_workspace_bytes",
            "spe_forward", "spe_forward_stages", "spe_forward_stages_u8", "spe_preprocess", "spe_preprocess_submission", "spe_criterion", "spe_criterion_sigma", "spe_ensemble_fuse", "spe_postprocess", "spe_pnp_batch", "spe_pnp_exhaustive", "spe_debug_pnp_exhaustive_stages", "spe_self_assess", "spe_speed_score", "spe_model_profile_begin",
            "spe_model_profile_end", "spe_model_profile_get", "spe_debug_gemm", "spe_debug_gemm_path", "spe_debug_gemm_h3", "spe_debug_ffn_h3", "spe_debug_ffn_h3_perm", "spe_debug_gemm_planes", "spe_debug_attention",
@@ -62,7 +63,8 @@ EXPORTS = ["spe_abi_version", "spe_last_error", "spe_model_create", "spe_model_c
            "spe_debug_ghost_cheap", "spe_debug_dfc_gate", "spe_debug_se_gate_bias", "spe_debug_pool2",
            "spe_debug_rt_resample2x", "spe_debug_rt_query_select", "spe_debug_rt_qpos_hidden", "spe_debug_rt_head_finish",
            "spe_debug_rt_msdeform",
-           "spe_forward_attention", "spe_forward_attention_workspace_bytes", "spe_debug_attn_map"]
+           "spe_forward_attention", "spe_forward_attention_workspace_bytes", "spe_debug_attn_map",
+           "spe_debug_ffn_pre", "spe_debug_oproj_pre"]
 
 
 class ModelConfig(ctypes.Structure):
@@ -108,6 +110,7 @@ def load(path: str):
     L.spe_last_error.restype = ctypes.c_char_p
     L.spe_model_create.argtypes = [ctypes.POINTER(ModelConfig), ctypes.POINTER(P)]
     L.spe_model_create_backbone.argtypes = [ctypes.POINTER(ModelConfig), I, ctypes.POINTER(P)]
+    L.spe_model_create_flags.argtypes = [ctypes.POINTER(ModelConfig), I, I, ctypes.POINTER(P)]
     L.spe_model_destroy.argtypes = [P]
     L.spe_model_destroy.restype = None
     L.spe_model_set_param.argtypes = [P, ctypes.c_char_p, P, I64]
@@ -148,6 +151,8 @@ def load(path: str):
     L.spe_debug_attention.argtypes = [P, I, P, I, P, I, P, P, I, I, I, I, I, F]
     L.spe_debug_layernorm.argtypes = [P, I, P, P, P, P, P, I, I]
     L.spe_debug_ffn.argtypes = [P, P, I, P, I, P, P, I, P, P, P, P, I, I, I, I, P, I]
+    L.spe_debug_ffn_pre.argtypes = L.spe_debug_ffn.argtypes + [P, P, P, P, I, P]
+    L.spe_debug_oproj_pre.argtypes = [P, P, I, P, I, P, P, I, P, I, I]
     L.spe_debug_xattn.argtypes = [P, P, I, P, I, P, I, P, I, P, P, P, I, I, I, I, I, P]
     L.spe_debug_xattn_h3.argtypes = [P, P, I, P, P, P, P, P, P, I, P, I, I, I, I, P, P]
     L.spe_debug_upconv.argtypes = [P, I, P, P, I, I, I, I, I]

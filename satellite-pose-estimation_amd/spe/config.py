@@ -29,6 +29,7 @@ class SpeConfig:
     num_classes: int = 11          # REV/models/detr_speed.py:305 (+1 no-object)
     sigma_head: bool = False       # UNC sigma head (UNC/src/zoo/rtdetr/rtdetr_decoder.py:295-297)
     backbone: str = "resnet50s8"   # --backbone (REV/main.py): "resnet50s8" (Backbone8s) or "resnet50" (Backbone)
+    pre_norm: bool = False         # --pre_norm (REV/main.py): normalize_before of both transformer layer classes
 
     def __post_init__(self):
         if self.backbone not in BACKBONES:
@@ -66,7 +67,8 @@ class SpeConfig:
                    hidden_dim=int(getattr(args, "hidden_dim", 256)),
                    nheads=int(getattr(args, "nheads", 8)),
                    dim_feedforward=int(getattr(args, "dim_feedforward", 2048)),
-                   sigma_head=bool(getattr(args, "sigma_head", False)))
+                   sigma_head=bool(getattr(args, "sigma_head", False)),
+                   pre_norm=bool(getattr(args, "pre_norm", False)))
 
     def to_dict(self):
         return asdict(self)

@@ -59,7 +59,8 @@ class DETR(nn.Module):
                              _lib.SPE_DTYPE_F16 if self.attn_dtype == "fp16" else 0)
         h = ctypes.c_void_p()
         bb = {"resnet50s8": _lib.SPE_BACKBONE_RESNET50_S8, "resnet50": _lib.SPE_BACKBONE_RESNET50_S16}[cfg.backbone]
-        _lib.check(L.spe_model_create_backbone(ctypes.byref(c), bb, ctypes.byref(h)), "spe_model_create_backbone")
+        flags = _lib.SPE_MODEL_PRE_NORM if cfg.pre_norm else 0
+        _lib.check(L.spe_model_create_flags(ctypes.byref(c), bb, flags, ctypes.byref(h)), "spe_model_create_flags")
         self._h = h
         self._keys = [L.spe_model_param_name(h, i).decode() for i in range(L.spe_model_num_params(h))]
 

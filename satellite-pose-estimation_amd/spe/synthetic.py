@@ -42,6 +42,8 @@ def param_shapes(cfg: SpeConfig):
                 (f"{p}.linear2.weight", (d, ff)), (f"{p}.linear2.bias", (d,)),
                 (f"{p}.norm1.weight", (d,)), (f"{p}.norm1.bias", (d,)),
                 (f"{p}.norm2.weight", (d,)), (f"{p}.norm2.bias", (d,))]
+    if cfg.pre_norm:   # TransformerEncoder's closing LayerNorm exists with normalize_before only
+        out += [("transformer.encoder.norm.weight", (d,)), ("transformer.encoder.norm.bias", (d,))]
     for i in range(cfg.dec_layers):
         p = f"transformer.decoder.layers.{i}"
         for a in ("self_attn", "multihead_attn"):
