@@ -1,5 +1,5 @@
 // Launch helpers of the native runtime (launch.h), shared by the DETR (forward.cpp) and the UNC
-// RT-DETR (rtdetr_model.cpp) launch sequences: every launch goes through run_gemm / run_attn /
+// RT-DETR (rtdetr_*.cpp) launch sequences: every launch goes through run_gemm / run_attn /
 // run_other, which bracket it with HIP events when the per-launch profiler is on
 // (spe_model_profile_*, bench roofline), and through the fp32h3 activation-scale ledger.
 #include "launch.h"

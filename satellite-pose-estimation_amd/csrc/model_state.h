@@ -1,4 +1,4 @@
-// Internal state of a spe_model (shared by registry.cpp, forward.cpp, launch.cpp and rtdetr_model.cpp).
+// Internal state of a spe_model (shared by registry.cpp, forward.cpp, launch.cpp and the rtdetr_*.cpp files).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -91,7 +91,7 @@ struct Profiler {
   size_t next_event = 0;
 };
 
-// ---- UNC RT-DETR (rtdetr_model.cpp)
+// ---- UNC RT-DETR (rtdetr_model.cpp; a backbone's packed state belongs to its rtdetr_<family>.cpp)
 struct RtBlock {             // PResNet BasicBlock / BottleNeck; shortcut conv (first block of a stage)
   Conv a, b, c, sc;          // variant d stride-2 shortcut: AvgPool2d(2, 2) + 1x1 folded into a 2x2/2 conv
   bool has_sc = false, bottleneck = false;
@@ -116,11 +116,14 @@ struct MbDw {                // depthwise conv: w fp32 [k*k][C] (BN scale folded
   float *w = nullptr, *bias = nullptr;
   int C = 0, k = 3, stride = 1;
 };
+struct MbSe {                // SE gate: w1 [hid][C] (BN folded), b1 [hid], w2t [hid][C], b2 [C] (GhostNetV2; else null)
+  float *w1 = nullptr, *b1 = nullptr, *w2t = nullptr, *b2 = nullptr;
+  int hidden = 0;
+};
 struct MbBlock {             // Block (mobilenetv3.py:45-120)
   Conv expand, project, skip_pw;     // 1x1 convs, rows [N][Kpad] T
   MbDw dw, skip_dw;
-  float *se_w1 = nullptr, *se_b1 = nullptr, *se_w2t = nullptr;   // SE gate: [hid][C] (BN folded), [hid], [hid][C]
-  int se_hidden = 0;
+  MbSe gate;
   int cin = 0, cexp = 0, cout = 0, stride = 1, act = 0;
   bool se = false, has_skip_pw = false, has_skip_dw = false;
 };
@@ -147,8 +150,7 @@ struct GhBlock {             // GhostBottleneckV2
   GhModule g1, g2;
   MbDw dw, sc_dw;            // conv_dw + bn_dw (stride 2), shortcut.0 + .1
   Conv sc_pw;                // shortcut.2 + .3
-  float *se_w1 = nullptr, *se_b1 = nullptr, *se_w2t = nullptr, *se_b2 = nullptr;   // [hid][mid_p], [hid], [hid][mid_p], [mid_p]
-  int se_hidden = 0;
+  MbSe gate;                 // over the mid_p lanes
   int cin_p = 0, mid_p = 0, cout_p = 0, k = 3, stride = 1;
   bool se = false, has_sc = false;
 };
@@ -158,18 +160,20 @@ struct RtGhost {
                                      // blocks.9.0 (160 -> 960, ReLU), Conv3
   std::vector<GhBlock> blocks;
 };
-struct RtModel {
-  spe_rtdetr_config cfg{};
-  bool mbv3 = false;                    // cfg.depth == SPE_RTDETR_MBV3_LARGE or SPE_RTDETR_MBV3_SMALL
-  bool mb_small = false;                // ... the latter
-  RtMbv3 mb;
-  bool ghost = false;                   // cfg.depth == SPE_RTDETR_GHOSTNETV2
-  RtGhost gh;
-  int fch[3] = {0, 0, 0};               // backbone output channels (the hybrid encoder's in_channels)
-  int L = 0, lvl_s[3] = {0, 0, 0}, lvl_start[4] = {0, 0, 0, 0};
+struct RtPresnet {
   Conv stem[3];
   std::vector<RtBlock> blocks;
   int stage_first[4] = {0, 0, 0, 0}, stage_n[4] = {0, 0, 0, 0};
+};
+struct RtBackbone;                      // rtdetr_backbone.h
+struct RtModel {
+  spe_rtdetr_config cfg{};
+  const RtBackbone* bb = nullptr;       // the family cfg.depth selects; its packed state is one of the next three
+  RtPresnet pr;
+  RtMbv3 mb;
+  RtGhost gh;
+  int fch[3] = {0, 0, 0};               // backbone output channels (the hybrid encoder's in_channels), set at create
+  int L = 0, lvl_s[3] = {0, 0, 0}, lvl_start[4] = {0, 0, 0, 0};
   Conv in_proj[3];
   Conv aqk, av, ao, al1, al2;          // AIFI encoder layer
   float *an1g, *an1b, *an2g, *an2b;

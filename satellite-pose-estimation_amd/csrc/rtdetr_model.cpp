@@ -4,245 +4,85 @@
 // itself defines, workspace plan and the launch sequence of RTDETR.forward in eval
 // (UNC/src/zoo/rtdetr/rtdetr.py:36-53):
 //
-//   PResNet-vd (UNC/nn/backbone/presnet.py:156-265) -> HybridEncoder (hybrid_encoder.py:332-401)
+//   backbone (one RtBackbone row, rtdetr_backbone.h) -> HybridEncoder (hybrid_encoder.py:332-401)
 //   -> RTDETRTransformer (rtdetr_decoder.py:505-710) -> RTDETRPostProcessor
 //      (rtdetr_postprocessor.py:44-76)
 //
 // Folds: every ConvNormLayer's eval BatchNorm into its conv; RepVggBlock's 3x3 + 1x1 branches
-// into one 3x3 conv (RepVggBlock.convert_to_deploy, hybrid_encoder.py:55-95); the variant-d
-// shortcut AvgPool2d(2, 2, ceil_mode) + 1x1 conv into one 2x2 stride-2 conv with w/4 per tap
-// (exact for the even feature sizes of inputs that are multiples of 32).
+// into one 3x3 conv (RepVggBlock.convert_to_deploy, hybrid_encoder.py:55-95).
 #include <hip/hip_runtime.h>
 
 #include <cmath>
 #include <cstdio>
 #include <cstring>
 
-#include "launch.h"
-#include "model_state.h"
-#include "registry.h"
+#include "rtdetr_backbone.h"
 
 #define fail spe_fail
 
 namespace {
 
-const int RESNET_CFG18[4] = {2, 2, 2, 2}, RESNET_CFG50[4] = {3, 4, 6, 3};
 
-inline bool is_mbv3_small(const spe_rtdetr_config& c) { return c.depth == SPE_RTDETR_MBV3_SMALL; }
-inline bool is_mbv3(const spe_rtdetr_config& c) { return c.depth == SPE_RTDETR_MBV3_LARGE || is_mbv3_small(c); }
-inline bool is_ghost(const spe_rtdetr_config& c) { return c.depth == SPE_RTDETR_GHOSTNETV2; }
-inline bool is_presnet(const spe_rtdetr_config& c) { return !is_mbv3(c) && !is_ghost(c); }
-inline int resnet_expansion(const spe_rtdetr_config& c) { return is_presnet(c) && c.depth >= 50 ? 4 : 1; }
-
-// MobileNetV3_Large.bneck (mobilenetv3.py:148-164): kernel, in, expand, out, Hardswish (else ReLU), SE, stride
-struct MbRow { int k, cin, cexp, cout, hs, se, stride; };
-const MbRow MBV3_LARGE[15] = {
-    {3, 16, 16, 16, 0, 0, 1},    {3, 16, 64, 24, 0, 0, 2},    {3, 24, 72, 24, 0, 0, 1},   {5, 24, 72, 40, 0, 1, 2},
-    {5, 40, 120, 40, 0, 1, 1},   {5, 40, 120, 40, 0, 1, 1},   {3, 40, 240, 80, 1, 0, 2},  {3, 80, 200, 80, 1, 0, 1},
-    {3, 80, 184, 80, 1, 0, 1},   {3, 80, 184, 80, 1, 0, 1},   {3, 80, 480, 112, 1, 1, 1}, {3, 112, 672, 112, 1, 1, 1},
-    {5, 112, 672, 160, 1, 1, 2}, {5, 160, 672, 160, 1, 1, 1}, {5, 160, 960, 160, 1, 1, 1}};
-// MobileNetV3_Small.bneck (mobilenetv3.py:248-260).  Block 0: full stem resolution, SE, stride 2 with in == out
-const MbRow MBV3_SMALL[11] = {
-    {3, 16, 16, 16, 0, 1, 2},  {3, 16, 72, 24, 0, 0, 2},  {3, 24, 88, 24, 0, 0, 1},  {5, 24, 96, 40, 1, 1, 2},
-    {5, 40, 240, 40, 1, 1, 1}, {5, 40, 240, 40, 1, 1, 1}, {5, 40, 120, 48, 1, 1, 1}, {5, 48, 144, 48, 1, 1, 1},
-    {5, 48, 288, 96, 1, 1, 2}, {5, 96, 576, 96, 1, 1, 1}, {5, 96, 576, 96, 1, 1, 1}};
-struct MbTable { const MbRow* rows; int n, last_in, head_in; };   // conv2's and linear3's input widths
-inline MbTable mb_table(const spe_rtdetr_config& c) {
-  return is_mbv3_small(c) ? MbTable{MBV3_SMALL, 11, 96, 576} : MbTable{MBV3_LARGE, 15, 160, 960};
-}
-inline int se_hidden(int c) { return c / 4 > 8 ? c / 4 : 8; }
-
-// GhostNetV2.cfgs at width 1.0 (ghostnetv2.py:297-319) in layer_id order: dw kernel, mid, out, SE, stride, and
-// the nn.Sequential stage / index the block's key carries.  Blocks 0-1: ghost1 mode "original", >= 2: "attn".
-struct GhRow { int k, mid, cout, se, stride, stage, idx; };
-const GhRow GHOSTV2[16] = {
-    {3, 16, 16, 0, 1, 0, 0},   {3, 48, 24, 0, 2, 1, 0},   {3, 72, 24, 0, 1, 2, 0},   {5, 72, 40, 1, 2, 3, 0},
-    {5, 120, 40, 1, 1, 4, 0},  {3, 240, 80, 0, 2, 5, 0},  {3, 200, 80, 0, 1, 6, 0},  {3, 184, 80, 0, 1, 6, 1},
-    {3, 184, 80, 0, 1, 6, 2},  {3, 480, 112, 1, 1, 6, 3}, {3, 672, 112, 1, 1, 6, 4}, {5, 672, 160, 1, 2, 7, 0},
-    {5, 960, 160, 0, 1, 8, 0}, {5, 960, 160, 1, 1, 8, 1}, {5, 960, 160, 0, 1, 8, 2}, {5, 960, 160, 1, 1, 8, 3}};
-constexpr int GH_ATTN_FROM = 2;
-// SqueezeExcite's reduced width, _make_divisible(mid * 0.25, 4) (ghostnetv2.py:21-34): 20, 32, 120, 168, 240
-inline int gh_se_hidden(int mid) {
-  const double v = mid * 0.25;
-  int n = (int)(v + 2) / 4 * 4;
-  if (n < 4) n = 4;
-  return n < 0.9 * v ? n + 4 : n;
-}
-inline std::string gh_key(const GhRow& r) { return "backbone.blocks." + std::to_string(r.stage) + "." + std::to_string(r.idx); }
-// physical layout of a C-channel ghost tensor: two halves of hp = pad8(C / 2) lanes (identity when C / 2 % 8 == 0)
-struct GhLay {
-  int C, half, hp;
-  explicit GhLay(int c) : C(c), half(c / 2), hp((c / 2 + 7) & ~7) {}
-  int Cp() const { return 2 * hp; }
-  int phys(int c) const { return c < half ? c : hp + c - half; }
-};
-
-std::vector<std::pair<std::string, std::vector<int64_t>>> rt_spec(const spe_rtdetr_config& c) {
-  std::vector<std::pair<std::string, std::vector<int64_t>>> s;
+// the parameter space: temper_param, the backbone's keys, then the decoder's and the encoder's
+std::vector<std::pair<std::string, std::vector<int64_t>>> rt_spec(const RtModel& r) {
+  const auto& c = r.cfg;
+  RtSpec s;
   const int64_t d = 256, C = c.num_classes + 1;
-  auto add = [&](const std::string& k, std::vector<int64_t> sh) { s.emplace_back(k, std::move(sh)); };
-  auto bn = [&](const std::string& p, int64_t ch) {
-    for (const char* n : {"weight", "bias", "running_mean", "running_var"}) add(p + "." + n, {ch});
-  };
-  auto cnl = [&](const std::string& p, int64_t cin, int64_t cout, int64_t k) {
-    add(p + ".conv.weight", {cout, cin, k, k});
-    bn(p + ".norm", cout);
-  };
-  auto lin = [&](const std::string& p, int64_t o, int64_t i) { add(p + ".weight", {o, i}); add(p + ".bias", {o}); };
   auto mlp = [&](const std::string& p, std::vector<int64_t> dims) {
-    for (size_t j = 0; j + 1 < dims.size(); ++j) lin(p + ".layers." + std::to_string(j), dims[j + 1], dims[j]);
+    for (size_t j = 0; j + 1 < dims.size(); ++j) s.lin(p + ".layers." + std::to_string(j), dims[j + 1], dims[j]);
   };
   auto mha = [&](const std::string& p) {
-    add(p + ".in_proj_weight", {3 * d, d});
-    add(p + ".in_proj_bias", {3 * d});
-    lin(p + ".out_proj", d, d);
+    s.add(p + ".in_proj_weight", {3 * d, d});
+    s.add(p + ".in_proj_bias", {3 * d});
+    s.lin(p + ".out_proj", d, d);
   };
-  add("temper_param", {1});
-  if (is_mbv3(c)) {     // registration order of MobileNetV3_{Large,Small}.__init__ (mobilenetv3.py:136-173, 241-270)
-    const std::string b = "backbone.";
-    const MbTable t = mb_table(c);
-    add(b + "conv1.weight", {16, 3, 3, 3});
-    if (!is_mbv3_small(c)) { bn(b + "bn1", 16); bn(b + "Bn1", 128); bn(b + "Bn2", 256); }
-    add(b + "Conv1.weight", {128, 16, 3, 3});
-    add(b + "Conv2.weight", {256, 128, 3, 3});
-    if (is_mbv3_small(c)) bn(b + "bn1", 16);       // Small: Conv1 / Conv2 are bare, bn1 is registered after them
-    for (int i = 0; i < t.n; ++i) {
-      const MbRow& r = t.rows[i];
-      const std::string p = b + "bneck." + std::to_string(i);
-      add(p + ".conv1.weight", {r.cexp, r.cin, 1, 1}); bn(p + ".bn1", r.cexp);
-      add(p + ".conv2.weight", {r.cexp, 1, r.k, r.k}); bn(p + ".bn2", r.cexp);
-      if (r.se) {
-        const int64_t h = se_hidden(r.cexp);
-        add(p + ".se.se.1.weight", {h, r.cexp, 1, 1}); bn(p + ".se.se.2", h);
-        add(p + ".se.se.4.weight", {r.cexp, h, 1, 1});
-      }
-      add(p + ".conv3.weight", {r.cout, r.cexp, 1, 1}); bn(p + ".bn3", r.cout);
-      if (r.stride == 1 && r.cin != r.cout) {
-        add(p + ".skip.0.weight", {r.cout, r.cin, 1, 1}); bn(p + ".skip.1", r.cout);
-      } else if (r.stride == 2 && r.cin != r.cout) {
-        add(p + ".skip.0.weight", {r.cin, 1, 3, 3}); bn(p + ".skip.1", r.cin);
-        add(p + ".skip.2.weight", {r.cout, r.cin, 1, 1}); add(p + ".skip.2.bias", {r.cout}); bn(p + ".skip.3", r.cout);
-      } else if (r.stride == 2) {
-        add(p + ".skip.0.weight", {r.cout, 1, 3, 3}); bn(p + ".skip.1", r.cout);
-      }
-    }
-    add(b + "conv2.weight", {512, t.last_in, 1, 1}); bn(b + "bn2", 512);
-    add(b + "linear3.weight", {1280, t.head_in}); bn(b + "bn3", 1280);     // built, never called
-  }
-  if (is_ghost(c)) {    // registration order of GhostNetV2.__init__ (ghostnetv2.py:331-387)
-    const std::string b = "backbone.";
-    bn(b + "Bn1", 128); bn(b + "Bn2", 256); bn(b + "Bn3", 512);
-    add(b + "Conv1.weight", {128, 16, 3, 3});
-    add(b + "Conv2.weight", {256, 128, 3, 3});
-    add(b + "Conv3.weight", {512, 960, 1, 1});
-    add(b + "conv_stem.weight", {16, 3, 3, 3});
-    bn(b + "bn1", 16);
-    auto ghost = [&](const std::string& p, int64_t cin, int64_t cout, bool attn) {
-      const int64_t h = (cout + 1) / 2;
-      add(p + ".primary_conv.0.weight", {h, cin, 1, 1}); bn(p + ".primary_conv.1", h);
-      add(p + ".cheap_operation.0.weight", {h, 1, 3, 3}); bn(p + ".cheap_operation.1", h);
-      if (attn) {
-        add(p + ".short_conv.0.weight", {cout, cin, 1, 1}); bn(p + ".short_conv.1", cout);
-        add(p + ".short_conv.2.weight", {cout, 1, 1, 5}); bn(p + ".short_conv.3", cout);
-        add(p + ".short_conv.4.weight", {cout, 1, 5, 1}); bn(p + ".short_conv.5", cout);
-      }
-    };
-    int64_t cin = 16;
-    for (int i = 0; i < 16; ++i) {
-      const GhRow& r = GHOSTV2[i];
-      const std::string p = gh_key(r);
-      ghost(p + ".ghost1", cin, r.mid, i >= GH_ATTN_FROM);
-      if (r.stride > 1) { add(p + ".conv_dw.weight", {r.mid, 1, r.k, r.k}); bn(p + ".bn_dw", r.mid); }
-      if (r.se) {
-        const int64_t h = gh_se_hidden(r.mid);
-        add(p + ".se.conv_reduce.weight", {h, r.mid, 1, 1}); add(p + ".se.conv_reduce.bias", {h});
-        add(p + ".se.conv_expand.weight", {r.mid, h, 1, 1}); add(p + ".se.conv_expand.bias", {r.mid});
-      }
-      ghost(p + ".ghost2", r.mid, r.cout, false);
-      if (!(cin == r.cout && r.stride == 1)) {
-        add(p + ".shortcut.0.weight", {cin, 1, r.k, r.k}); bn(p + ".shortcut.1", cin);
-        add(p + ".shortcut.2.weight", {r.cout, cin, 1, 1}); bn(p + ".shortcut.3", r.cout);
-      }
-      cin = r.cout;
-    }
-    add(b + "blocks.9.0.conv.weight", {960, 160, 1, 1}); bn(b + "blocks.9.0.bn1", 960);
-    add(b + "conv_head.weight", {1280, 960, 1, 1}); add(b + "conv_head.bias", {1280});   // built, never called
-    lin(b + "classifier", 1000, 1280);
-  }
-  const bool bott = is_presnet(c) && c.depth >= 50;
-  const int64_t exp = bott ? 4 : 1;
-  if (is_presnet(c)) {
-  cnl("backbone.conv1.conv1_1", 3, 32, 3);
-  cnl("backbone.conv1.conv1_2", 32, 32, 3);
-  cnl("backbone.conv1.conv1_3", 32, 64, 3);
-  const int* nb = bott ? RESNET_CFG50 : RESNET_CFG18;
-  const int64_t widths[4] = {64, 128, 256, 512};
-  int64_t cin = 64;
-  for (int i = 0; i < 4; ++i)
-    for (int j = 0; j < nb[i]; ++j) {
-      const std::string p = "backbone.res_layers." + std::to_string(i) + ".blocks." + std::to_string(j);
-      const int64_t co = widths[i];
-      const bool s2 = j == 0 && i > 0;
-      auto shortcut = [&] { if (j == 0) cnl(s2 ? p + ".short.conv" : p + ".short", cin, co * exp, 1); };
-      if (bott) {
-        cnl(p + ".branch2a", cin, co, 1);
-        cnl(p + ".branch2b", co, co, 3);
-        cnl(p + ".branch2c", co, co * exp, 1);
-        shortcut();
-      } else {                       // BasicBlock registers `short` before its branches
-        shortcut();
-        cnl(p + ".branch2a", cin, co, 3);
-        cnl(p + ".branch2b", co, co, 3);
-      }
-      cin = co * exp;
-    }
-  }
+  s.add("temper_param", {1});
+  r.bb->spec(c, s);
   const int NL = 3, NP = 4, H = 8, P = H * NL * NP;
-  for (int l = 0; l < NL; ++l) cnl("decoder.input_proj." + std::to_string(l), d, d, 1);
+  for (int l = 0; l < NL; ++l) s.cnl("decoder.input_proj." + std::to_string(l), d, d, 1);
   for (int i = 0; i < c.dec_layers; ++i) {
     const std::string p = "decoder.decoder.layers." + std::to_string(i);
     mha(p + ".self_attn");
-    add(p + ".norm1.weight", {d}); add(p + ".norm1.bias", {d});
-    lin(p + ".cross_attn.sampling_offsets", 2 * P, d);
-    lin(p + ".cross_attn.attention_weights", P, d);
-    lin(p + ".cross_attn.value_proj", d, d);
-    lin(p + ".cross_attn.output_proj", d, d);
-    add(p + ".norm2.weight", {d}); add(p + ".norm2.bias", {d});
-    lin(p + ".linear1", c.dec_ff, d);
-    lin(p + ".linear2", d, c.dec_ff);
-    add(p + ".norm3.weight", {d}); add(p + ".norm3.bias", {d});
+    s.add(p + ".norm1.weight", {d}); s.add(p + ".norm1.bias", {d});
+    s.lin(p + ".cross_attn.sampling_offsets", 2 * P, d);
+    s.lin(p + ".cross_attn.attention_weights", P, d);
+    s.lin(p + ".cross_attn.value_proj", d, d);
+    s.lin(p + ".cross_attn.output_proj", d, d);
+    s.add(p + ".norm2.weight", {d}); s.add(p + ".norm2.bias", {d});
+    s.lin(p + ".linear1", c.dec_ff, d);
+    s.lin(p + ".linear2", d, c.dec_ff);
+    s.add(p + ".norm3.weight", {d}); s.add(p + ".norm3.bias", {d});
   }
   for (int i = 0; i < c.dec_layers; ++i) mlp("decoder.decoder.sigma_embed." + std::to_string(i), {d, d, d, 1});
   mlp("decoder.query_pos_head", {2, 2 * d, d});
-  lin("decoder.enc_output.0", d, d);
-  add("decoder.enc_output.1.weight", {d}); add("decoder.enc_output.1.bias", {d});
-  lin("decoder.enc_score_head", C, d);
+  s.lin("decoder.enc_output.0", d, d);
+  s.add("decoder.enc_output.1.weight", {d}); s.add("decoder.enc_output.1.bias", {d});
+  s.lin("decoder.enc_score_head", C, d);
   mlp("decoder.enc_bbox_head", {d, d, d, 2});
-  for (int i = 0; i < c.dec_layers; ++i) lin("decoder.dec_score_head." + std::to_string(i), C, d);
+  for (int i = 0; i < c.dec_layers; ++i) s.lin("decoder.dec_score_head." + std::to_string(i), C, d);
   for (int i = 0; i < c.dec_layers; ++i) mlp("decoder.dec_bbox_head." + std::to_string(i), {d, d, d, 2});
-  const int64_t bc[3] = {128 * exp, 256 * exp, 512 * exp};
   for (int l = 0; l < 3; ++l) {
-    add("encoder.input_proj." + std::to_string(l) + ".0.weight", {d, bc[l], 1, 1});
-    bn("encoder.input_proj." + std::to_string(l) + ".1", d);
+    s.add("encoder.input_proj." + std::to_string(l) + ".0.weight", {d, r.fch[l], 1, 1});
+    s.bn("encoder.input_proj." + std::to_string(l) + ".1", d);
   }
-  add("encoder.encoder_fusion_input.weight", {d, 3 * d, 1, 1});
+  s.add("encoder.encoder_fusion_input.weight", {d, 3 * d, 1, 1});
   const std::string a = "encoder.encoder.0.layers.0";
   mha(a + ".self_attn");
-  lin(a + ".linear1", c.enc_ff, d);
-  lin(a + ".linear2", d, c.enc_ff);
-  for (const char* n : {"norm1", "norm2"}) { add(a + "." + n + ".weight", {d}); add(a + "." + n + ".bias", {d}); }
-  for (int i = 0; i < 2; ++i) cnl("encoder.lateral_convs." + std::to_string(i), d, d, 1);
+  s.lin(a + ".linear1", c.enc_ff, d);
+  s.lin(a + ".linear2", d, c.enc_ff);
+  for (const char* n : {"norm1", "norm2"}) { s.add(a + "." + n + ".weight", {d}); s.add(a + "." + n + ".bias", {d}); }
+  for (int i = 0; i < 2; ++i) s.cnl("encoder.lateral_convs." + std::to_string(i), d, d, 1);
   const int64_t h = c.csp_hidden;
   for (const char* blocks : {"fpn_blocks", "pan_blocks"})
     for (int i = 0; i < 2; ++i) {
       const std::string p = std::string("encoder.") + blocks + "." + std::to_string(i);
-      cnl(p + ".conv1", 2 * d, h, 1);
-      cnl(p + ".conv2", 2 * d, h, 1);
-      cnl(p + ".bottlenecks.0.conv1", h, h, 3);
-      cnl(p + ".bottlenecks.0.conv2", h, h, 1);
-      if (h != d) cnl(p + ".conv3", h, d, 1);
+      s.cnl(p + ".conv1", 2 * d, h, 1);
+      s.cnl(p + ".conv2", 2 * d, h, 1);
+      s.cnl(p + ".bottlenecks.0.conv1", h, h, 3);
+      s.cnl(p + ".bottlenecks.0.conv2", h, h, 1);
+      if (h != d) s.cnl(p + ".conv3", h, d, 1);
     }
-  return s;
+  return std::move(s.keys);
 }
 
 // rows [r0, r0+n) of several [*, K] weights stacked into one linear (one GEMM for several heads)
@@ -338,35 +178,21 @@ RtCsp make_csp(spe_model* m, const std::string& p, int h) {
   return c;
 }
 
-// largest tiles x channels product of an SE block's pool partials (block 11: 4 tiles x 672 at 256 input)
-constexpr size_t MB_POOL_MAX = 4096;
-
 // ---- workspace plan
-struct RtWs {
-  size_t x0, bufA, bufB, t1, t2, sc, f0, f1, f2;
-  size_t cat0, cat1, catp0, catp1, aqk, avt, aao, atmp, affn, aout;
-  size_t x1, x2, y, inner1, p3, n4, n5;
-  size_t mbpool, mbscale;      // MobileNetV3: dwconv pool partials [B][MB_POOL_MAX], SE scales [B][960]
-  size_t mem, omem, elog, value;
-  size_t topk, tgt, slog, sanc, refs, qh, qpos, hh1, hh2, dqk, dvt, dao, dtmp, t1d, t2d, soaw, dcr, dffn, hs, lgt;
-  size_t total;
-};
-
 RtWs rt_plan(const spe_model* m, int B) {
   const RtModel& r = *m->rt;
   const auto& c = r.cfg;
   const size_t E = m->esz, S = c.input_size, Q = c.num_queries, L = r.L, BQ = (size_t)B * Q;
   const size_t s0 = r.lvl_s[0], s1 = r.lvl_s[1], s2 = r.lvl_s[2];
-  const size_t exp = resnet_expansion(c);
   RtWs w{};
   size_t off = 0;
   auto take = [&](size_t bytes) { size_t o = off; off += (bytes + 255) & ~size_t(255); return o; };
   const size_t big = (size_t)B * S * S * 16 * E;     // stride 2 x 64 ch == stride 4 x 256 ch
   w.x0 = take((size_t)B * S * S * 8 * E);
   w.bufA = take(big); w.bufB = take(big); w.t1 = take(big); w.t2 = take(big); w.sc = take(big);
-  w.f0 = take((size_t)B * s0 * s0 * 128 * exp * E);
-  w.f1 = take((size_t)B * s1 * s1 * 256 * exp * E);
-  w.f2 = take((size_t)B * s2 * s2 * 512 * exp * E);
+  w.f0 = take((size_t)B * s0 * s0 * r.fch[0] * E);
+  w.f1 = take((size_t)B * s1 * s1 * r.fch[1] * E);
+  w.f2 = take((size_t)B * s2 * s2 * r.fch[2] * E);
   w.cat0 = take((size_t)B * s0 * s0 * 512 * E);
   w.cat1 = take((size_t)B * s1 * s1 * 512 * E);
   w.catp0 = take((size_t)B * s1 * s1 * 512 * E);
@@ -380,9 +206,9 @@ RtWs rt_plan(const spe_model* m, int B) {
   w.p3 = take((size_t)B * s0 * s0 * 256 * E);
   w.n4 = take((size_t)B * s1 * s1 * 256 * E);
   w.n5 = take((size_t)B * s2 * s2 * 256 * E);
-  // (zero bytes for PResNet handles: their plan is what it was)
-  w.mbpool = take(r.mbv3 || r.ghost ? (size_t)B * MB_POOL_MAX * 4 : 0);
-  w.mbscale = take(r.mbv3 || r.ghost ? (size_t)B * 960 * 4 : 0);
+  // (zero bytes for a backbone without SE blocks)
+  w.mbpool = take(r.bb->se_scratch ? (size_t)B * MB_POOL_MAX * 4 : 0);
+  w.mbscale = take(r.bb->se_scratch ? (size_t)B * 960 * 4 : 0);
   w.mem = take((size_t)B * L * 256 * E);
   w.omem = take((size_t)B * L * 256 * E);
   w.elog = take((size_t)B * L * (c.num_classes + 1) * 4);
@@ -402,582 +228,9 @@ RtWs rt_plan(const spe_model* m, int B) {
   return w;
 }
 
-// ---- MobileNetV3_Large packing: eval BatchNorm (eps 1e-5) folded in double, like fold_conv
-void bn_fold(spe_model* m, const std::string& bn, int C, std::vector<double>& scale, std::vector<double>& shift) {
-  scale.assign(C, 1.0);
-  shift.assign(C, 0.0);
-  if (bn.empty()) return;            // a bare conv (MobileNetV3_Small's Conv1 / Conv2): identity
-  const auto& g = m->host[bn + ".weight"];
-  const auto& b = m->host[bn + ".bias"];
-  const auto& rm = m->host[bn + ".running_mean"];
-  const auto& rv = m->host[bn + ".running_var"];
-  for (int c = 0; c < C; ++c) {
-    scale[c] = (double)g[c] / std::sqrt((double)rv[c] + 1e-5);
-    shift[c] = (double)b[c] - (double)rm[c] * scale[c];
-  }
-}
-
-// conv [cout][cin][kh][kw] (+ a bias in front of the norm) + BatchNorm -> rows [cout][(y*kw + x)*cin + ci]
-// (the plain tap-major K order mb_gemm's A loader walks), folded bias.  pool2: the conv reads a 2x2 mean
-// of its input -- folded into a (2kh)x(2kw) kernel of stride 2*stride, pad 2*pad, w/4 per tap (exact).
-Conv mb_conv(spe_model* m, const std::string& wkey, const std::string& bn, const std::string& biaskey, int stride,
-             int pad, bool pool2 = false) {
-  const auto sh = param_shape(m, wkey);
-  const int cout = (int)sh[0], cin = (int)sh[1], kh = (int)sh[2], kw = (int)sh[3];
-  const int f = pool2 ? 2 : 1, KH = kh * f, KW = kw * f, K = KH * KW * cin;
-  std::vector<double> scale, shift;
-  bn_fold(m, bn, cout, scale, shift);
-  const auto& w = m->host[wkey];
-  std::vector<float> rows((size_t)cout * K, 0.f), bias(cout);
-  for (int co = 0; co < cout; ++co) {
-    if (!biaskey.empty()) shift[co] += (double)m->host[biaskey][co] * scale[co];
-    bias[co] = (float)shift[co];
-    for (int ci = 0; ci < cin; ++ci)
-      for (int y = 0; y < KH; ++y)
-        for (int x = 0; x < KW; ++x)
-          rows[(size_t)co * K + (size_t)(y * KW + x) * cin + ci] =
-              (float)((double)w[(((size_t)co * cin + ci) * kh + y / f) * kw + x / f] * scale[co] / (f * f));
-  }
-  Conv c;
-  c.N = cout; c.K = K; c.Kpad = pad64(K); c.Cin = cin; c.KH = KH; c.KW = KW; c.stride = stride * f; c.pad = pad * f;
-  c.w = upload_rows(m, rows, c.N, c.K, c.Kpad);
-  c.bias = upload_f32(m, bias.data(), bias.size());
-  return c;
-}
-
-MbDw mb_dw(spe_model* m, const std::string& wkey, const std::string& bn, int stride) {
-  const auto sh = param_shape(m, wkey);
-  const int C = (int)sh[0], k = (int)sh[2];
-  std::vector<double> scale, shift;
-  bn_fold(m, bn, C, scale, shift);
-  const auto& w = m->host[wkey];
-  std::vector<float> wt((size_t)k * k * C), bias(C);
-  for (int c = 0; c < C; ++c) {
-    bias[c] = (float)shift[c];
-    for (int t = 0; t < k * k; ++t) wt[(size_t)t * C + c] = (float)((double)w[(size_t)c * k * k + t] * scale[c]);
-  }
-  MbDw d;
-  d.C = C; d.k = k; d.stride = stride;
-  d.w = upload_f32(m, wt.data(), wt.size());
-  d.bias = upload_f32(m, bias.data(), bias.size());
-  return d;
-}
-
-void build_mbv3(spe_model* m) {
-  RtMbv3& mb = m->rt->mb;
-  const std::string b = "backbone.";
-  const bool small = m->rt->mb_small;
-  const MbTable tab = mb_table(m->rt->cfg);
-  std::vector<float> entry(MBS_W_FLOATS, 0.f);     // Small: mbs_entry's weights (spe_kernels.h, MBS_W_*)
-  {   // conv1 + bn1: fp32 [27][16] with k = (ci*3 + kh)*3 + kw
-    std::vector<double> scale, shift;
-    bn_fold(m, b + "bn1", 16, scale, shift);
-    const auto& w = m->host[b + "conv1.weight"];
-    std::vector<float> wt(27 * 16), bias(16);
-    for (int c = 0; c < 16; ++c) {
-      bias[c] = (float)shift[c];
-      for (int k = 0; k < 27; ++k) wt[(size_t)k * 16 + c] = (float)((double)w[(size_t)c * 27 + k] * scale[c]);
-    }
-    mb.stem_w = upload_f32(m, wt.data(), wt.size());
-    mb.stem_b = upload_f32(m, bias.data(), bias.size());
-    std::copy(wt.begin(), wt.end(), entry.begin() + MBS_W_STEM);
-    std::copy(bias.begin(), bias.end(), entry.begin() + MBS_W_STEM_B);
-  }
-  // Small: Conv1 / Conv2 are bare convolutions (no BatchNorm, no activation)
-  mb.side_act = small ? MB_ACT_NONE : MB_ACT_HSWISH;
-  mb.conv_b = mb_conv(m, b + "Conv1.weight", small ? "" : b + "Bn1", "", 2, 1, true);
-  if (small) mb.conv_b3 = mb_conv(m, b + "Conv1.weight", "", "", 2, 1);     // over mbs_entry's pooled map
-  mb.conv_c = mb_conv(m, b + "Conv2.weight", small ? "" : b + "Bn2", "", 2, 1);
-  mb.blocks.clear();
-  for (int i = 0; i < tab.n; ++i) {
-    const MbRow& r = tab.rows[i];
-    const std::string p = b + "bneck." + std::to_string(i);
-    MbBlock k;
-    k.cin = r.cin; k.cexp = r.cexp; k.cout = r.cout; k.stride = r.stride;
-    k.act = r.hs ? MB_ACT_HSWISH : MB_ACT_RELU;
-    k.expand = mb_conv(m, p + ".conv1.weight", p + ".bn1", "", 1, 0);
-    k.dw = mb_dw(m, p + ".conv2.weight", p + ".bn2", r.stride);
-    k.se = r.se != 0;
-    if (k.se) {
-      const int h = se_hidden(r.cexp), C = r.cexp;
-      k.se_hidden = h;
-      std::vector<double> scale, shift;
-      bn_fold(m, p + ".se.se.2", h, scale, shift);
-      const auto& w1 = m->host[p + ".se.se.1.weight"];
-      const auto& w2 = m->host[p + ".se.se.4.weight"];
-      std::vector<float> f1((size_t)h * C), b1(h), f2t((size_t)h * C);
-      for (int j = 0; j < h; ++j) {
-        b1[j] = (float)shift[j];
-        for (int c = 0; c < C; ++c) {
-          f1[(size_t)j * C + c] = (float)((double)w1[(size_t)j * C + c] * scale[j]);
-          f2t[(size_t)j * C + c] = w2[(size_t)c * h + j];
-        }
-      }
-      k.se_w1 = upload_f32(m, f1.data(), f1.size());
-      k.se_b1 = upload_f32(m, b1.data(), b1.size());
-      k.se_w2t = upload_f32(m, f2t.data(), f2t.size());
-    }
-    k.project = mb_conv(m, p + ".conv3.weight", p + ".bn3", "", 1, 0);
-    if (r.stride == 1 && r.cin != r.cout) {
-      k.has_skip_pw = true;
-      k.skip_pw = mb_conv(m, p + ".skip.0.weight", p + ".skip.1", "", 1, 0);
-    } else if (r.stride == 2) {
-      k.has_skip_dw = true;
-      k.skip_dw = mb_dw(m, p + ".skip.0.weight", p + ".skip.1", 2);
-      if (r.cin != r.cout) {
-        k.has_skip_pw = true;
-        k.skip_pw = mb_conv(m, p + ".skip.2.weight", p + ".skip.3", p + ".skip.2.bias", 1, 0);
-      }
-    }
-    mb.blocks.push_back(k);
-  }
-  mb.last = mb_conv(m, b + "conv2.weight", b + "bn2", "", 1, 0);
-  if (small) {     // block 0's expand [ci][co], depthwise and skip depthwise [9][16], fp32 with BatchNorm folded
-    const std::string p = b + "bneck.0";
-    std::vector<double> scale, shift;
-    bn_fold(m, p + ".bn1", 16, scale, shift);
-    const auto& w1 = m->host[p + ".conv1.weight"];
-    for (int co = 0; co < 16; ++co) {
-      entry[MBS_W_EXP_B + co] = (float)shift[co];
-      for (int ci = 0; ci < 16; ++ci) entry[MBS_W_EXP + ci * 16 + co] = (float)((double)w1[(size_t)co * 16 + ci] * scale[co]);
-    }
-    const char* dwk[2][2] = {{".conv2.weight", ".bn2"}, {".skip.0.weight", ".skip.1"}};
-    const int off[2][2] = {{MBS_W_DW, MBS_W_DW_B}, {MBS_W_SKIP, MBS_W_SKIP_B}};
-    for (int j = 0; j < 2; ++j) {
-      bn_fold(m, p + dwk[j][1], 16, scale, shift);
-      const auto& w = m->host[p + dwk[j][0]];
-      for (int c = 0; c < 16; ++c) {
-        entry[off[j][1] + c] = (float)shift[c];
-        for (int t = 0; t < 9; ++t) entry[off[j][0] + t * 16 + c] = (float)((double)w[(size_t)c * 9 + t] * scale[c]);
-      }
-    }
-    mb.entry_w = upload_f32(m, entry.data(), entry.size());
-  }
-}
-
-// bytes a backbone's first launch reads per input pixel: the fp32 batch's three channels or the crop's 1 / 3
-inline double image_px_bytes(const ImageSrc& img) { return img.u8 ? (double)img.ch : 12.0; }
-
-// ---- backbone stages: both leave f0 / f1 / f2 (NHWC, strides 8 / 16 / 32) where the hybrid encoder reads them
-int rt_backbone_presnet(spe_model* m, hipStream_t s, const ImageSrc& images, int B, char* ws, const RtWs& w) {
-  const RtModel& r = *m->rt;
-  const auto& c = r.cfg;
-  const int dt = c.dtype, S = c.input_size, E = m->esz;
-  auto P = [&](size_t o) { return (void*)(ws + o); };
-  // conv as an implicit GEMM, or a plain GEMM over NHWC rows when it is 1x1 / stride 1; the
-  // residual R (same row layout as the output) is added before the activation
-  auto cgemm = [&](const char* kind, const Conv& cv, const void* in, int Hin, void* outp, int ldc, int act,
-                   const void* R) {
-    GemmArgs g;
-    int mode = GEMM_CONV;
-    if (cv.KH == 1 && cv.KW == 1 && cv.stride == 1 && cv.pad == 0) {
-      g = linear_args(cv, in, cv.Cin, B * Hin * Hin, outp, ldc);
-      mode = GEMM_LINEAR;
-    } else {
-      g = conv_args(cv, in, B, Hin, Hin, outp, ldc);
-    }
-    g.act = act;
-    g.R = R; g.ldr = ldc;
-    return run_gemm(m, kind, g, mode, s);
-  };
-
-  // ---------------- PResNet-vd (presnet.py:248-265)
-  CK(run_other(m, "eltwise.pack", 0.0, (double)B * S * S * (image_px_bytes(images) + 8 * E), s,
-               [&] { return spe_launch_pack_input(images, P(w.x0), B, S, dt, s); }));
-  int H = S;
-  size_t cur = w.x0;
-  const size_t stem_out[3] = {w.bufA, w.bufB, w.bufA};
-  for (int i = 0; i < 3; ++i) {
-    GemmArgs g = conv_args(r.stem[i], P(cur), B, H, H, P(stem_out[i]), r.stem[i].N);
-    g.act = ACT_RELU;
-    CK(run_gemm(m, "rt.conv.stem", g, GEMM_CONV, s));
-    H = g.Ho;
-    cur = stem_out[i];
-  }
-  const int Hp = (H + 2 - 3) / 2 + 1;
-  CK(run_other(m, "eltwise.maxpool", 0.0, (double)B * 64 * (H * H + Hp * Hp) * E, s,
-               [&] { return spe_launch_maxpool3s2(P(cur), P(w.bufB), B, H, H, 64, Hp, Hp, dt, s); }));
-  H = Hp;
-  cur = w.bufB;
-  const size_t feat[3] = {w.f0, w.f1, w.f2};
-  for (int st = 0; st < 4; ++st)
-    for (int j = 0; j < r.stage_n[st]; ++j) {
-      const RtBlock& b = r.blocks[r.stage_first[st] + j];
-      const int Ho = H / b.stride;
-      const bool last = j == r.stage_n[st] - 1;
-      const size_t outbuf = (last && st > 0) ? feat[st - 1] : (cur == w.bufA ? w.bufB : w.bufA);
-      size_t res = cur;
-      if (b.has_sc) {
-        CK(cgemm(b.stride == 2 ? "rt.conv.short" : "rt.conv.1x1", b.sc, P(cur), H, P(w.sc), b.cout, ACT_NONE, nullptr));
-        res = w.sc;
-      }
-      CK(cgemm(b.bottleneck ? "rt.conv.1x1" : "rt.conv.3x3", b.a, P(cur), H, P(w.t1), b.a.N, ACT_RELU, nullptr));
-      const int Ha = (H + 2 * b.a.pad - b.a.KH) / b.a.stride + 1;
-      if (b.bottleneck) {
-        CK(cgemm("rt.conv.3x3", b.b, P(w.t1), Ha, P(w.t2), b.b.N, ACT_RELU, nullptr));
-        CK(cgemm("rt.conv.1x1", b.c, P(w.t2), Ho, P(outbuf), b.cout, ACT_RELU, P(res)));
-      } else {
-        CK(cgemm("rt.conv.3x3", b.b, P(w.t1), Ha, P(outbuf), b.cout, ACT_RELU, P(res)));
-      }
-      H = Ho;
-      cur = outbuf;
-    }
-  return 0;
-}
-
-// MobileNetV3_Large.forward / MobileNetV3_Small.forward (mobilenetv3.py:206-225, 301-320) at input 256: stem -> x0 [B][128][128][16]; Conv1 (2x2
-// mean folded in) -> f0, Conv2 -> f1; the 15 blocks ping-pong bufA / bufB with the expanded tensor in t1,
-// the depthwise output in t2 and the skip branch in sc; conv2 -> f2.  Small with the fused entry (mbs_entry,
-// SPE_MBS_ENTRY, default on): one launch leaves the 2x2 mean of the stem map in x0 [B][64][64][16] (Conv1 reads
-// it as a plain 3x3/s2), block 0's skip in sc and its depthwise output in t2 with the SE pool partials; the
-// block loop then starts at block 0's SE gate.
-int rt_backbone_mbv3(spe_model* m, hipStream_t s, const ImageSrc& images, int B, char* ws, const RtWs& w) {
-  const RtModel& r = *m->rt;
-  const RtMbv3& mb = r.mb;
-  const int dt = r.cfg.dtype, S = r.cfg.input_size;
-  const double E = m->esz;
-  auto P = [&](size_t o) { return (void*)(ws + o); };
-  // 1x1 conv (or Conv1 / Conv2's implicit GEMM) over an NHWC map of edge Hin
-  auto pw = [&](const Conv& cv, const void* in, int Hin, void* outp, int act, const void* R, const float* scale) {
-    MbGemmArgs g{};
-    const int Ho = (Hin + 2 * cv.pad - cv.KH) / cv.stride + 1;
-    g.A = in; g.lda = cv.Cin;
-    g.Bw = cv.w; g.ldb = cv.Kpad;
-    g.bias = cv.bias; g.scale = scale;
-    g.R = R; g.ldr = cv.N;
-    g.C = outp; g.ldc = cv.N;
-    g.M = B * Ho * Ho; g.N = cv.N; g.K = cv.K;
-    g.H = Hin; g.W = Hin; g.Cin = cv.Cin; g.KH = cv.KH; g.KW = cv.KW; g.stride = cv.stride; g.pad = cv.pad;
-    g.Ho = Ho; g.Wo = Ho;
-    g.act = act;
-    const double a_elems = (double)B * Hin * Hin * cv.Cin;
-    return run_other(m, "conv.pw.mb", 2.0 * g.M * g.N * g.K,
-                     (a_elems + (double)g.N * g.K + (double)g.M * g.N * (R ? 2 : 1)) * E, s,
-                     [&] { return spe_launch_mb_gemm(g, dt, s); });
-  };
-  auto dw = [&](const MbDw& d, const void* in, int Hin, void* outp, int act, float* pool) {
-    MbDwArgs a{};
-    a.in = in; a.out = outp; a.w = d.w; a.bias = d.bias; a.pool = pool;
-    a.B = B; a.H = Hin; a.W = Hin; a.C = d.C; a.k = d.k; a.stride = d.stride; a.act = act;
-    const int Ho = Hin / d.stride;
-    return run_other(m, "conv.dw", 2.0 * B * Ho * Ho * d.C * d.k * d.k,
-                     (double)B * d.C * (Hin * Hin + Ho * Ho) * E, s, [&] { return spe_launch_mb_dwconv(a, dt, s); });
-  };
-  const int H0 = S / 2;
-  const bool fused = r.mb_small && spe_mbs_entry_enabled();
-  if (fused) {
-    if ((size_t)spe_mbs_entry_tiles(S) * 16 > MB_POOL_MAX) return fail(SPE_E_WORKSPACE, "SE pool partials exceed the plan");
-    MbsEntryArgs a{};
-    a.src = images; a.w = mb.entry_w;
-    a.pooled = P(w.x0); a.skip = P(w.sc); a.t2 = P(w.t2); a.pool = (float*)P(w.mbpool);
-    a.B = B; a.S = S;
-    const double px = (double)B * (S / 4) * (S / 4);
-    CK(run_other(m, "conv.entry.mbs", 2.0 * px * 16 * (4 * 27 + 4 * 16 + 9 + 9),
-                 (double)B * S * S * image_px_bytes(images) + 3.0 * px * 16 * E, s,
-                 [&] { return spe_launch_mbs_entry(a, dt, s); }));
-    CK(pw(mb.conv_b3, P(w.x0), S / 4, P(w.f0), mb.side_act, nullptr, nullptr));
-  } else {
-    CK(run_other(m, "conv.stem.mb", 2.0 * B * H0 * H0 * 16 * 27,
-                 (double)B * (S * S * image_px_bytes(images) + H0 * H0 * 16 * E), s,
-                 [&] { return spe_launch_mb_stem(images, mb.stem_w, mb.stem_b, P(w.x0), B, S, dt, s); }));
-    CK(pw(mb.conv_b, P(w.x0), H0, P(w.f0), mb.side_act, nullptr, nullptr));
-  }
-  CK(pw(mb.conv_c, P(w.f0), r.lvl_s[0], P(w.f1), mb.side_act, nullptr, nullptr));
-  int H = H0;
-  size_t cur = w.x0;
-  const size_t sc_pw = w.sc + (((w.f0 - w.sc) / 2) & ~size_t(255));   // second half of sc: the skip branch's 1x1 output
-  bool entry_done = fused;             // block 0's expand, depthwise and skip are already in t2 / sc
-  for (const MbBlock& k : mb.blocks) {
-    const int Ho = H / k.stride;
-    const size_t outbuf = cur == w.bufA ? w.bufB : w.bufA;
-    const bool head = entry_done;
-    entry_done = false;
-    if (!head) CK(pw(k.expand, P(cur), H, P(w.t1), k.act, nullptr, nullptr));
-    float* pool = nullptr;
-    const int tiles = spe_mb_dwconv_tiles(Ho, Ho);
-    if (k.se) {
-      if ((size_t)tiles * k.cexp > MB_POOL_MAX) return fail(SPE_E_WORKSPACE, "SE pool partials exceed the plan");
-      pool = (float*)P(w.mbpool);      // rows [B][tiles][C]: B * tiles * C <= B * MB_POOL_MAX floats
-    }
-    if (!head) CK(dw(k.dw, P(w.t1), H, P(w.t2), k.act, pool));
-    const float* scale = nullptr;
-    if (k.se) {
-      MbSeArgs a{};
-      a.pool = pool; a.tiles = tiles; a.inv_hw = 1.0f / (float)(Ho * Ho);
-      a.w1 = k.se_w1; a.b1 = k.se_b1; a.w2t = k.se_w2t;
-      a.scale = (float*)P(w.mbscale);
-      a.B = B; a.C = k.cexp; a.hidden = k.se_hidden;
-      CK(run_other(m, "rt.se", 4.0 * B * k.cexp * k.se_hidden, ((double)B * (tiles + 1) * k.cexp + 2.0 * k.cexp * k.se_hidden) * 4, s,
-                   [&] { return spe_launch_mb_se_gate(a, s); }));
-      scale = a.scale;
-    }
-    const void* res = P(cur);
-    if (k.has_skip_dw) {
-      if (!head) CK(dw(k.skip_dw, P(cur), H, P(w.sc), MB_ACT_NONE, nullptr));
-      res = P(w.sc);
-    }
-    if (k.has_skip_pw) {
-      CK(pw(k.skip_pw, res, k.has_skip_dw ? Ho : H, P(sc_pw), MB_ACT_NONE, nullptr, nullptr));
-      res = P(sc_pw);
-    }
-    CK(pw(k.project, P(w.t2), Ho, P(outbuf), k.act, res, scale));
-    H = Ho;
-    cur = outbuf;
-  }
-  CK(pw(mb.last, P(cur), H, P(w.f2), MB_ACT_HSWISH, nullptr, nullptr));
-  return 0;
-}
-
-// ---- GhostNetV2 packing.  Inputs and outputs of every conv are in the padded ghost layout (GhLay): weights
-// of a pad lane, as an input column or an output row, and its bias are zero.
-// 1x1 conv [cout][cin] + BatchNorm -> rows [N][Cp(cin)]; half_out: the output is a ghost half (N = pad8(cout),
-// rows in order), else a whole ghost tensor (N = Cp(cout), rows at GhLay(cout).phys)
-Conv gh_pw(spe_model* m, const std::string& conv, const std::string& bn, bool half_out) {
-  const auto sh = param_shape(m, conv + ".weight");
-  const int cout = (int)sh[0], cin = (int)sh[1];
-  const GhLay li(cin), lo(cout);
-  const int K = li.Cp(), N = half_out ? (cout + 7) & ~7 : lo.Cp();
-  std::vector<double> scale, shift;
-  bn_fold(m, bn, cout, scale, shift);
-  const auto& w = m->host[conv + ".weight"];
-  std::vector<float> rows((size_t)N * K, 0.f), bias(N, 0.f);
-  for (int co = 0; co < cout; ++co) {
-    const int n = half_out ? co : lo.phys(co);
-    bias[n] = (float)shift[co];
-    for (int ci = 0; ci < cin; ++ci) rows[(size_t)n * K + li.phys(ci)] = (float)((double)w[(size_t)co * cin + ci] * scale[co]);
-  }
-  Conv c;
-  c.N = N; c.K = K; c.Kpad = pad64(K); c.Cin = K; c.KH = 1; c.KW = 1; c.stride = 1; c.pad = 0;
-  c.w = upload_rows(m, rows, c.N, c.K, c.Kpad);
-  c.bias = upload_f32(m, bias.data(), bias.size());
-  return c;
-}
-
-// depthwise conv [C][1][kh][kw] + BatchNorm -> fp32 taps [kh*kw][Cp] and bias [Cp]; half: C is a ghost half
-// (lanes in order, Cp = pad8(C)), else a whole ghost tensor
-void gh_dw_pack(spe_model* m, const std::string& conv, const std::string& bn, bool half, float** wd, float** bd, int* Cp,
-                int* k) {
-  const auto sh = param_shape(m, conv + ".weight");
-  const int C = (int)sh[0], taps = (int)(sh[2] * sh[3]);
-  const GhLay l(C);
-  const int P = half ? (C + 7) & ~7 : l.Cp();
-  std::vector<double> scale, shift;
-  bn_fold(m, bn, C, scale, shift);
-  const auto& w = m->host[conv + ".weight"];
-  std::vector<float> wt((size_t)taps * P, 0.f), bias(P, 0.f);
-  for (int c = 0; c < C; ++c) {
-    const int pc = half ? c : l.phys(c);
-    bias[pc] = (float)shift[c];
-    for (int t = 0; t < taps; ++t) wt[(size_t)t * P + pc] = (float)((double)w[(size_t)c * taps + t] * scale[c]);
-  }
-  *wd = upload_f32(m, wt.data(), wt.size());
-  *bd = upload_f32(m, bias.data(), bias.size());
-  if (Cp) *Cp = P;
-  if (k) *k = (int)sh[2];
-}
-
-MbDw gh_dw(spe_model* m, const std::string& conv, const std::string& bn, int stride) {
-  MbDw d;
-  gh_dw_pack(m, conv, bn, false, &d.w, &d.bias, &d.C, &d.k);
-  d.stride = stride;
-  return d;
-}
-
-GhModule gh_module(spe_model* m, const std::string& p, bool attn) {
-  GhModule g;
-  g.primary = gh_pw(m, p + ".primary_conv.0", p + ".primary_conv.1", true);
-  gh_dw_pack(m, p + ".cheap_operation.0", p + ".cheap_operation.1", true, &g.cheap_w, &g.cheap_b, &g.half_p, nullptr);
-  g.attn = attn;
-  if (attn) {
-    g.short_pw = gh_pw(m, p + ".short_conv.0", p + ".short_conv.1", false);
-    gh_dw_pack(m, p + ".short_conv.2", p + ".short_conv.3", false, &g.dfc_w1, &g.dfc_b1, nullptr, nullptr);
-    gh_dw_pack(m, p + ".short_conv.4", p + ".short_conv.5", false, &g.dfc_w2, &g.dfc_b2, nullptr, nullptr);
-  }
-  return g;
-}
-
-void build_ghost(spe_model* m) {
-  RtGhost& gh = m->rt->gh;
-  const std::string b = "backbone.";
-  {   // conv_stem: fp32 [27][16] with k = (ci*3 + kh)*3 + kw; bn1 stays apart (the raw output is needed too)
-    std::vector<double> scale, shift;
-    bn_fold(m, b + "bn1", 16, scale, shift);
-    const auto& w = m->host[b + "conv_stem.weight"];
-    std::vector<float> wt(27 * 16), sc(16), sf(16);
-    for (int c = 0; c < 16; ++c) {
-      sc[c] = (float)scale[c];
-      sf[c] = (float)shift[c];
-      for (int k = 0; k < 27; ++k) wt[(size_t)k * 16 + c] = w[(size_t)c * 27 + k];
-    }
-    gh.stem_w = upload_f32(m, wt.data(), wt.size());
-    gh.stem_scale = upload_f32(m, sc.data(), sc.size());
-    gh.stem_shift = upload_f32(m, sf.data(), sf.size());
-  }
-  gh.conv_b = mb_conv(m, b + "Conv1.weight", b + "Bn1", "", 2, 1, true);
-  gh.conv_c = mb_conv(m, b + "Conv2.weight", b + "Bn2", "", 2, 1);
-  gh.blocks.clear();
-  int cin = 16;
-  for (int i = 0; i < 16; ++i) {
-    const GhRow& r = GHOSTV2[i];
-    const std::string p = gh_key(r);
-    GhBlock k;
-    k.cin_p = GhLay(cin).Cp(); k.mid_p = GhLay(r.mid).Cp(); k.cout_p = GhLay(r.cout).Cp();
-    k.k = r.k; k.stride = r.stride;
-    k.g1 = gh_module(m, p + ".ghost1", i >= GH_ATTN_FROM);
-    if (r.stride > 1) k.dw = gh_dw(m, p + ".conv_dw", p + ".bn_dw", r.stride);
-    k.se = r.se != 0;
-    if (k.se) {
-      const int h = gh_se_hidden(r.mid), C = r.mid, Cp = k.mid_p;
-      const GhLay l(C);
-      k.se_hidden = h;
-      const auto& w1 = m->host[p + ".se.conv_reduce.weight"];
-      const auto& w2 = m->host[p + ".se.conv_expand.weight"];
-      const auto& b2 = m->host[p + ".se.conv_expand.bias"];
-      std::vector<float> f1((size_t)h * Cp, 0.f), f2t((size_t)h * Cp, 0.f), fb2(Cp, 0.f);
-      for (int c = 0; c < C; ++c) {
-        fb2[l.phys(c)] = b2[c];
-        for (int j = 0; j < h; ++j) {
-          f1[(size_t)j * Cp + l.phys(c)] = w1[(size_t)j * C + c];
-          f2t[(size_t)j * Cp + l.phys(c)] = w2[(size_t)c * h + j];
-        }
-      }
-      k.se_w1 = upload_f32(m, f1.data(), f1.size());
-      k.se_b1 = upload_key(m, p + ".se.conv_reduce.bias");
-      k.se_w2t = upload_f32(m, f2t.data(), f2t.size());
-      k.se_b2 = upload_f32(m, fb2.data(), fb2.size());
-    }
-    k.g2 = gh_module(m, p + ".ghost2", false);
-    k.has_sc = !(cin == r.cout && r.stride == 1);
-    if (k.has_sc) {
-      k.sc_dw = gh_dw(m, p + ".shortcut.0", p + ".shortcut.1", r.stride);
-      k.sc_pw = gh_pw(m, p + ".shortcut.2", p + ".shortcut.3", false);
-    }
-    gh.blocks.push_back(k);
-    cin = r.cout;
-  }
-  gh.head = gh_pw(m, b + "blocks.9.0.conv", b + "blocks.9.0.bn1", false);
-  gh.last = gh_pw(m, b + "Conv3", b + "Bn3", false);
-}
-
-// GhostNetV2.forward (ghostnetv2.py:418-441) at input 256: stem -> raw (x0) and relu(bn1) (bufA), both
-// [B][128][128][16]; Conv1 (2x2 mean folded in) over raw -> f0, Conv2 -> f1; the 16 blocks ping-pong bufA /
-// bufB with a module's primary output in t1, ghost1's output in t2 and, in eighths of sc, the stride-2
-// depthwise output (2), the pooled input, the DFC branch's 1x1 output, its gate, the shortcut's depthwise
-// and 1x1 outputs; blocks.9.0 -> t2, Conv3 -> f2
-int rt_backbone_ghostv2(spe_model* m, hipStream_t s, const ImageSrc& images, int B, char* ws, const RtWs& w) {
-  const RtModel& r = *m->rt;
-  const RtGhost& gh = r.gh;
-  const int dt = r.cfg.dtype, S = r.cfg.input_size;
-  const double E = m->esz;
-  auto P = [&](size_t o) { return (void*)(ws + o); };
-  const size_t eighth = (size_t)B * S * S * 2 * m->esz;      // of a `big` buffer: 131072 elements an image at 256
-  const size_t sc_dw = w.sc, sc_pool = w.sc + 2 * eighth, sc_res = w.sc + 3 * eighth, sc_gate = w.sc + 4 * eighth,
-               sc_sdw = w.sc + 5 * eighth, sc_spw = w.sc + 6 * eighth;
-  auto fits = [&](size_t elems_per_image, size_t eighths) { return elems_per_image * B * m->esz <= eighths * eighth; };
-  auto pw = [&](const Conv& cv, const void* in, int Hin, void* outp, int act, const float* scale) {
-    MbGemmArgs g{};
-    const int Ho = (Hin + 2 * cv.pad - cv.KH) / cv.stride + 1;
-    g.A = in; g.lda = cv.Cin;
-    g.Bw = cv.w; g.ldb = cv.Kpad;
-    g.bias = cv.bias; g.scale = scale;
-    g.C = outp; g.ldc = cv.N;
-    g.M = B * Ho * Ho; g.N = cv.N; g.K = cv.K;
-    g.H = Hin; g.W = Hin; g.Cin = cv.Cin; g.KH = cv.KH; g.KW = cv.KW; g.stride = cv.stride; g.pad = cv.pad;
-    g.Ho = Ho; g.Wo = Ho;
-    g.act = act;
-    return run_other(m, "conv.pw.mb", 2.0 * g.M * g.N * g.K,
-                     ((double)B * Hin * Hin * cv.Cin + (double)g.N * g.K + (double)g.M * g.N) * E, s,
-                     [&] { return spe_launch_mb_gemm(g, dt, s); });
-  };
-  auto dw = [&](const MbDw& d, const void* in, int Hin, void* outp, float* pool) {
-    MbDwArgs a{};
-    a.in = in; a.out = outp; a.w = d.w; a.bias = d.bias; a.pool = pool;
-    a.B = B; a.H = Hin; a.W = Hin; a.C = d.C; a.k = d.k; a.stride = d.stride; a.act = MB_ACT_NONE;
-    const int Ho = Hin / d.stride;
-    return run_other(m, "conv.dw", 2.0 * B * Ho * Ho * d.C * d.k * d.k,
-                     (double)B * d.C * (Hin * Hin + Ho * Ho) * E, s, [&] { return spe_launch_mb_dwconv(a, dt, s); });
-  };
-  // x1 (t1, [B][H][H][half_p]) -> out [B][H][H][2 half_p]
-  auto cheap = [&](const GhModule& g, int H, void* outp, int act, int post, const void* gate, const void* resid, float* pool) {
-    GhCheapArgs a{};
-    a.x1 = P(w.t1); a.ldx = g.half_p; a.xoff = 0;
-    a.w = g.cheap_w; a.bias = g.cheap_b; a.out = outp; a.gate = gate; a.resid = resid; a.pool = pool;
-    a.B = B; a.H = H; a.W = H; a.half = g.half_p; a.act = act; a.post = post;
-    const double px = (double)B * H * H * g.half_p;
-    return run_other(m, "conv.ghost", 2.0 * px * 9, px * (3 + (post == GH_POST_RESIDUAL ? 2 : 0)) * E, s,
-                     [&] { return spe_launch_gh_cheap(a, dt, s); });
-  };
-  const int H0 = S / 2;
-  CK(run_other(m, "conv.stem.gh", 2.0 * B * H0 * H0 * 16 * 27,
-               (double)B * (S * S * image_px_bytes(images) + 2.0 * H0 * H0 * 16 * E), s, [&] {
-    return spe_launch_gh_stem(images, gh.stem_w, gh.stem_scale, gh.stem_shift, P(w.x0), P(w.bufA), B, S, dt, s);
-  }));
-  CK(pw(gh.conv_b, P(w.x0), H0, P(w.f0), MB_ACT_HSWISH, nullptr));
-  CK(pw(gh.conv_c, P(w.f0), r.lvl_s[0], P(w.f1), MB_ACT_HSWISH, nullptr));
-  int H = H0;
-  size_t cur = w.bufA;
-  for (const GhBlock& k : gh.blocks) {
-    const int Ho = H / k.stride;
-    const size_t outbuf = cur == w.bufA ? w.bufB : w.bufA;
-    // t2 holds ghost1's output; the slices of sc hold what only some blocks make
-    if (!fits((size_t)H * H * k.mid_p, 8) || (k.stride > 1 && !fits((size_t)Ho * Ho * k.mid_p, 2)) ||
-        (k.g1.attn && !fits((size_t)(H / 2) * (H / 2) * (k.mid_p > k.cin_p ? k.mid_p : k.cin_p), 1)) ||
-        (k.has_sc && (!fits((size_t)Ho * Ho * k.cout_p, 1) || !fits((size_t)Ho * Ho * k.cin_p, 1))))
-      return fail(SPE_E_WORKSPACE, "GhostNetV2 block buffers exceed the plan");
-    // ghost1: the DFC gate first (mode "attn"), then primary -> t1, cheap + gate -> t2
-    const void* gate = nullptr;
-    if (k.g1.attn) {
-      const int Hp = H / 2;
-      CK(run_other(m, "eltwise.pool2", 0.0, (double)B * k.cin_p * (H * H + Hp * Hp) * E, s,
-                   [&] { return spe_launch_gh_pool2(P(cur), P(sc_pool), B, H, H, k.cin_p, dt, s); }));
-      CK(pw(k.g1.short_pw, P(sc_pool), Hp, P(sc_res), MB_ACT_NONE, nullptr));
-      GhDfcArgs a{};
-      a.x = P(sc_res); a.gate = P(sc_gate);
-      a.w1 = k.g1.dfc_w1; a.b1 = k.g1.dfc_b1; a.w2 = k.g1.dfc_w2; a.b2 = k.g1.dfc_b2;
-      a.B = B; a.H = Hp; a.W = Hp; a.C = k.mid_p;
-      CK(run_other(m, "conv.dfc", 2.0 * B * Hp * Hp * k.mid_p * 25, 2.0 * B * Hp * Hp * k.mid_p * E, s,
-                   [&] { return spe_launch_gh_dfc(a, dt, s); }));
-      gate = a.gate;
-    }
-    CK(pw(k.g1.primary, P(cur), H, P(w.t1), MB_ACT_RELU, nullptr));
-    float* pool = nullptr;
-    const int tiles = spe_mb_dwconv_tiles(Ho, Ho);      // gh_cheap tiles the same 8 x 8 grid
-    if (k.se) {
-      if ((size_t)tiles * k.mid_p > MB_POOL_MAX) return fail(SPE_E_WORKSPACE, "SE pool partials exceed the plan");
-      pool = (float*)P(w.mbpool);
-    }
-    CK(cheap(k.g1, H, P(w.t2), MB_ACT_RELU, gate ? GH_POST_GATE : GH_POST_NONE, gate, nullptr, k.stride == 1 ? pool : nullptr));
-    const void* mid = P(w.t2);
-    if (k.stride > 1) {
-      CK(dw(k.dw, P(w.t2), H, P(sc_dw), pool));
-      mid = P(sc_dw);
-    }
-    const float* scale = nullptr;
-    if (k.se) {
-      MbSeArgs a{};
-      a.pool = pool; a.tiles = tiles; a.inv_hw = 1.0f / (float)(Ho * Ho);
-      a.w1 = k.se_w1; a.b1 = k.se_b1; a.w2t = k.se_w2t; a.b2 = k.se_b2;
-      a.scale = (float*)P(w.mbscale);
-      a.B = B; a.C = k.mid_p; a.hidden = k.se_hidden;
-      CK(run_other(m, "rt.se", 4.0 * B * k.mid_p * k.se_hidden, ((double)B * (tiles + 1) * k.mid_p + 2.0 * k.mid_p * k.se_hidden) * 4, s,
-                   [&] { return spe_launch_mb_se_gate(a, s); }));
-      scale = a.scale;
-    }
-    // shortcut, then ghost2: primary (SE scale on A) -> t1, cheap + residual -> the block's output
-    const void* res = P(cur);
-    if (k.has_sc) {
-      CK(dw(k.sc_dw, P(cur), H, P(sc_sdw), nullptr));
-      CK(pw(k.sc_pw, P(sc_sdw), Ho, P(sc_spw), MB_ACT_NONE, nullptr));
-      res = P(sc_spw);
-    }
-    CK(pw(k.g2.primary, mid, Ho, P(w.t1), MB_ACT_NONE, scale));
-    CK(cheap(k.g2, Ho, P(outbuf), MB_ACT_NONE, GH_POST_RESIDUAL, nullptr, res, nullptr));
-    H = Ho;
-    cur = outbuf;
-  }
-  CK(pw(gh.head, P(cur), H, P(w.t2), MB_ACT_RELU, nullptr));
-  CK(pw(gh.last, P(w.t2), H, P(w.f2), MB_ACT_HSWISH, nullptr));
-  return 0;
+// BACKBONE: images -> f0 / f1 / f2
+int rt_backbone_stage(spe_model* m, hipStream_t s, const ImageSrc& images, int B, char* ws, const RtWs& w) {
+  return m->rt->bb->run(m, s, images, B, ws, w);
 }
 
 }  // namespace
@@ -986,57 +239,7 @@ int spe_rtdetr_build_device(spe_model* m) {
   RtModel& r = *m->rt;
   const auto& c = r.cfg;
   const int d = 256;
-  r.blocks.clear();
-  if (r.mbv3 || r.ghost) {
-    if (r.ghost) build_ghost(m);
-    else build_mbv3(m);
-    r.fch[0] = 128; r.fch[1] = 256; r.fch[2] = 512;
-  } else {
-  const std::string bb = "backbone.conv1.conv1_";
-  r.stem[0] = make_conv(m, bb + "1.conv.weight", bb + "1.norm", "", 8, 2, 1);
-  r.stem[1] = make_conv(m, bb + "2.conv.weight", bb + "2.norm", "", 0, 1, 1);
-  r.stem[2] = make_conv(m, bb + "3.conv.weight", bb + "3.norm", "", 0, 1, 1);
-  const bool bott = c.depth >= 50;
-  const int* nb = bott ? RESNET_CFG50 : RESNET_CFG18;
-  const int widths[4] = {64, 128, 256, 512}, exp = bott ? 4 : 1;
-  int cin = 64;
-  for (int i = 0; i < 4; ++i) {
-    r.stage_first[i] = (int)r.blocks.size();
-    r.stage_n[i] = nb[i];
-    for (int j = 0; j < nb[i]; ++j) {
-      const std::string p = "backbone.res_layers." + std::to_string(i) + ".blocks." + std::to_string(j);
-      RtBlock b;
-      b.bottleneck = bott;
-      b.stride = (j == 0 && i > 0) ? 2 : 1;
-      b.cin = cin;
-      b.cout = widths[i] * exp;
-      if (bott) {
-        b.a = make_conv(m, p + ".branch2a.conv.weight", p + ".branch2a.norm", "", 0, 1, 0);
-        b.b = make_conv(m, p + ".branch2b.conv.weight", p + ".branch2b.norm", "", 0, b.stride, 1);
-        b.c = make_conv(m, p + ".branch2c.conv.weight", p + ".branch2c.norm", "", 0, 1, 0);
-      } else {
-        b.a = make_conv(m, p + ".branch2a.conv.weight", p + ".branch2a.norm", "", 0, b.stride, 1);
-        b.b = make_conv(m, p + ".branch2b.conv.weight", p + ".branch2b.norm", "", 0, 1, 1);
-      }
-      if (j == 0) {
-        b.has_sc = true;
-        if (b.stride == 2) {     // AvgPool2d(2, 2, ceil_mode) + ConvNormLayer(1x1) == 2x2/2 conv, w/4 per tap
-          std::vector<float> w1, bias;
-          fold_conv(m, p + ".short.conv.conv.weight", p + ".short.conv.norm", "", w1, bias);
-          std::vector<float> w4((size_t)b.cout * cin * 4);
-          for (size_t k = 0; k < (size_t)b.cout * cin; ++k)
-            for (int t = 0; t < 4; ++t) w4[k * 4 + t] = w1[k] * 0.25f;
-          b.sc = pack_conv(m, w4, bias, b.cout, cin, 2, 2, 0, 2, 0);
-        } else {
-          b.sc = make_conv(m, p + ".short.conv.weight", p + ".short.norm", "", 0, 1, 0);
-        }
-      }
-      r.blocks.push_back(b);
-      cin = b.cout;
-    }
-  }
-  for (int l = 0; l < 3; ++l) r.fch[l] = r.blocks[r.stage_first[l + 1]].cout;
-  }
+  CK(r.bb->build(m));
   for (int l = 0; l < 3; ++l) {
     const std::string p = "encoder.input_proj." + std::to_string(l);
     r.in_proj[l] = make_conv(m, p + ".0.weight", p + ".1", "", 0, 1, 0);
@@ -1110,9 +313,7 @@ int spe_rtdetr_backbone(spe_model* m, hipStream_t s, const float* images, int B,
   if ((int64_t)w.total > ws_bytes) return fail(SPE_E_WORKSPACE, "workspace too small");
   const RtModel& r = *m->rt;
   char* ws = (char*)workspace;
-  const ImageSrc src{images, nullptr, 0};
-  CK(r.ghost ? rt_backbone_ghostv2(m, s, src, B, ws, w)
-     : r.mbv3 ? rt_backbone_mbv3(m, s, src, B, ws, w) : rt_backbone_presnet(m, s, src, B, ws, w));
+  CK(rt_backbone_stage(m, s, ImageSrc{images, nullptr, 0}, B, ws, w));
   const size_t off[3] = {w.f0, w.f1, w.f2};
   for (int l = 0; l < 3; ++l) {
     if (f) f[l] = ws + off[l];
@@ -1126,17 +327,11 @@ extern "C" {
 
 int spe_rtdetr_create(const spe_rtdetr_config* cfg, spe_model** out) {
   if (!cfg || !out) return fail(SPE_E_ARG, "null argument");
-  if (cfg->depth != 18 && cfg->depth != 50 && !is_mbv3(*cfg) && !is_ghost(*cfg))
+  const RtBackbone* bb = rt_backbone_for(*cfg);
+  if (!bb)
     return fail(SPE_E_ARG, "depth must be a PResNet depth (18 or 50), SPE_RTDETR_MBV3_LARGE, SPE_RTDETR_MBV3_SMALL or "
                            "SPE_RTDETR_GHOSTNETV2");
-  if (is_ghost(*cfg) && cfg->input_size != 256)
-    return fail(SPE_E_ARG, "GhostNetV2 supports input_size 256 only: the backbone resizes its raw stem output to a "
-                           "hard-coded 64x64, which is the stride-4 grid the stride-8 / 16 levels are built from "
-                           "only at 256");
-  if (is_mbv3(*cfg) && cfg->input_size != 256)
-    return fail(SPE_E_ARG, "MobileNetV3_Large / _Small support input_size 256 only: the backbone resizes its stem output to "
-                           "a hard-coded 64x64, which is the stride-4 grid the stride-8 / 16 levels are built from "
-                           "only at 256");
+  if (const char* why = bb->refuses(*cfg)) return fail(SPE_E_ARG, why);
   if (cfg->input_size % 32 || cfg->input_size < 64) return fail(SPE_E_ARG, "input_size must be a multiple of 32, >= 64");
   if (cfg->num_queries < 1 || cfg->num_queries > 64) return fail(SPE_E_ARG, "num_queries must be in [1, 64]");
   if (cfg->dec_layers < 1 || cfg->enc_ff % 64 || cfg->dec_ff % 64 || cfg->csp_hidden % 64 || cfg->csp_hidden < 64 ||
@@ -1147,14 +342,13 @@ int spe_rtdetr_create(const spe_rtdetr_config* cfg, spe_model** out) {
   m->family = 1;
   m->rt = new RtModel();
   m->rt->cfg = *cfg;
-  m->rt->mbv3 = is_mbv3(*cfg);
-  m->rt->mb_small = is_mbv3_small(*cfg);
-  m->rt->ghost = is_ghost(*cfg);
+  m->rt->bb = bb;
+  bb->channels(*cfg, m->rt->fch);
   m->esz = cfg->dtype == SPE_DTYPE_BF16_ ? 2 : 4;
   m->cfg.dtype = cfg->dtype;
   m->cfg.input_size = cfg->input_size;
   m->cfg.num_queries = cfg->num_queries;
-  m->spec = rt_spec(*cfg);
+  m->spec = rt_spec(*m->rt);
   RtModel& r = *m->rt;
   r.L = 0;
   for (int l = 0; l < 3; ++l) {
@@ -1460,11 +654,8 @@ int rt_forward_stages(spe_model* m, void* stream, const ImageSrc& images, bool u
   if (!m->finalized) return fail(SPE_E_STATE, "model not finalized");
   const RtWs w = rt_plan(m, B);
   if ((int64_t)w.total > ws_bytes) return fail(SPE_E_WORKSPACE, "workspace too small");
-  const RtModel& r = *m->rt;
   const RtFwd f{m, w, (char*)workspace, (hipStream_t)stream, B};
-  if (stages & SPE_STAGE_BACKBONE)
-    CK(r.ghost ? rt_backbone_ghostv2(m, f.s, images, B, f.ws, w)
-       : r.mbv3 ? rt_backbone_mbv3(m, f.s, images, B, f.ws, w) : rt_backbone_presnet(m, f.s, images, B, f.ws, w));
+  if (stages & SPE_STAGE_BACKBONE) CK(rt_backbone_stage(m, f.s, images, B, f.ws, w));
   // (a stage's failing launch has recorded its own error)
   if (stages & SPE_STAGE_TRANSFORMER)
     if (const int rc = rt_encoder_stage(f)) return rc;

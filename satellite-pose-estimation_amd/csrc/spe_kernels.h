@@ -396,7 +396,7 @@ int spe_launch_ensemble_fuse(const EnsembleArgs& a, hipStream_t s);
 int spe_launch_postprocess(const float* logits, const float* points, const float* clip_bbox, int B, int Q,
                            float* probs, float* points_px, hipStream_t s);
 
-// ---- UNC RT-DETR (rtdetr.hip, rtdetr_model.cpp)
+// ---- UNC RT-DETR (rtdetr.hip; rtdetr_model.cpp and, for the backbone kernels below, its rtdetr_<family>.cpp files)
 // nearest x2 (mode 0) / bicubic x0.5 (mode 1) resample of NHWC [B][H][W][C] (row stride ldi)
 // into [B][Ho][Wo] rows of stride ldo (a channel slice of a concat buffer)
 int spe_launch_resample2x(const void* in, int ldi, void* out, int ldo, int B, int H, int W, int C, int mode, int dtype,

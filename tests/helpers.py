@@ -77,14 +77,17 @@ LAUNCH_TABLE_MODES = {"bf16": ("bf16", None), "bf16_attn_fp16": ("bf16", "fp16")
 # s128_q11_l2 in bf16 and fp32h3, also: encode then decode as two calls (their tables concatenated), the
 # 8-bit crop entry, and a call that fills the aux outputs
 LAUNCH_TABLE_VARIANTS = ["split", "u8", "aux"]
-LAUNCH_TABLE_RTDETR = "rtdetr_r18_s128-fp32"
+# RT-DETR cases, "<golden>-<dtype>": BasicBlock and BottleNeck PResNet, then the three light backbones (the
+# MobileNetV3_Small case takes the default fused entry)
+LAUNCH_TABLE_RTDETR = ["rtdetr_r18_s128-fp32", "rtdetr_r50_s256-bf16", "rtdetr_mbv3l_s256-fp32", "rtdetr_mbv3s_s256-bf16",
+                       "rtdetr_ghostv2_s256-fp32"]
 
 
 def launch_table_cases():
     """Case names of tests/golden/launch_tables.json."""
     names = [f"{t}-{m}" for t in LAUNCH_TABLE_TAGS for m in LAUNCH_TABLE_MODES]
     names += [f"s128_q11_l2-{m}-{v}" for m in ("bf16", "fp32h3") for v in LAUNCH_TABLE_VARIANTS]
-    return names + [LAUNCH_TABLE_RTDETR]
+    return names + LAUNCH_TABLE_RTDETR
 
 
 _lt_models = {}
@@ -100,13 +103,14 @@ def run_launch_table_case(name, dev):
     from spe.config import SpeConfig
     from spe.synthetic import random_weights, synthetic_batch
     golden = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
-    if name == LAUNCH_TABLE_RTDETR:
+    if name in LAUNCH_TABLE_RTDETR:
         from spe.rtdetr import RTDETR
         from spe.rtdetr_spec import RtdetrConfig, random_rtdetr_weights
-        g = np.load(os.path.join(golden, "rtdetr_r18_s128.npz"))
+        tag, dtype = name.split("-")
+        g = np.load(os.path.join(golden, tag + ".npz"))
         cfg = RtdetrConfig(**json.loads(str(g["config"])))
         if name not in _lt_models:
-            _lt_models[name] = RTDETR(cfg, "fp32")
+            _lt_models[name] = RTDETR(cfg, dtype)
             _lt_models[name].load_state_dict(random_rtdetr_weights(cfg, int(g["weight_seed"])))
         m = _lt_models[name]
         b = synthetic_batch(SpeConfig(input_size=cfg.input_size), int(g["batch"]), int(g["image_seed"]))
