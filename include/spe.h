@@ -258,8 +258,8 @@ int spe_forward_stages_u8(spe_model* m, void* stream, const uint8_t* crops, int 
  * Either map may be NULL (that tap is skipped), not both.  Negative layer indices count from the end; the
  * reference's choice is enc_layer = -1, dec_layer = -2.  Graph-capturable like spe_forward.  Model dtypes
  * BF16_ (attn_dtype F16_ included) and F32_; SPE_E_ARG, before anything is launched, for the split-precision
- * modes (F32X3_ / F32X6_ / F32H3_: their operands live as split planes), an RT-DETR handle, a layer index out
- * of range, both maps NULL.  The workspace is spe_forward_attention_workspace_bytes (today equal to
+ * modes (F32X3_ / F32X6_ / F32H3_: their operands live as split planes), an RT-DETR handle (that family's entry
+ * is spe_rtdetr_forward_attention), a layer index out of range, both maps NULL. The workspace is spe_forward_attention_workspace_bytes (today equal to
  * spe_model_workspace_bytes: every served mode leaves q and k in the forward's own workspace). */
 int64_t spe_forward_attention_workspace_bytes(const spe_model* m, int batch);
 int spe_forward_attention(spe_model* m, void* stream, const float* images, int batch, void* workspace,
@@ -293,6 +293,31 @@ int spe_rtdetr_forward_stages(spe_model* m, void* stream, const float* images, i
  * the fp32 batch normalised that way. */
 int spe_rtdetr_forward_stages_u8(spe_model* m, void* stream, const uint8_t* crops, int channels, int batch,
                                  void* workspace, int64_t workspace_bytes, const spe_rtdetr_outputs* out, int stages);
+
+/* spe_rtdetr_forward that also exports attention maps (spe_forward_attention is the DETR entry and refuses an
+ * RT-DETR handle; this one refuses a DETR handle).  All maps are device fp32, each nullable, not all four:
+ *   enc_map      [B][T5][T5], T5 = (input_size / 32)^2: the AIFI layer's self-attention (encoder.encoder.0.layers.0.
+ *                self_attn), the probabilities averaged over the 8 heads, row = query token, y * W + x order: the
+ *                map kernel of spe_forward_attention (attn_map.hip) on the q / k the AIFI attention kernel reads
+ *   dec_map      [B][Q][L], L = the memory tokens of one image in the reference's order (level-major: stride 8,
+ *                16, 32; y * W_l + x inside a level): decoder.decoder.layers[dec_layer].cross_attn.  The multi-scale
+ *                deformable attention forms no matrix: per head it reads levels x points = 12 bilinear samples with
+ *                softmaxed weights w.  dec_map[b][q][t] = (1/8) sum_h sum_samples w . (the sample's bilinear weight
+ *                on cell t), which is the matrix with cross_attn's sampled output = dec_map_h . value_h.  Corners off
+ *                a level read grid_sample's zero padding and are dropped: a row sums to <= 1, the rest fell off the maps
+ *   dec_loc      [B][Q][8][3][4][2]: the normalised sampling locations (x, y) in crop coordinates,
+ *                reference point + offset / (W_l, H_l)
+ *   dec_weights  [B][Q][8][3][4]: the weights w (softmax over a head's 12 samples)
+ * The launch sequence of spe_rtdetr_forward (`out` is bit-identical) plus one launch of the map kernel for enc_map
+ * and one of rt_deform_map (rtdetr.hip) after the tapped layer's msdeform; no host synchronisation, no
+ * allocation.  Negative dec_layer counts from the end (-1: the last layer, whose points are the output).  The
+ * workspace is spe_model_workspace_bytes.  Refusals, before any launch and in this order: a null handle /
+ * workspace or batch <= 0, a DETR handle ("not an RT-DETR model"), null images / out / out->logits /
+ * out->points, all four maps NULL, dec_layer out of range (all SPE_E_ARG); a model not finalized (SPE_E_STATE);
+ * a workspace below spe_model_workspace_bytes (SPE_E_WORKSPACE).  (ABI 9 addition) */
+int spe_rtdetr_forward_attention(spe_model* m, void* stream, const float* images, int batch, void* workspace,
+                                 int64_t workspace_bytes, const spe_rtdetr_outputs* out, int dec_layer,
+                                 float* enc_map, float* dec_map, float* dec_loc, float* dec_weights);
 
 /* Validation input pipeline on the device (SpeedTrain.__getitem__ with train=False,
  * REV/datasets/speed.py:209-233): generate_clip_bbox_val (:246-258), Pillow crop,
@@ -736,6 +761,14 @@ int spe_debug_rt_head_finish(void* stream, int dtype, int rows, int Q, int C, co
 int spe_debug_rt_msdeform(void* stream, int dtype, const void* value, int ldv, const float* so_aw, int ld_so,
                           const float* ref, void* out, int ldo, int rows, int Q, int heads, int levels, int points,
                           const int* lvl_h, const int* lvl_w, const int* lvl_rows0);
+/* rt_deform_map: the head-averaged attention map of one rt_msdeform call (spe_rtdetr_forward_attention's decoder
+ * tap) from the same so_aw / ref / level sizes; it reads no value, so it has no dtype.  map [rows][L] (L = sum of
+ * H_l * W_l, columns level-major, y * W_l + x; cells no sample touches are exactly 0), loc [rows][heads][levels]
+ * [points][2], weights [rows][heads][levels][points]: each nullable, not all three.  No atomics and a fixed
+ * summation order: two runs are bit-identical.  heads 8, 1 <= levels <= 4, 1 <= points <= 4, L <= 12288. */
+int spe_debug_rt_deform_map(void* stream, const float* so_aw, int ld_so, const float* ref, int rows, int Q, int heads,
+                            int levels, int points, const int* lvl_h, const int* lvl_w, float* map, float* loc,
+                            float* weights);
 
 #ifdef __cplusplus
 }

@@ -575,4 +575,17 @@ int spe_debug_rt_msdeform(void* stream, int dtype, const void* value, int ldv, c
   return spe_launch_msdeform(a, dtype, (hipStream_t)stream);
 }
 
+int spe_debug_rt_deform_map(void* stream, const float* so_aw, int ld_so, const float* ref, int rows, int Q, int heads,
+                            int levels, int points, const int* lvl_h, const int* lvl_w, float* map, float* loc,
+                            float* weights) {
+  RtDeformMapArgs a{};
+  a.so_aw = so_aw; a.ld_so = ld_so; a.ref = ref; a.map = map; a.loc = loc; a.weights = weights;
+  a.rows = rows; a.Q = Q; a.heads = heads; a.levels = levels; a.points = points;
+  for (int l = 0; l < 4 && l < levels; ++l) {                                   // (levels > 4 is refused below)
+    a.lvl_h[l] = lvl_h[l]; a.lvl_w[l] = lvl_w[l];
+    a.lvl_start[l + 1] = a.lvl_start[l] + lvl_h[l] * lvl_w[l];
+  }
+  return spe_launch_deform_map(a, (hipStream_t)stream);
+}
+
 }  // extern "C"

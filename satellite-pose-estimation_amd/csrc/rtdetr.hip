@@ -21,6 +21,8 @@
 //                  per (query, head) softmax over levels x points of the attention logits,
 //                  sampling location = ref + offset / (W_l, H_l), bilinear grid_sample
 //                  (align_corners=False, zero padding) of the level's value map, weighted sum
+//   deform_map     the head-averaged attention map of one msdeform call over the image's memory tokens
+//                  (no reference counterpart: the diagnostic tap of spe_rtdetr_forward_attention)
 //
 // Memory (the decoder's value input) is level-major: rows [level][image][y * W_l + x].
 #include "spe_common.h"
@@ -277,6 +279,95 @@ __global__ __launch_bounds__(256) void msdeform_kernel(RtDeformArgs a) {
   ((T*)a.out)[(size_t)row * a.ldo + tid] = from_f32<T>(acc);
 }
 
+// ---------------------------------------------------------------- deform_map
+// The attention map msdeform never forms (the diagnostic tap of spe_rtdetr_forward_attention): per query
+// row, the weight each memory token receives, averaged over the heads,
+//   map[row][lvl_start[l] + y W_l + x] = (1/H) sum_h sum_p w[h,l,p] . (bilinear corner weight of sample
+//   (h,l,p) at cell (y, x)),
+// corners off the level dropped (what grid_sample's zero padding reads there), so a row sums to <= 1.
+// One workgroup of 256 threads per query row, three steps:
+//   1. softmax and sample positions into LDS: msdeform_kernel's own statements (tests/
+//      test_gpu_rtdetr_attention.py runs both kernels on the same operands: map . value == msdeform's output)
+//   2. the <= H*NL*NP*4 (token, weight) pairs of the row into LDS, sample-major (h, l, p, nw/ne/sw/se);
+//      a corner off the level is (-1, 0)
+//   3. thread t owns tokens t, t + 256, ..., DM_TOK of them per sweep of the pair list, each summed in list
+//      order and stored once: no atomics, a fixed summation order, untouched tokens exactly 0.
+constexpr int DM_NT = 256;
+constexpr int DM_TOK = 4;
+constexpr int DM_MAXL = 12288;
+
+__global__ __launch_bounds__(DM_NT) void deform_map_kernel(RtDeformMapArgs a) {
+  constexpr int MAXP = 8 * 4 * 4;      // heads x levels x points
+  __shared__ float w[MAXP], lx[MAXP], ly[MAXP];
+  __shared__ int ptok[4 * MAXP];
+  __shared__ float pwt[4 * MAXP];
+  const int row = blockIdx.x, tid = threadIdx.x;
+  const int H = a.heads, NL = a.levels, NP = a.points, LP = NL * NP;
+  const float* so = a.so_aw + (size_t)row * a.ld_so;        // [H][NL][NP][2] offsets, then [H][NL*NP] logits
+  const float rx = a.ref[2 * row], ry = a.ref[2 * row + 1];
+  if (tid < H) {
+    const float* lg = so + 2 * H * LP + tid * LP;
+    float mx = lg[0];
+    for (int i = 1; i < LP; ++i) mx = fmaxf(mx, lg[i]);
+    float s = 0.f;
+    for (int i = 0; i < LP; ++i) { const float e = expf(lg[i] - mx); w[tid * LP + i] = e; s += e; }
+    for (int i = 0; i < LP; ++i) w[tid * LP + i] = w[tid * LP + i] / s;
+  }
+  if (tid < H * LP) {
+    const int l = (tid % LP) / NP;
+    const float Wl = (float)a.lvl_w[l], Hl = (float)a.lvl_h[l];
+    const float locx = rx + so[2 * tid] / Wl, locy = ry + so[2 * tid + 1] / Hl;
+    const float gx = 2.f * locx - 1.f, gy = 2.f * locy - 1.f;
+    lx[tid] = ((gx + 1.f) * Wl - 1.f) / 2.f;
+    ly[tid] = ((gy + 1.f) * Hl - 1.f) / 2.f;
+    if (a.loc) {
+      float* lo = a.loc + ((size_t)row * H * LP + tid) * 2;
+      lo[0] = locx;
+      lo[1] = locy;
+    }
+  }
+  __syncthreads();
+  if (tid < H * LP) {
+    const int s = tid, l = (tid % LP) / NP;
+    const int Wl = a.lvl_w[l], Hl = a.lvl_h[l];
+    const float ix = lx[s], iy = ly[s];
+    const float fx = floorf(ix), fy = floorf(iy);
+    const int x0 = (int)fx, y0 = (int)fy;
+    const float tx = ix - fx, ty = iy - fy;
+    const float nw = (1.f - tx) * (1.f - ty), ne = tx * (1.f - ty), sw = (1.f - tx) * ty, se = tx * ty;
+    const float ws = w[s];
+    if (a.weights) a.weights[(size_t)row * H * LP + s] = ws;
+    auto put = [&](int c, int y, int x, float bw) {
+      const bool in = x >= 0 && x < Wl && y >= 0 && y < Hl;
+      ptok[4 * s + c] = in ? a.lvl_start[l] + y * Wl + x : -1;
+      pwt[4 * s + c] = in ? ws * bw : 0.f;
+    };
+    put(0, y0, x0, nw);
+    put(1, y0, x0 + 1, ne);
+    put(2, y0 + 1, x0, sw);
+    put(3, y0 + 1, x0 + 1, se);
+  }
+  if (!a.map) return;
+  __syncthreads();
+  const int L = a.lvl_start[NL], np4 = 4 * H * LP;
+  const float inv_h = 1.f / (float)H;
+  float* mrow = a.map + (size_t)row * L;
+  for (int t0 = tid; t0 < L; t0 += DM_NT * DM_TOK) {
+    float acc[DM_TOK];
+#pragma unroll
+    for (int j = 0; j < DM_TOK; ++j) acc[j] = 0.f;
+    for (int i = 0; i < np4; ++i) {
+      const int dtok = ptok[i] - t0;
+      const float v = pwt[i];
+#pragma unroll
+      for (int j = 0; j < DM_TOK; ++j) acc[j] += dtok == j * DM_NT ? v : 0.f;
+    }
+#pragma unroll
+    for (int j = 0; j < DM_TOK; ++j)
+      if (t0 + j * DM_NT < L) mrow[t0 + j * DM_NT] = acc[j] * inv_h;
+  }
+}
+
 }  // namespace
 
 int spe_launch_resample2x(const void* in, int ldi, void* out, int ldo, int B, int H, int W, int C, int mode, int dtype,
@@ -322,6 +413,17 @@ int spe_launch_msdeform(const RtDeformArgs& a, int dtype, hipStream_t s) {
   if (a.heads * 32 != 256 || a.heads * a.levels * a.points > 128 || a.levels > 4 || a.points > 4) return -5;
   if (dtype == SPE_DTYPE_BF16) hipLaunchKernelGGL(msdeform_kernel<bf16>, dim3(a.rows), dim3(256), 0, s, a);
   else hipLaunchKernelGGL(msdeform_kernel<float>, dim3(a.rows), dim3(256), 0, s, a);
+  return (int)hipGetLastError();
+}
+
+int spe_launch_deform_map(const RtDeformMapArgs& a, hipStream_t s) {
+  if (a.rows <= 0) return 0;
+  if (a.heads != 8 || a.levels < 1 || a.levels > 4 || a.points < 1 || a.points > 4) return -5;
+  if (a.lvl_start[a.levels] > DM_MAXL || (!a.map && !a.loc && !a.weights)) return -5;
+  if (!a.so_aw || !a.ref || a.lvl_start[0] != 0) return -5;
+  for (int l = 0; l < a.levels; ++l)      // the map's columns are exactly the levels' cells
+    if (a.lvl_h[l] < 1 || a.lvl_w[l] < 1 || a.lvl_start[l + 1] - a.lvl_start[l] != a.lvl_h[l] * a.lvl_w[l]) return -5;
+  hipLaunchKernelGGL(deform_map_kernel, dim3(a.rows), dim3(DM_NT), 0, s, a);
   return (int)hipGetLastError();
 }
 

@@ -368,12 +368,22 @@ namespace {
 
 // One forward call's context: the stages below are the launch sequence of RTDETR.forward cut at the
 // two points where everything the rest reads lies in the workspace (include/spe.h, staging contract).
+// spe_rtdetr_forward_attention's taps: device fp32 buffers (each nullable) and the tapped decoder layer
+struct RtTap {
+  int dec_layer;
+  float* enc_map;       // [B][T5][T5]
+  float* dec_map;       // [B][Q][L]
+  float* dec_loc;       // [B][Q][8][3][4][2]
+  float* dec_weights;   // [B][Q][8][3][4]
+};
+
 struct RtFwd {
   spe_model* m;
   const RtWs& w;
   char* ws;
   hipStream_t s;
   int B;
+  const RtTap* tap;     // null: the plain forward
   void* P(size_t o) const { return (void*)(ws + o); }
 };
 
@@ -412,6 +422,15 @@ int rt_encoder_stage(const RtFwd& f) {
     at.o = P(w.aao); at.ldo = d;
     at.B = B; at.H = 8; at.Tq = T; at.Tk = T; at.scale = 1.0f / std::sqrt(32.0f);
     CK(run_attn(m, "rt.attn.aifi", at, dt, s));
+    if (f.tap && f.tap->enc_map) {   // the map of the q / k the attention kernel just read
+      AttnMapArgs am{};
+      am.q = at.q; am.q_sb = (long long)T * 2 * d; am.q_sh = 32; am.ldq = 2 * d;
+      am.k = at.k; am.k_sb = am.q_sb; am.k_sh = 32; am.ldk = 2 * d;
+      am.out = f.tap->enc_map;
+      am.B = B; am.H = 8; am.Tq = T; am.Tk = T; am.head_dim = 32; am.scale = at.scale;
+      CK(run_other(m, "rt.attn_map.aifi", 2.0 * 2.0 * B * 8.0 * T * (double)T * 32,
+                   (double)B * T * (double)T * 4 + 2.0 * M * d * E, s, [&] { return spe_launch_attn_map(am, dt, s); }));
+    }
     GemmArgs go = linear_args(r.ao, P(w.aao), d, M, P(w.atmp), d);
     go.R = P(w.aout); go.ldr = d;
     CK(run_gemm(m, "rt.aifi.o", go, GEMM_LINEAR, s));
@@ -595,6 +614,16 @@ int rt_decoder_stage(const RtFwd& f, const spe_rtdetr_outputs* out) {
       da.lvl_rows0[l] = B * r.lvl_start[l];
     }
     CK(run_other(m, "rt.msdeform", 0.0, (double)BQ * 96 * 4 * 32 * E, s, [&] { return spe_launch_msdeform(da, dt, s); }));
+    if (f.tap && i == f.tap->dec_layer && (f.tap->dec_map || f.tap->dec_loc || f.tap->dec_weights)) {
+      RtDeformMapArgs dm{};       // this layer's so_aw (the next layer overwrites it) and reference points
+      dm.so_aw = da.so_aw; dm.ld_so = da.ld_so; dm.ref = ref;
+      dm.map = f.tap->dec_map; dm.loc = f.tap->dec_loc; dm.weights = f.tap->dec_weights;
+      dm.rows = BQ; dm.Q = Q; dm.heads = 8; dm.levels = 3; dm.points = 4;
+      for (int l = 0; l < 3; ++l) dm.lvl_h[l] = dm.lvl_w[l] = r.lvl_s[l];
+      for (int l = 0; l < 4; ++l) dm.lvl_start[l] = r.lvl_start[l];
+      CK(run_other(m, "rt.attn_map.deform", 0.0, (double)BQ * ((dm.map ? r.L : 0) + 96 * 6) * 4, s,
+                   [&] { return spe_launch_deform_map(dm, s); }));
+    }
     GemmArgs gc = linear_args(e.oproj, P(w.dcr), d, BQ, P(w.dtmp), d);
     gc.R = P(w.t1d); gc.ldr = d;
     CK(run_gemm(m, "rt.gemm.dec", gc, GEMM_LINEAR, s));
@@ -654,7 +683,7 @@ int rt_forward_stages(spe_model* m, void* stream, const ImageSrc& images, bool u
   if (!m->finalized) return fail(SPE_E_STATE, "model not finalized");
   const RtWs w = rt_plan(m, B);
   if ((int64_t)w.total > ws_bytes) return fail(SPE_E_WORKSPACE, "workspace too small");
-  const RtFwd f{m, w, (char*)workspace, (hipStream_t)stream, B};
+  const RtFwd f{m, w, (char*)workspace, (hipStream_t)stream, B, nullptr};
   if (stages & SPE_STAGE_BACKBONE) CK(rt_backbone_stage(m, f.s, images, B, f.ws, w));
   // (a stage's failing launch has recorded its own error)
   if (stages & SPE_STAGE_TRANSFORMER)
@@ -681,6 +710,27 @@ int spe_rtdetr_forward_stages(spe_model* m, void* stream, const float* images, i
 int spe_rtdetr_forward_stages_u8(spe_model* m, void* stream, const uint8_t* crops, int channels, int B, void* workspace,
                                  int64_t ws_bytes, const spe_rtdetr_outputs* out, int stages) {
   return rt_forward_stages(m, stream, ImageSrc{nullptr, crops, channels}, true, B, workspace, ws_bytes, out, stages);
+}
+
+int spe_rtdetr_forward_attention(spe_model* m, void* stream, const float* images, int B, void* workspace, int64_t ws_bytes,
+                                 const spe_rtdetr_outputs* out, int dec_layer, float* enc_map, float* dec_map,
+                                 float* dec_loc, float* dec_weights) {
+  if (!m || !workspace || B <= 0) return fail(SPE_E_ARG, "bad argument");
+  if (m->family != 1) return fail(SPE_E_ARG, "not an RT-DETR model");
+  if (!images) return fail(SPE_E_ARG, "null images");
+  if (!out || !out->logits || !out->points) return fail(SPE_E_ARG, "null outputs");
+  if (!enc_map && !dec_map && !dec_loc && !dec_weights) return fail(SPE_E_ARG, "attention maps: every map null");
+  const int nd = m->rt->cfg.dec_layers;
+  const int dl = dec_layer < 0 ? dec_layer + nd : dec_layer;
+  if (dl < 0 || dl >= nd) return fail(SPE_E_ARG, "attention maps: dec_layer out of range");
+  if (!m->finalized) return fail(SPE_E_STATE, "model not finalized");
+  const RtWs w = rt_plan(m, B);
+  if ((int64_t)w.total > ws_bytes) return fail(SPE_E_WORKSPACE, "workspace too small");
+  const RtTap tap{dl, enc_map, dec_map, dec_loc, dec_weights};
+  const RtFwd f{m, w, (char*)workspace, (hipStream_t)stream, B, &tap};
+  CK(rt_backbone_stage(m, f.s, ImageSrc{images, nullptr, 0}, B, f.ws, w));
+  if (const int rc = rt_encoder_stage(f)) return rc;
+  return rt_decoder_stage(f, out);
 }
 
 }  // extern "C"

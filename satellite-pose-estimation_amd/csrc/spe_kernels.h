@@ -424,6 +424,20 @@ struct RtDeformArgs {
   int lvl_h[4], lvl_w[4], lvl_rows0[4];
 };
 int spe_launch_msdeform(const RtDeformArgs& a, int dtype, hipStream_t s);
+// The head-averaged map of one msdeform call (the diagnostic tap of spe_rtdetr_forward_attention): the weight
+// every memory token of the row's image receives through the bilinear corners of the 8 x levels x points
+// samples.  Reads what msdeform reads but the value, so one kernel serves both model dtypes.
+struct RtDeformMapArgs {
+  const float* so_aw; int ld_so;   // as RtDeformArgs
+  const float* ref;                // [rows][2]
+  float* map;                      // [rows][L] token order of one image: level-major, y * W_l + x (nullable)
+  float* loc;                      // [rows][H][NL][NP][2] normalised sampling locations (x, y) (nullable)
+  float* weights;                  // [rows][H][NL][NP] softmaxed attention weights (nullable)
+  int rows, Q, heads, levels, points;
+  int lvl_h[4], lvl_w[4];
+  int lvl_start[5];                // per-image token offsets, [levels] = L <= 12288
+};
+int spe_launch_deform_map(const RtDeformMapArgs& a, hipStream_t s);   // -5: arguments outside the contract
 struct RtHeadArgs {
   int rows, Q, C;
   const float* hs;                 // [rows][256] fp32 layer output (score head input; null: no score head)

@@ -62,7 +62,7 @@ EXPORTS = ["spe_abi_version", "spe_last_error", "spe_model_create", "spe_model_c
            "spe_debug_mb_stem", "spe_debug_mbs_entry_tiles", "spe_debug_mbs_entry",
            "spe_debug_ghost_cheap", "spe_debug_dfc_gate", "spe_debug_se_gate_bias", "spe_debug_pool2",
            "spe_debug_rt_resample2x", "spe_debug_rt_query_select", "spe_debug_rt_qpos_hidden", "spe_debug_rt_head_finish",
-           "spe_debug_rt_msdeform",
+           "spe_debug_rt_msdeform", "spe_debug_rt_deform_map", "spe_rtdetr_forward_attention",
            "spe_forward_attention", "spe_forward_attention_workspace_bytes", "spe_debug_attn_map",
            "spe_debug_ffn_pre", "spe_debug_oproj_pre"]
 
@@ -192,6 +192,8 @@ def load(path: str):
     L.spe_debug_rt_qpos_hidden.argtypes = [P, I, P, P, P, P, I, I]
     L.spe_debug_rt_head_finish.argtypes = [P, I, I, I, I, P, P, P, P, I, P, P, P, P, P, I, P, P, P, P, P, P, P]
     L.spe_debug_rt_msdeform.argtypes = [P, I, P, I, P, I, P, P, I, I, I, I, I, I, IP, IP, IP]
+    L.spe_debug_rt_deform_map.argtypes = [P, P, I, P, I, I, I, I, I, IP, IP, P, P, P]
+    L.spe_rtdetr_forward_attention.argtypes = [P, P, P, I, P, I64, ctypes.POINTER(RtdetrOutputs), I, P, P, P, P]
     L.spe_jpeg_workspace_bytes.argtypes = [I, I, I, I64]
     L.spe_jpeg_workspace_bytes.restype = I64
     L.spe_jpeg_decode.argtypes = [P, P, P, P, I, I, I, I64, P, P, P, I64]

@@ -25,6 +25,30 @@ def decoder_heatmaps(dec_map, feat: int):
     return m.reshape(m.shape[0], m.shape[1], feat, feat)
 
 
+def rtdetr_decoder_heatmaps(dec_map, level_sizes):
+    """The RT-DETR decoder map (RTDETR.forward_with_attention's "dec_map" [B,Q,L], tokens level-major, row-major
+    inside a level) as images.  level_sizes: the side s_l of each level's map, finest first (maps["level_sizes"]).
+    Returns (per_level, combined): per_level[l] is [B,Q,s_l,s_l] (a view); combined [B,Q,s_0,s_0] is every level
+    on the finest grid, a coarser cell's weight spread equally over the k x k finest cells it covers (each gets
+    weight / k^2, k = s_0 / s_l), so combined.sum((-1, -2)) == dec_map.sum(-1): the mass is kept."""
+    sizes = [int(s) for s in level_sizes]
+    m = torch.as_tensor(dec_map)
+    if m.dim() != 3 or m.shape[-1] != sum(s * s for s in sizes):
+        raise ValueError(f"dec_map: expected [B, Q, {sum(s * s for s in sizes)}], got {tuple(m.shape)}")
+    if not sizes or any(s < 1 or sizes[0] % s for s in sizes):
+        raise ValueError(f"level_sizes: sides dividing the finest one, got {sizes}")
+    B, Q = m.shape[:2]
+    per_level, start = [], 0
+    for s in sizes:
+        per_level.append(m[..., start:start + s * s].reshape(B, Q, s, s))
+        start += s * s
+    combined = torch.zeros(B, Q, sizes[0], sizes[0], dtype=m.dtype, device=m.device)
+    for s, lv in zip(sizes, per_level):
+        k = sizes[0] // s
+        combined += (lv / (k * k)).repeat_interleave(k, dim=-2).repeat_interleave(k, dim=-1)
+    return per_level, combined
+
+
 def encoder_heatmaps_at(enc_map, points_norm, feat: int):
     """visualize_enc_features: for each predicted keypoint, the encoder self-attention that every token
     pays to the token under that keypoint.  The reference views the [T,T] map as [qy,qx,ky,kx] and

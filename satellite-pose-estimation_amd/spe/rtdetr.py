@@ -201,6 +201,51 @@ class RTDETR(nn.Module):
         self._run(images, B, self.workspace(B, dev, stream), stream, o, _lib.SPE_STAGE_ENCODE | _lib.SPE_STAGE_DECODE)
         return out
 
+    def forward_with_attention(self, samples, dec_layer=-1, clip_bbox=None, stream=None, enc=True, points=True):
+        """forward() plus where the model looked (spe_rtdetr_forward_attention).  Returns (out, maps): `out` is
+        forward()'s dict, bit for bit; `maps` holds device fp32 tensors
+          "enc_map"     [B,T5,T5], T5 = (S/32)^2: the AIFI layer's self-attention averaged over the heads (row =
+                        query token; attention_maps.encoder_heatmaps_at with feat = S/32); enc=False skips it
+          "dec_map"     [B,Q,L]: the weight query q's deformable cross-attention of decoder layer `dec_layer` puts
+                        on each memory token, averaged over the heads; tokens level-major (stride 8, 16, 32), row-major
+                        inside a level (attention_maps.rtdetr_decoder_heatmaps).  Rows sum to <= 1: samples that
+                        fall off a level read zeros
+          "dec_points"  [B,Q,8,3,4,2] the sampling locations (x, y), crop-normalised, and
+          "dec_weights" [B,Q,8,3,4] their softmaxed weights; points=False skips both
+        and "level_sizes", the side of each level's map.  Negative dec_layer counts from the end.  fp32 batches
+        only (the u8 crop form is forward()'s)."""
+        if not self._ready:
+            raise RuntimeError("RTDETR: load_state_dict() with every parameter before forward_with_attention()")
+        if isinstance(samples, (list, tuple)):
+            samples = nested_tensor_from_tensor_list(list(samples))
+        images = samples.tensors if isinstance(samples, NestedTensor) else samples
+        if not images.is_cuda:
+            raise RuntimeError("RTDETR (HIP) expects device tensors")
+        images = images.contiguous().float()
+        B, C3, H, W = images.shape
+        S = self.cfg.input_size
+        if C3 != 3 or H != S or W != S:
+            raise ValueError(f"expected [B,3,{S},{S}] input, got {tuple(images.shape)}")
+        dev = images.device
+        if clip_bbox is not None:
+            clip_bbox = clip_bbox.to(device=dev, dtype=torch.float32).contiguous()
+        out, o = self._outputs(B, dev, clip_bbox, self.aux_outputs, False)
+        sizes = list(self.cfg.level_sizes)
+        Q, T5, L = self.cfg.num_queries, sizes[-1] ** 2, sum(s * s for s in sizes)
+        maps = {"dec_map": torch.empty(B, Q, L, device=dev)}
+        if enc:
+            maps["enc_map"] = torch.empty(B, T5, T5, device=dev)
+        if points:
+            maps["dec_points"] = torch.empty(B, Q, 8, len(sizes), 4, 2, device=dev)
+            maps["dec_weights"] = torch.empty(B, Q, 8, len(sizes), 4, device=dev)
+        ws = self.workspace(B, dev, stream)
+        _lib.check(_lib.lib().spe_rtdetr_forward_attention(
+            self._h, _lib.stream_ptr(stream), _lib.ptr(images), B, _lib.ptr(ws), ws.numel(), ctypes.byref(o),
+            int(dec_layer), _lib.ptr(maps.get("enc_map")), _lib.ptr(maps["dec_map"]), _lib.ptr(maps.get("dec_points")),
+            _lib.ptr(maps.get("dec_weights"))), "spe_rtdetr_forward_attention")
+        maps["level_sizes"] = sizes
+        return out, maps
+
     def backbone_features(self, images, stream=None):
         """The backbone stage alone (spe_debug_rtdetr_backbone): the stride 8 / 16 / 32 maps as fp32 NCHW."""
         if not self._ready:
