@@ -770,6 +770,37 @@ int spe_debug_rt_deform_map(void* stream, const float* so_aw, int ld_so, const f
                             int levels, int points, const int* lvl_h, const int* lvl_w, float* map, float* loc,
                             float* weights);
 
+/* DETR stem, neck and head helpers (elementwise.hip, heads.hip; additions, ABI 9 unchanged).  As the rt hooks:
+ * the launcher's own code, 0, a hipError_t, or -5 / -6 when the arguments are outside the kernel's contract
+ * (refused before any launch; spe_last_error is not set); a null required pointer is SPE_E_ARG.
+ * pack_input: the crop batch, images_f32 [B][3][S][S] or (when that is null) crops_u8 [B][S][S][channels]
+ * (channels 1: gray into all three, or 3; normalised (u / 255 - mean) / std in fp32) -> NHWC out [B][S][S][cpad]:
+ * dtype BF16_ cpad 8, F32_ cpad 8 or 4; the pad channels are +0.  amax (nullable, F32_ only; BF16_ ignores it):
+ * one fp32 slot raised to max |x| when that is larger, never lowered.  Neither source, or channels not 1 / 3: -5. */
+int spe_debug_pack_input(void* stream, int dtype, const float* images_f32, const void* crops_u8, int channels, void* out,
+                         int B, int S, int cpad, float* amax);
+/* pack_input_pad4: the same sources -> bf16 out [B][S+6][S+6][4], the image inside a 3-pixel border; the border
+ * and channel 3 are written as zeros on every call. */
+int spe_debug_pack_input_pad4(void* stream, const float* images_f32, const void* crops_u8, int channels, void* out, int B,
+                              int S);
+/* maxpool3s2: 3 x 3 / stride 2 / pad 1 max-pool (-inf padding), NHWC in [B][H][W][C] T -> out [B][Ho][Wo] rows of
+ * stride ldo T (0 = C; a channel slice of a concat buffer), Ho = (H - 1) / 2 + 1, Wo likewise.  C and ldo
+ * multiples of the 16-byte chunk (8 bf16, 4 fp32), ldo >= C, else -5. */
+int spe_debug_maxpool3s2(void* stream, int dtype, const void* in, void* out, int B, int H, int W, int C, int ldo);
+/* upsample2x: bilinear x2, align_corners=True, NHWC in [B][H][W][C] T -> out [B][2H][2W][C] T; C a multiple of
+ * the 16-byte chunk, else -5. */
+int spe_debug_upsample2x(void* stream, int dtype, const void* in, void* out, int B, int H, int W, int C);
+/* heads: the class / point / sigma heads fused with PostProcess on hs [B*Q][256] fp32, D == 256 (else -6);
+ * weights transposed [in][out] as the kernel reads them: cls_wt [256][12], pt_w0t / pt_w1t [256][256], pt_w2t
+ * [256][2], sg_* the same with sg_w2t [256][1] (sg_w0t null: no sigma head).  logits [B*Q][12], points [B*Q][2]
+ * (sigmoid); probs (nullable) softmax; points_px (nullable, needs clip_bbox [B][4]) = points * (x1 - x0, y1 - y0)
+ * + (x0, y0) of image row / Q; log_sigmas, sigmas (nullable) [B*Q][2], both columns equal.  B * Q == 0: 0. */
+int spe_debug_heads(void* stream, const float* hs, int B, int Q, int D, const float* cls_wt, const float* cls_b,
+                    const float* pt_w0t, const float* pt_b0, const float* pt_w1t, const float* pt_b1, const float* pt_w2t,
+                    const float* pt_b2, const float* sg_w0t, const float* sg_b0, const float* sg_w1t, const float* sg_b1,
+                    const float* sg_w2t, const float* sg_b2, const float* clip_bbox, float* logits, float* points,
+                    float* probs, float* points_px, float* log_sigmas, float* sigmas);
+
 #ifdef __cplusplus
 }
 #endif

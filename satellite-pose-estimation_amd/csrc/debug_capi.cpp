@@ -588,4 +588,55 @@ int spe_debug_rt_deform_map(void* stream, const float* so_aw, int ld_so, const f
   return spe_launch_deform_map(a, (hipStream_t)stream);
 }
 
+// ---- DETR stem, neck and head helpers (elementwise.hip, heads.hip).  Like the rt hooks: the launcher's own code
+// (0, a hipError_t, -5 / -6 for arguments outside the kernel's contract, refused before any launch).
+int spe_debug_pack_input(void* stream, int dtype, const float* images_f32, const void* crops_u8, int channels, void* out,
+                         int B, int S, int cpad, float* amax) {
+  if (!out || B < 0 || S < 1) return spe_fail(SPE_E_ARG, "bad argument");
+  if (dtype != SPE_DTYPE_BF16 && dtype != SPE_DTYPE_F32) return spe_fail(SPE_E_ARG, "bad dtype");
+  const ImageSrc src{images_f32, (const uint8_t*)crops_u8, channels};
+  return spe_launch_pack_input(src, out, B, S, dtype, (hipStream_t)stream, amax, cpad);
+}
+
+int spe_debug_pack_input_pad4(void* stream, const float* images_f32, const void* crops_u8, int channels, void* out, int B,
+                              int S) {
+  if (!out || B < 0 || S < 1) return spe_fail(SPE_E_ARG, "bad argument");
+  const ImageSrc src{images_f32, (const uint8_t*)crops_u8, channels};
+  return spe_launch_pack_input_pad4(src, out, B, S, (hipStream_t)stream);
+}
+
+int spe_debug_maxpool3s2(void* stream, int dtype, const void* in, void* out, int B, int H, int W, int C, int ldo) {
+  if (!in || !out || B < 0 || H < 1 || W < 1 || C < 1) return spe_fail(SPE_E_ARG, "bad argument");
+  if (dtype != SPE_DTYPE_BF16 && dtype != SPE_DTYPE_F32) return spe_fail(SPE_E_ARG, "bad dtype");
+  const int Ho = (H - 1) / 2 + 1, Wo = (W - 1) / 2 + 1;     // (forward.cpp's)
+  return spe_launch_maxpool3s2(in, out, B, H, W, C, Ho, Wo, dtype, (hipStream_t)stream, ldo);
+}
+
+int spe_debug_upsample2x(void* stream, int dtype, const void* in, void* out, int B, int H, int W, int C) {
+  if (!in || !out || B < 0 || H < 1 || W < 1 || C < 1) return spe_fail(SPE_E_ARG, "bad argument");
+  if (dtype != SPE_DTYPE_BF16 && dtype != SPE_DTYPE_F32) return spe_fail(SPE_E_ARG, "bad dtype");
+  return spe_launch_upsample2x(in, out, B, H, W, C, dtype, (hipStream_t)stream);
+}
+
+int spe_debug_heads(void* stream, const float* hs, int B, int Q, int D, const float* cls_wt, const float* cls_b,
+                    const float* pt_w0t, const float* pt_b0, const float* pt_w1t, const float* pt_b1, const float* pt_w2t,
+                    const float* pt_b2, const float* sg_w0t, const float* sg_b0, const float* sg_w1t, const float* sg_b1,
+                    const float* sg_w2t, const float* sg_b2, const float* clip_bbox, float* logits, float* points,
+                    float* probs, float* points_px, float* log_sigmas, float* sigmas) {
+  if (!hs || !cls_wt || !cls_b || !pt_w0t || !pt_b0 || !pt_w1t || !pt_b1 || !pt_w2t || !pt_b2 || !logits || !points ||
+      B < 0 || Q < 1)
+    return spe_fail(SPE_E_ARG, "bad argument");
+  if (sg_w0t && (!sg_b0 || !sg_w1t || !sg_b1 || !sg_w2t || !sg_b2))
+    return spe_fail(SPE_E_ARG, "heads: a sigma head needs its three weight / bias pairs");
+  HeadArgs a{};
+  a.hs = hs; a.B = B; a.Q = Q; a.D = D;
+  a.cls_wt = cls_wt; a.cls_b = cls_b;
+  a.pt_w0t = pt_w0t; a.pt_b0 = pt_b0; a.pt_w1t = pt_w1t; a.pt_b1 = pt_b1; a.pt_w2t = pt_w2t; a.pt_b2 = pt_b2;
+  a.sg_w0t = sg_w0t; a.sg_b0 = sg_b0; a.sg_w1t = sg_w1t; a.sg_b1 = sg_b1; a.sg_w2t = sg_w2t; a.sg_b2 = sg_b2;
+  a.clip_bbox = clip_bbox;
+  a.logits = logits; a.points = points; a.probs = probs; a.points_px = points_px;
+  a.log_sigmas = log_sigmas; a.sigmas = sigmas;
+  return spe_launch_heads(a, (hipStream_t)stream);
+}
+
 }  // extern "C"

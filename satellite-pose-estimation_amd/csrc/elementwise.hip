@@ -378,6 +378,7 @@ int spe_launch_upconv_combine(const void* z, void* out, int ldo, int B, int H, i
 int spe_launch_layernorm(const void* x, const float* gamma, const float* beta, void* out, float* out_f32, int M, int D,
                          int dtype, hipStream_t s) {
   if (D != 256) return -6;
+  if (M == 0) return 0;                           // (an empty grid is an invalid launch configuration)
   const int rows_per_block = 4;
   dim3 grid((M + rows_per_block - 1) / rows_per_block), block(64 * rows_per_block);
   if (dtype == SPE_DTYPE_BF16)

@@ -64,7 +64,9 @@ EXPORTS = ["spe_abi_version", "spe_last_error", "spe_model_create", "spe_model_c
            "spe_debug_rt_resample2x", "spe_debug_rt_query_select", "spe_debug_rt_qpos_hidden", "spe_debug_rt_head_finish",
            "spe_debug_rt_msdeform", "spe_debug_rt_deform_map", "spe_rtdetr_forward_attention",
            "spe_forward_attention", "spe_forward_attention_workspace_bytes", "spe_debug_attn_map",
-           "spe_debug_ffn_pre", "spe_debug_oproj_pre"]
+           "spe_debug_ffn_pre", "spe_debug_oproj_pre",
+           "spe_debug_pack_input", "spe_debug_pack_input_pad4", "spe_debug_maxpool3s2", "spe_debug_upsample2x",
+           "spe_debug_heads"]
 
 
 class ModelConfig(ctypes.Structure):
@@ -193,6 +195,11 @@ def load(path: str):
     L.spe_debug_rt_head_finish.argtypes = [P, I, I, I, I, P, P, P, P, I, P, P, P, P, P, I, P, P, P, P, P, P, P]
     L.spe_debug_rt_msdeform.argtypes = [P, I, P, I, P, I, P, P, I, I, I, I, I, I, IP, IP, IP]
     L.spe_debug_rt_deform_map.argtypes = [P, P, I, P, I, I, I, I, I, IP, IP, P, P, P]
+    L.spe_debug_pack_input.argtypes = [P, I, P, P, I, P, I, I, I, P]
+    L.spe_debug_pack_input_pad4.argtypes = [P, P, P, I, P, I, I]
+    L.spe_debug_maxpool3s2.argtypes = [P, I, P, P, I, I, I, I, I]
+    L.spe_debug_upsample2x.argtypes = [P, I, P, P, I, I, I, I]
+    L.spe_debug_heads.argtypes = [P, P, I, I, I] + [P] * 21
     L.spe_rtdetr_forward_attention.argtypes = [P, P, P, I, P, I64, ctypes.POINTER(RtdetrOutputs), I, P, P, P, P]
     L.spe_jpeg_workspace_bytes.argtypes = [I, I, I, I64]
     L.spe_jpeg_workspace_bytes.restype = I64
