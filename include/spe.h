@@ -207,13 +207,22 @@ int spe_model_create(const spe_model_config* cfg, spe_model** out);
  * Everything after src (stages, u8 crops, attention maps, outputs) is the same for both. */
 enum { SPE_BACKBONE_RESNET50_S8 = 0, SPE_BACKBONE_RESNET50_S16 = 1 };
 int spe_model_create_backbone(const spe_model_config* cfg, int backbone, spe_model** out);
-/* The same with a flags word (additive, ABI 9; flags == 0 is spe_model_create_backbone):
+/* The same with a flags word, an OR of the bits below (additive, ABI 9; flags == 0 is spe_model_create_backbone):
  *   SPE_MODEL_PRE_NORM  the reference's --pre_norm transformer (REV/models/transformer.py forward_pre of both layer
  *                       classes): every LayerNorm in front of its sub-block, the encoder closed by
  *                       transformer.encoder.norm.{weight,bias} (two more keys, after the encoder layers': 414 / 410).
  *                       dtypes BF16_ (attn_dtype F16_ included), F32_, F32X3_ and F32X6_; F32H3_ is refused with
  *                       SPE_E_ARG (its activation-scale ledger rests on post-norm LayerNorm output bounds). */
-enum { SPE_MODEL_PRE_NORM = 1 };
+/*   SPE_MODEL_GROUP_NORM  the reference's --bn group_bn backbone (REV/models/backbone.py:168-181): nn.GroupNorm(32, C),
+ *                       eps 1e-5, in all 43 norm positions of the ResNet-50.  The keys are the reference's: every
+ *                       ...bnN.weight / .bias and downsample.1.weight / .bias, no running_mean / running_var (326 keys
+ *                       at stride 8, 322 at stride 16).  Nothing folds into a conv: every body conv runs bare and a
+ *                       GroupNorm (groupnorm.hip: norm.gn.stats + norm.gn.apply) follows it.  Composes with both
+ *                       backbones and with SPE_MODEL_PRE_NORM.  dtypes BF16_ (attn_dtype F16_ included), F32_, F32X3_
+ *                       and F32X6_; F32H3_ is refused with SPE_E_ARG (its activation-scale ledger takes static
+ *                       bounds from folded-BatchNorm weights; a GroupNorm output's scale depends on the data). */
+/* (bit value 2 is not a flag and stays refused with SPE_E_ARG, as it was before SPE_MODEL_GROUP_NORM existed) */
+enum { SPE_MODEL_PRE_NORM = 1, SPE_MODEL_GROUP_NORM = 4 };
 int spe_model_create_flags(const spe_model_config* cfg, int backbone, int flags, spe_model** out);
 void spe_model_destroy(spe_model* m);
 int spe_model_set_param(spe_model* m, const char* key, const float* host_data, int64_t numel);
@@ -800,6 +809,18 @@ int spe_debug_heads(void* stream, const float* hs, int B, int Q, int D, const fl
                     const float* pt_b2, const float* sg_w0t, const float* sg_b0, const float* sg_w1t, const float* sg_b1,
                     const float* sg_w2t, const float* sg_b2, const float* clip_bbox, float* logits, float* points,
                     float* probs, float* points_px, float* log_sigmas, float* sigmas);
+/* groupnorm: GroupNorm(32, C), eps 1e-5, over NHWC rows x [B*H*W][ldx] T (dtype BF16_ or F32_):
+ * y = (x - mean) * rsqrt(var + eps) * gamma[c] + beta[c] (+ residual) (ReLU when relu != 0), mean and biased variance
+ * per (image, group of C / 32 consecutive channels), fp32 statistics from the stored values.  Runs the model's two
+ * launches (stats, then apply) with `scratch` holding the partial statistics, fp32 [B][tiles][32][3] (count, mean,
+ * M2): spe_debug_groupnorm_scratch_bytes(B, H, W, C) = B * tiles * 384 bytes (0 for sizes it does not serve), tiles =
+ * ceil(H * W / (16384 / C)) for both dtypes.  x, residual and y may alias.  SPE_E_ARG before any launch: C not a
+ * multiple of 32 (or C / 32 not 2, 4, 8, 16 or 32), an ld below C or not a multiple of 8, a null x / gamma / beta / y /
+ * scratch, a pointer not 16-byte aligned, scratch_bytes below the stated size. */
+int spe_debug_groupnorm(void* stream, int dtype, const void* x, int ldx, const void* residual, int ldr,
+                        const float* gamma, const float* beta, void* y, int ldy, int B, int H, int W, int C, int relu,
+                        void* scratch, int64_t scratch_bytes);
+int64_t spe_debug_groupnorm_scratch_bytes(int B, int H, int W, int C);
 
 #ifdef __cplusplus
 }

@@ -126,6 +126,25 @@ int spe_debug_layernorm(void* stream, int dtype, const void* x, const float* gam
   return rc < 0 ? spe_fail(SPE_E_LAUNCH, "layernorm launch rejected its arguments") : rc;
 }
 
+int spe_debug_groupnorm(void* stream, int dtype, const void* x, int ldx, const void* residual, int ldr,
+                        const float* gamma, const float* beta, void* y, int ldy, int B, int H, int W, int C, int relu,
+                        void* scratch, int64_t scratch_bytes) {
+  GroupNormArgs a{};
+  a.x = x; a.ldx = ldx; a.res = residual; a.ldr = ldr; a.gamma = gamma; a.beta = beta; a.y = y; a.ldy = ldy;
+  a.B = B; a.H = H; a.W = W; a.C = C; a.relu = relu; a.part = (float*)scratch;
+  const int dt = dtype == SPE_DTYPE_BF16_ ? (int)SPE_DTYPE_BF16 : dtype == SPE_DTYPE_F32_ ? (int)SPE_DTYPE_F32 : -1;
+  if (const char* why = spe_gn_check(a, dt)) return spe_fail(SPE_E_ARG, why);
+  if (scratch_bytes < spe_gn_scratch_bytes(B, H, W, C)) return spe_fail(SPE_E_ARG, "groupnorm: scratch below the stated size");
+  int rc = spe_launch_gn_stats(a, dt, (hipStream_t)stream);
+  if (rc == 0) rc = spe_launch_gn_apply(a, dt, (hipStream_t)stream);
+  return rc < 0 ? spe_fail(SPE_E_LAUNCH, "groupnorm launch rejected its arguments") : rc;
+}
+
+int64_t spe_debug_groupnorm_scratch_bytes(int B, int H, int W, int C) {
+  if (B <= 0 || C <= 0 || C % 32) return 0;
+  return spe_gn_scratch_bytes(B, H, W, C);
+}
+
 int spe_debug_ffn_pre(void* stream, const void* x, int ldx, const void* w1, int ld1, const float* b1, const void* w2,
                       int ld2, const float* b2, const float* gamma, const float* beta, void* y, int ldy, int M, int D,
                       int F, float* partial, int splits, const float* gamma2, const float* beta2, void* y2,

@@ -247,6 +247,64 @@ int bottleneck(Fwd& f, size_t bi, BlockIn& in) {
   return 0;
 }
 
+// ---------------- the GroupNorm backbone (SPE_MODEL_GROUP_NORM; REV/models/backbone.py:168-181, --bn group_bn)
+//
+// Every body conv runs with an identity epilogue (no bias, no ReLU, no residual) and nn.GroupNorm(32, C) follows it
+// as two launches over the conv's output, in place (groupnorm.hip): norm.gn.stats, then norm.gn.apply with the
+// block's residual and ReLU.  No fused stem + pool and no fused bottleneck tail is taken: a norm sits inside each.
+
+// x [B*H*H][ld] = relu?(GroupNorm(x; a) (+ res)) over C channels
+int group_norm(Fwd& f, void* x, int ld, int H, int C, const GnAffine& a, const void* res, int ldr, bool relu) {
+  spe_model* m = f.m;
+  GroupNormArgs g{};
+  g.x = x; g.ldx = ld; g.res = res; g.ldr = ldr; g.gamma = a.g; g.beta = a.b; g.y = x; g.ldy = ld;
+  g.B = f.B; g.H = H; g.W = H; g.C = C; g.relu = relu; g.part = (float*)f.P(f.w.gn);
+  const double elems = (double)f.B * H * H * C, part = (double)spe_gn_scratch_bytes(f.B, H, H, C);
+  CK(run_other(m, "norm.gn.stats", 0.0, elems * m->esz + part, f.s, [&] { return spe_launch_gn_stats(g, f.dt, f.s); }));
+  CK(run_other(m, "norm.gn.apply", 0.0, elems * m->esz * (res ? 3.0 : 2.0) + part, f.s,
+               [&] { return spe_launch_gn_apply(g, f.dt, f.s); }));
+  return 0;
+}
+
+// a conv with nothing behind its accumulator
+int bare_gemm(Fwd& f, const char* kind, GemmArgs g, int mode) {
+  g.bias = nullptr;
+  return run_gemm(f.m, kind, g, mode, f.s);
+}
+
+// bottleneck block bi over `in`: conv1 -> GN + ReLU; conv2 -> GN + ReLU; conv3 -> GN (+ the identity, or the GN'd
+// downsample branch) + ReLU (torchvision Bottleneck.forward with norm_layer = MyGroupNorm)
+int bottleneck_gn(Fwd& f, size_t bi, BlockIn& in) {
+  spe_model* m = f.m;
+  const Ws& w = f.w;
+  const int B = f.B, H = in.H;
+  const Block& blk = m->blocks[bi];
+  const bool s16bb = m->backbone == SPE_BACKBONE_RESNET50_S16;
+  const size_t outbuf = (bi == 6 && !s16bb) ? w.xs8 : (in.x == w.bufA ? w.bufB : w.bufA);
+  const int Ho = (H + 2 - 3) / blk.stride + 1;
+  CK(bare_gemm(f, "conv.1x1", linear_args(blk.c1, f.P(in.x), in.ld, B * H * H, f.P(w.t1), blk.c1.N), GEMM_LINEAR));
+  TRY(group_norm(f, f.P(w.t1), blk.c1.N, H, blk.c1.N, blk.n1, nullptr, 0, true));
+  CK(bare_gemm(f, "conv.3x3", conv_args(blk.c2, f.P(w.t1), B, H, H, f.P(w.t2), blk.c2.N), GEMM_CONV));
+  TRY(group_norm(f, f.P(w.t2), blk.c2.N, Ho, blk.c2.N, blk.n2, nullptr, 0, true));
+  size_t res = in.x;
+  int ldr = in.ld;
+  if (blk.has_ds) {
+    if (blk.stride == 1)
+      CK(bare_gemm(f, "conv.1x1", linear_args(blk.ds, f.P(in.x), in.ld, B * H * H, f.P(w.ds), blk.ds.N), GEMM_LINEAR));
+    else
+      CK(bare_gemm(f, "conv.1x1s2", conv_args(blk.ds, f.P(in.x), B, H, H, f.P(w.ds), blk.ds.N), GEMM_CONV));
+    TRY(group_norm(f, f.P(w.ds), blk.ds.N, Ho, blk.ds.N, blk.nds, nullptr, 0, false));
+    res = w.ds;
+    ldr = blk.ds.N;
+  }
+  CK(bare_gemm(f, "conv.1x1", linear_args(blk.c3, f.P(w.t2), blk.c2.N, B * Ho * Ho, f.P(outbuf), blk.c3.N), GEMM_LINEAR));
+  TRY(group_norm(f, f.P(outbuf), blk.c3.N, Ho, blk.c3.N, blk.n3, f.P(res), ldr, true));
+  in.ld = blk.c3.N;
+  in.H = Ho;
+  in.x = outbuf;
+  return 0;
+}
+
 // s8_latern | s16_latern -> concat, output_conv, input_proj -> src [B*T, d] and its scale slot
 int neck(Fwd& f, size_t xs16, const float* xs8_amax, const float* xs16_amax) {
   spe_model* m = f.m;
@@ -329,7 +387,16 @@ int backbone_stage(Fwd& f, const ImageSrc& images) {
   const bool fuse0 = b0.c3ds.w != nullptr;
   const int uld = fuse0 ? b0.c3ds.K : 64;
   const size_t pool_at = fuse0 ? w.ds + (size_t)b0.c2.N * m->esz : w.pool;
-  if (pairs && spe_stempool_enabled() && spe_stempool_fits(S)) {
+  if (m->group_norm) {
+    // 7x7/2 -> GN + ReLU -> max-pool: the unfused stem, its norm in place over the stem output
+    GemmArgs g = pairs ? conv_args(m->stem, f.P(w.x0), B, S + 6, S + 6, f.P(w.stem), 64)
+                       : conv_args(m->stem, f.P(w.x0), B, S, S, f.P(w.stem), 64);
+    CK(bare_gemm(f, "conv.stem", g, GEMM_CONV));
+    TRY(group_norm(f, f.P(w.stem), 64, H, 64, m->stem_n, nullptr, 0, true));
+    CK(run_other(m, "eltwise.maxpool", 0.0, (double)B * 64 * (H * H + Hp * Hp) * m->esz, s, [&] {
+      return spe_launch_maxpool3s2(f.P(w.stem), f.P(pool_at), B, H, H, 64, Hp, Hp, dt, s, uld);
+    }));
+  } else if (pairs && spe_stempool_enabled() && spe_stempool_fits(S)) {
     // stem + bias + ReLU + max-pool in one pass (stempool.hip): the stem output stays in registers
     const double flops = 2.0 * B * H * H * 64 * 7 * 8 * 4;
     const double bytes = (double)B * (S + 6) * (S + 6) * 8 + (double)B * Hp * Hp * 64 * m->esz;
@@ -349,7 +416,7 @@ int backbone_stage(Fwd& f, const ImageSrc& images) {
   BlockIn x{pool_at, uld, Hp, stem_amax, false, false, false};  // (the max-pool's maximum is the stem's)
   const float* xs8_amax = nullptr;
   for (size_t bi = 0; bi < m->blocks.size(); ++bi) {
-    TRY(bottleneck(f, bi, x));
+    TRY(m->group_norm ? bottleneck_gn(f, bi, x) : bottleneck(f, bi, x));
     if (bi == 6) xs8_amax = x.amax;
   }
   if (m->backbone != SPE_BACKBONE_RESNET50_S16)

@@ -18,8 +18,13 @@ struct Conv {              // conv / linear packed as [N][Kpad] in T, bias fp32
   float l1max = 0.f, bmax = 0.f;   // linears: max_n sum_k |W[n][k]| and max |bias| (|y| <= max |x| l1max + bmax)
 };
 
+struct GnAffine {           // a GroupNorm layer's gamma / beta, fp32 [C] (SPE_MODEL_GROUP_NORM models)
+  float *g = nullptr, *b = nullptr;
+};
+
 struct Block {
   Conv c1, c2, c3, ds;
+  GnAffine n1, n2, n3, nds;  // group_norm models: bn1 / bn2 / bn3 / downsample.1 as GroupNorm; the convs carry no fold
   Conv c3ds;               // bf16, stride-1 first block: [W3 | Wds] over [t2 | x] (K = w + cin), or empty
   Conv c1p;                // bf16, input = a block output: conv1 with K columns in spe_btail_perm (K = 256) or
                            // spe_btail_wide_perm (512 / 1024) order, fused into the previous block's tail
@@ -73,6 +78,7 @@ struct Ws {                // workspace layout (byte offsets)
   size_t xvp;                // fp32h3: the memory's fp16 value planes (xattn_h3.hip; the key planes go to srcpos)
   size_t nrm, dnrm;          // pre-norm models: the normed copies of the encoder / decoder residual stream (else 0 bytes)
   size_t amax;               // fp32h3: max |activation| slots (SPE_AMAX_SLOTS floats; backbone, then transformer)
+  size_t gn;                 // group_norm models: partial statistics of the layer being normalised (else 0 bytes)
   size_t total;
 };
 
@@ -192,6 +198,7 @@ struct RtModel {
 struct spe_model {
   int family = 0;            // 0: DETR (REV), 1: RT-DETR (UNC)
   int pre_norm = 0;          // DETR: SPE_MODEL_PRE_NORM (REV/models/transformer.py normalize_before)
+  int group_norm = 0;        // DETR: SPE_MODEL_GROUP_NORM (REV/models/backbone.py --bn group_bn): GroupNorm(32, C) behind every body conv
   int backbone = 0;          // DETR: SPE_BACKBONE_RESNET50_S8 (Backbone8s) or SPE_BACKBONE_RESNET50_S16 (Backbone)
   int x3 = 0;                // fp32 model computed with split-bf16 MFMA (SPE_DTYPE_F32X3_, _F32X6_)
   int x6 = 0;                // ... with the GEMMs / convs on the three-way split path (SPE_DTYPE_F32X6_)
@@ -213,6 +220,7 @@ struct spe_model {
   size_t dbytes = 0, dused = 0;
   int upload_err = 0;
   Conv stem, s8, s16, outc, inproj, crossK, crossV;
+  GnAffine stem_n;         // group_norm models: body.bn1
   Conv s16taps;            // bf16 models: s16_latern as 9 per-tap [256][1024] blocks (spe_use_upconv)
   Conv neckip;             // input_proj . output_conv as one 3x3 conv 512 -> hidden (spe_use_neckfold)
   Conv ipp;                // bf16 stride-16 models: input_proj with its K columns in spe_btail_wide_perm order, the

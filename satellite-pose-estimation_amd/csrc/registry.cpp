@@ -33,13 +33,15 @@ int spe_fail(int code, const std::string& msg) {
 
 namespace {
 
-std::vector<std::pair<std::string, std::vector<int64_t>>> build_spec(const spe_model_config& c, int backbone, bool pre_norm) {
+std::vector<std::pair<std::string, std::vector<int64_t>>> build_spec(const spe_model_config& c, int backbone, bool pre_norm, bool group_norm) {
   const bool s16 = backbone == SPE_BACKBONE_RESNET50_S16;   // no neck; input_proj over layer3's 1024 channels
   std::vector<std::pair<std::string, std::vector<int64_t>>> s;
   const int64_t d = c.hidden_dim, ff = c.dim_feedforward;
   auto add = [&](const std::string& k, std::vector<int64_t> sh) { s.emplace_back(k, std::move(sh)); };
+  // (nn.GroupNorm registers weight and bias only: --bn group_bn checkpoints carry no running statistics)
   auto bn = [&](const std::string& p, int64_t ch) {
-    for (const char* n : {"weight", "bias", "running_mean", "running_var"}) add(p + "." + n, {ch});
+    for (const char* n : {"weight", "bias", "running_mean", "running_var"})
+      if (!group_norm || n[0] != 'r') add(p + "." + n, {ch});
   };
   for (int i = 0; i < c.enc_layers; ++i) {
     std::string p = "transformer.encoder.layers." + std::to_string(i);
@@ -445,6 +447,16 @@ int build_device(spe_model* m) {
   const auto& c = m->cfg;
   const int d = c.hidden_dim, ff = c.dim_feedforward, Q = c.num_queries;
   const std::string b = "backbone.0.body";
+  // group_norm models fold nothing into the body convs (the statistics are per image): every conv is packed bare,
+  // with a zero bias the launch sequence never reads, and its norm layer's gamma / beta are uploaded beside it
+  const bool gn = m->group_norm != 0;
+  auto norm = [&](const std::string& key) { return gn ? std::string() : key; };
+  auto affine = [&](const std::string& key) {
+    GnAffine a;
+    if (gn) { a.g = upload_key(m, key + ".weight"); a.b = upload_key(m, key + ".bias"); }
+    return a;
+  };
+  m->stem_n = affine(b + ".bn1");
   static const int stem_pairs = spe_env_int("SPE_STEM_PAIRS", 1);
   if (m->esz == 2 && stem_pairs) {
     // bf16: the pair-packed stem (SPE_STEM_PAIRS=0: the 8-channel tap-major stem, A/B knob).  The 7x7/s2/p3 conv over 3 channels runs as a 7x8/s2 conv
@@ -452,7 +464,7 @@ int build_device(spe_model* m) {
     // kw = 7 and ci = 3 have zero weights, K = 224 (4 K-steps) instead of 7*7*8 = 392 (7 K-steps),
     // and each 16-byte chunk is the taps kw, kw+1 of one row.
     std::vector<float> w, bias;
-    fold_conv(m, b + ".conv1.weight", b + ".bn1", "", w, bias);
+    fold_conv(m, b + ".conv1.weight", norm(b + ".bn1"), "", w, bias);
     constexpr int KH = 7, KW = 8, CI = 4, K = KH * KW * CI;
     std::vector<float> rows((size_t)64 * K, 0.f);
     if (m->dmem)
@@ -469,7 +481,7 @@ int build_device(spe_model* m) {
   } else {
     // fp32 models: 3 channels padded to 4 (K = 7*7*4 = 196: half the 8-channel form's products; the
     // 16-byte chunk is one pixel); bf16 with SPE_STEM_PAIRS=0: 8 channels (a 16-byte bf16 chunk)
-    m->stem = make_conv(m, b + ".conv1.weight", b + ".bn1", "", m->esz == 4 ? 4 : 8, 2, 3);
+    m->stem = make_conv(m, b + ".conv1.weight", norm(b + ".bn1"), "", m->esz == 4 ? 4 : 8, 2, 3);
   }
   m->blocks.clear();
   m->btail_rows = spe_btail_rows_enabled();
@@ -480,13 +492,15 @@ int build_device(spe_model* m) {
       std::string p = b + ".layer" + std::to_string(li + 1) + "." + std::to_string(k);
       Block blk;
       blk.stride = (k == 0 && li > 0) ? 2 : 1;
-      blk.c1 = make_conv(m, p + ".conv1.weight", p + ".bn1", "", 0, 1, 0);
-      blk.c2 = make_conv(m, p + ".conv2.weight", p + ".bn2", "", 0, blk.stride, 1);
-      blk.c3 = make_conv(m, p + ".conv3.weight", p + ".bn3", "", 0, 1, 0);
+      blk.c1 = make_conv(m, p + ".conv1.weight", norm(p + ".bn1"), "", 0, 1, 0);
+      blk.c2 = make_conv(m, p + ".conv2.weight", norm(p + ".bn2"), "", 0, blk.stride, 1);
+      blk.c3 = make_conv(m, p + ".conv3.weight", norm(p + ".bn3"), "", 0, 1, 0);
+      blk.n1 = affine(p + ".bn1"); blk.n2 = affine(p + ".bn2"); blk.n3 = affine(p + ".bn3");
       if (k == 0) {
         blk.has_ds = true;
-        blk.ds = make_conv(m, p + ".downsample.0.weight", p + ".downsample.1", "", 0, blk.stride, 0);
-        if (blk.stride == 1 && m->esz == 2) {
+        blk.ds = make_conv(m, p + ".downsample.0.weight", norm(p + ".downsample.1"), "", 0, blk.stride, 0);
+        blk.nds = affine(p + ".downsample.1");
+        if (blk.stride == 1 && m->esz == 2 && !gn) {
           // conv3 + downsample of a stride-1 first block as ONE K = w + cin GEMM over the
           // channel concatenation [conv2 output | block input] (forward.cpp lays them out side by
           // side): relu(W3 t2 + b3 + Wds x + bds) with no downsample output round trip
@@ -518,7 +532,8 @@ int build_device(spe_model* m) {
       const bool narrow = spe_btail_enabled() && gi >= 1 && blk.c1.K == 256;
       const bool wide = spe_btail_wide_enabled() && li >= 1 && !m->blocks.empty() && m->blocks.back().c3.N == blk.c1.K &&
                         (blk.c1.K == 512 || blk.c1.K == 1024);
-      if (m->esz == 2 && (narrow || wide)) {
+      // (group_norm models take no fused tail: a norm sits between conv3 and the next conv1)
+      if (m->esz == 2 && (narrow || wide) && !gn) {
         std::vector<float> w1, b1;
         fold_conv(m, p + ".conv1.weight", p + ".bn1", "", w1, b1);
         const int n = blk.c1.N, K = blk.c1.K;
@@ -538,7 +553,7 @@ int build_device(spe_model* m) {
     m->inproj = make_conv(m, "input_proj.weight", "", "input_proj.bias", 0, 1, 0);   // K = 1024, over block 12's output
     // Nobody but input_proj reads the last bottleneck's output, so bf16 models take input_proj as the
     // second product of that block's tail (btail_wide.hip's final form): its weights like a c1p
-    if (m->esz == 2 && spe_btail_wide_enabled() && m->inproj.K == 1024 && m->blocks.back().c3.N == 1024) {
+    if (m->esz == 2 && spe_btail_wide_enabled() && m->inproj.K == 1024 && m->blocks.back().c3.N == 1024 && !gn) {
       std::vector<float> w, bias;
       fold_conv(m, "input_proj.weight", "", "input_proj.bias", w, bias);
       const int n = m->inproj.N, K = m->inproj.K;
@@ -774,6 +789,15 @@ Ws spe_plan(const spe_model* m, int B) {
   w.nrm = take(m->pre_norm ? (size_t)B * T * d * E : 0);
   w.dnrm = take(m->pre_norm ? (size_t)B * Q * d * E : 0);
   w.amax = take(m->h3 ? SPE_AMAX_SLOTS * 4 : 0);
+  // group_norm models: the Welford partials of one norm layer at a time (groupnorm.hip), sized for the layer with
+  // the most tiles per image -- the stem, 64 channels at S/2, down to 1024 channels at S/16
+  size_t gn_bytes = 0;
+  if (m->group_norm) {
+    const size_t shapes[][2] = {{H2, 64}, {H4, 64}, {H4, 128}, {H4, 256}, {H8, 128}, {H8, 256}, {H8, 512}, {H16, 256}, {H16, 1024}};
+    for (auto& sh : shapes)
+      gn_bytes = std::max(gn_bytes, (size_t)spe_gn_scratch_bytes(B, (int)sh[0], (int)sh[0], (int)sh[1]));
+  }
+  w.gn = take(gn_bytes);
   w.total = off;
   return w;
 }
@@ -793,7 +817,12 @@ int spe_model_create_backbone(const spe_model_config* cfg, int backbone, spe_mod
 
 int spe_model_create_flags(const spe_model_config* cfg, int backbone, int flags, spe_model** out) {
   if (!cfg || !out) return fail(SPE_E_ARG, "null argument");
-  if (flags & ~SPE_MODEL_PRE_NORM) return fail(SPE_E_ARG, "flags: SPE_MODEL_PRE_NORM or 0");
+  if (flags & ~(SPE_MODEL_PRE_NORM | SPE_MODEL_GROUP_NORM))
+    return fail(SPE_E_ARG, "flags: an OR of SPE_MODEL_PRE_NORM and SPE_MODEL_GROUP_NORM, or 0");
+  if ((flags & SPE_MODEL_GROUP_NORM) && cfg->dtype == SPE_DTYPE_F32H3_)
+    return fail(SPE_E_ARG, "group_norm: fp32h3 is not served (its activation-scale ledger takes static bounds from "
+                           "folded-BatchNorm weights, and a GroupNorm output's scale depends on the data); use fp32, "
+                           "fp32x3, fp32x6 or bf16");
   if ((flags & SPE_MODEL_PRE_NORM) && cfg->dtype == SPE_DTYPE_F32H3_)
     return fail(SPE_E_ARG, "pre_norm: fp32h3 is not served (its activation-scale ledger takes static bounds from "
                            "post-norm LayerNorm outputs, which the pre-norm residual stream does not have); use "
@@ -822,7 +851,8 @@ int spe_model_create_flags(const spe_model_config* cfg, int backbone, int flags,
   m->esz = cfg->dtype == SPE_DTYPE_BF16_ ? 2 : 4;
   m->backbone = backbone;
   m->pre_norm = (flags & SPE_MODEL_PRE_NORM) != 0;
-  m->spec = build_spec(*cfg, backbone, m->pre_norm);
+  m->group_norm = (flags & SPE_MODEL_GROUP_NORM) != 0;
+  m->spec = build_spec(*cfg, backbone, m->pre_norm, m->group_norm);
   *out = m;
   return 0;
 }

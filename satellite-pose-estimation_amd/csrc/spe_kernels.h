@@ -326,6 +326,25 @@ int spe_launch_upconv_combine(const void* z, void* out, int ldo, int B, int H, i
 int spe_launch_layernorm(const void* x, const float* gamma, const float* beta, void* out, float* out_f32,
                          int M, int D, int dtype, hipStream_t s);
 
+// GroupNorm(32, C), eps 1e-5, over NHWC rows [B*H*W][ld] (groupnorm.hip): y = (x - mean) rstd gamma[c] + beta[c]
+// (+ res) (ReLU), mean / biased variance per (image, group).  Two launches: spe_launch_gn_stats writes Welford
+// triples part[B][tiles][32][3] (spe_gn_scratch_bytes), spe_launch_gn_apply merges them and normalises; x, res and
+// y may alias.  C / 32 in {2, 4, 8, 16, 32}, every ld >= C and a multiple of 8, pointers 16-byte aligned:
+// spe_gn_check names the first violation (null = served), the launchers return -1 for one.
+struct GroupNormArgs {
+  const void* x; int ldx;
+  const void* res; int ldr;        // residual added before the ReLU, or null
+  const float* gamma; const float* beta;
+  void* y; int ldy;
+  int B, H, W, C, relu;
+  float* part;
+};
+int spe_gn_tiles(int H, int W, int C);                     // partial-statistics tiles per image (dtype-independent)
+int64_t spe_gn_scratch_bytes(int B, int H, int W, int C);
+const char* spe_gn_check(const GroupNormArgs& a, int dtype);
+int spe_launch_gn_stats(const GroupNormArgs& a, int dtype, hipStream_t s);
+int spe_launch_gn_apply(const GroupNormArgs& a, int dtype, hipStream_t s);
+
 struct HeadArgs {
   const float* hs;                 // [B*Q][256] fp32 (decoder_norm output of the last layer)
   int B, Q, D;

@@ -44,7 +44,7 @@ MBS_W_FLOATS = 1040              # spe_debug_mbs_entry's folded weights (include
 GH_POST_NONE, GH_POST_GATE, GH_POST_RESIDUAL = 0, 1, 2
 MB_ACT_NONE, MB_ACT_RELU, MB_ACT_HSWISH = 0, 1, 4
 SPE_BACKBONE_RESNET50_S8, SPE_BACKBONE_RESNET50_S16 = 0, 1     # spe_model_create_backbone
-SPE_MODEL_PRE_NORM = 1           # spe_model_create_flags
+SPE_MODEL_PRE_NORM, SPE_MODEL_GROUP_NORM = 1, 4     # spe_model_create_flags (bits; 2 is no flag and is refused)
 SPE_STAGE_ENCODE, SPE_STAGE_DECODE, SPE_STAGE_BACKBONE, SPE_STAGE_TRANSFORMER = 1, 2, 4, 8
 SPE_PNP_EPNP, SPE_PNP_RANSAC_P3P_LM, SPE_PNP_EPNP_RANSAC_SIGMA, SPE_PNP_EPNP_LM, SPE_PNP_EPNP_CERES = 0, 1, 2, 3, 4
 SPE_PNP_EXHAUSTIVE = 5           # spe_pnp_exhaustive only
@@ -66,7 +66,7 @@ EXPORTS = ["spe_abi_version", "spe_last_error", "spe_model_create", "spe_model_c
            "spe_forward_attention", "spe_forward_attention_workspace_bytes", "spe_debug_attn_map",
            "spe_debug_ffn_pre", "spe_debug_oproj_pre",
            "spe_debug_pack_input", "spe_debug_pack_input_pad4", "spe_debug_maxpool3s2", "spe_debug_upsample2x",
-           "spe_debug_heads"]
+           "spe_debug_heads", "spe_debug_groupnorm", "spe_debug_groupnorm_scratch_bytes"]
 
 
 class ModelConfig(ctypes.Structure):
@@ -200,6 +200,9 @@ def load(path: str):
     L.spe_debug_maxpool3s2.argtypes = [P, I, P, P, I, I, I, I, I]
     L.spe_debug_upsample2x.argtypes = [P, I, P, P, I, I, I, I]
     L.spe_debug_heads.argtypes = [P, P, I, I, I] + [P] * 21
+    L.spe_debug_groupnorm.argtypes = [P, I, P, I, P, I, P, P, P, I, I, I, I, I, I, P, I64]
+    L.spe_debug_groupnorm_scratch_bytes.argtypes = [I, I, I, I]
+    L.spe_debug_groupnorm_scratch_bytes.restype = I64
     L.spe_rtdetr_forward_attention.argtypes = [P, P, P, I, P, I64, ctypes.POINTER(RtdetrOutputs), I, P, P, P, P]
     L.spe_jpeg_workspace_bytes.argtypes = [I, I, I, I64]
     L.spe_jpeg_workspace_bytes.restype = I64

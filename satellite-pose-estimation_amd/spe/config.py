@@ -15,6 +15,7 @@ _DATA = os.path.join(os.path.dirname(__file__), "data")
 
 
 BACKBONES = ("resnet50s8", "resnet50")
+NORMS = ("frozen_bn", "group_bn")
 
 
 @dataclass(frozen=True)
@@ -30,10 +31,13 @@ class SpeConfig:
     sigma_head: bool = False       # UNC sigma head (UNC/src/zoo/rtdetr/rtdetr_decoder.py:295-297)
     backbone: str = "resnet50s8"   # --backbone (REV/main.py): "resnet50s8" (Backbone8s) or "resnet50" (Backbone)
     pre_norm: bool = False         # --pre_norm (REV/main.py): normalize_before of both transformer layer classes
+    norm: str = "frozen_bn"        # --bn (REV/main.py:118): the backbone's norm layer, "frozen_bn" or "group_bn"
 
     def __post_init__(self):
         if self.backbone not in BACKBONES:
             raise ValueError(f"backbone {self.backbone!r}: one of {BACKBONES}")
+        if self.norm not in NORMS:
+            raise ValueError(f"norm {self.norm!r}: one of {NORMS}")
 
     @property
     def stride(self) -> int:
@@ -53,7 +57,13 @@ class SpeConfig:
     def from_args(cls, args) -> "SpeConfig":
         """Build from a reference-style argparse.Namespace (REV/main.py:90-187).  The backbone follows
         build_backbone (REV/models/backbone.py:188-195): "resnet50" is the plain stride-16 Backbone, every
-        other name the stride-8 Backbone8s -- except resnet18 / resnet34, which the reference cannot run."""
+        other name the stride-8 Backbone8s -- except resnet18 / resnet34, which the reference cannot run.
+        args.bn (REV/models/backbone.py:173-181): "frozen_bn", "bn" and "sync_bn" all map to norm "frozen_bn" -- in
+        eval each is the same per-channel affine of its running statistics, eps 1e-5, over the same keys;
+        "group_bn" (nn.GroupNorm(32, C), no running statistics) maps to "group_bn"."""
+        bn = str(getattr(args, "bn", "frozen_bn"))
+        if bn not in ("frozen_bn", "bn", "sync_bn", "group_bn"):
+            raise ValueError(f"bn {bn!r}: one of frozen_bn, bn, sync_bn, group_bn")
         name = str(getattr(args, "backbone", "resnet50s8"))
         if name in ("resnet18", "resnet34"):
             raise ValueError(f"backbone {name!r}: the reference declares num_channels 512 for it but returns "
@@ -68,7 +78,8 @@ class SpeConfig:
                    nheads=int(getattr(args, "nheads", 8)),
                    dim_feedforward=int(getattr(args, "dim_feedforward", 2048)),
                    sigma_head=bool(getattr(args, "sigma_head", False)),
-                   pre_norm=bool(getattr(args, "pre_norm", False)))
+                   pre_norm=bool(getattr(args, "pre_norm", False)),
+                   norm="group_bn" if bn == "group_bn" else "frozen_bn")
 
     def to_dict(self):
         return asdict(self)

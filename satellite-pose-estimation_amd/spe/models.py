@@ -2,7 +2,8 @@
 REV/models/detr_speed.py:32-100,264-336) over the HIP path in libspe.so.
 
     model, criterion, postprocessors = build_model(args)
-    model.load_state_dict(state_dict)      # the reference's 412 keys (checkpoint['model']; 408 for --backbone resnet50)
+    model.load_state_dict(state_dict)      # the reference's 412 keys (checkpoint['model']; 408 for --backbone resnet50;
+                                           # 326 / 322 for --bn group_bn, whose norms have no running statistics)
     out = model(samples)                   # NestedTensor | list[Tensor] | Tensor [B,3,S,S]
     results = postprocessors['points'](out, clip_bbox_list)
 
@@ -25,7 +26,8 @@ from .misc import NestedTensor, nested_tensor_from_tensor_list
 class DETR(nn.Module):
     """Keypoint-set predictor (REV/models/detr_speed.py:32-100), HIP implementation.  cfg.backbone
     "resnet50s8": the stride-8 fusion neck (Backbone8s); "resnet50": ResNet-50 cut after layer3 with
-    input_proj straight on the stride-16 map (Backbone, REV/models/backbone.py:57-102).
+    input_proj straight on the stride-16 map (Backbone, REV/models/backbone.py:57-102).  cfg.norm "group_bn":
+    nn.GroupNorm(32, C) in the backbone's 43 norm positions (--bn group_bn), computed per image on the device.
 
     dtype "bf16": bf16 storage / MFMA with fp32 accumulation, softmax, LayerNorm and heads
     (throughput path).  dtype "fp32": exact-f32 MFMA everywhere (parity path).  dtype "fp32x3":
@@ -59,7 +61,8 @@ class DETR(nn.Module):
                              _lib.SPE_DTYPE_F16 if self.attn_dtype == "fp16" else 0)
         h = ctypes.c_void_p()
         bb = {"resnet50s8": _lib.SPE_BACKBONE_RESNET50_S8, "resnet50": _lib.SPE_BACKBONE_RESNET50_S16}[cfg.backbone]
-        flags = _lib.SPE_MODEL_PRE_NORM if cfg.pre_norm else 0
+        flags = (_lib.SPE_MODEL_PRE_NORM if cfg.pre_norm else 0) | \
+                (_lib.SPE_MODEL_GROUP_NORM if cfg.norm == "group_bn" else 0)
         _lib.check(L.spe_model_create_flags(ctypes.byref(c), bb, flags, ctypes.byref(h)), "spe_model_create_flags")
         self._h = h
         self._keys = [L.spe_model_param_name(h, i).decode() for i in range(L.spe_model_num_params(h))]

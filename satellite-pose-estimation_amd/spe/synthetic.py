@@ -2,8 +2,8 @@
 
 * `param_shapes(cfg)`  - the reference's state_dict key space (412 keys for the REV
   DETR, REV/models/detr_speed.py:32-56, backbone.py:105-131, transformer.py:18-49; 408 with the
-  plain stride-16 backbone, backbone.py:57-102, which has no neck), plus the optional UNC-style
-  sigma head.
+  plain stride-16 backbone, backbone.py:57-102, which has no neck; 326 / 322 with --bn group_bn, whose
+  GroupNorm layers have no running statistics), plus the optional UNC-style sigma head.
 * `random_weights(cfg, seed)` - deterministic random-init weights in that key space
   (there is no trained checkpoint in the reference tree), with non-trivial FrozenBN
   statistics so the BN folding path is exercised.
@@ -26,8 +26,10 @@ IMAGENET_STD = np.array([0.229, 0.224, 0.225], np.float32)
 _RESNET50_STAGES = [(64, 3, 1), (128, 4, 2), (256, 6, 2)]   # layer1..3 (layer4 never runs)
 
 
-def _bn_keys(prefix, c):
-    return [(f"{prefix}.{n}", (c,)) for n in ("weight", "bias", "running_mean", "running_var")]
+def _bn_keys(prefix, c, group_norm=False):
+    """a norm layer's keys: FrozenBatchNorm2d's four, or nn.GroupNorm's affine alone (--bn group_bn)"""
+    names = ("weight", "bias") if group_norm else ("weight", "bias", "running_mean", "running_var")
+    return [(f"{prefix}.{n}", (c,)) for n in names]
 
 
 def param_shapes(cfg: SpeConfig):
@@ -62,16 +64,17 @@ def param_shapes(cfg: SpeConfig):
     out += [("query_embed.weight", (Q, d)), ("input_proj.weight", (d, 1024 if s16 else 512, 1, 1)),
             ("input_proj.bias", (d,))]
     b = "backbone.0.body"
-    out += [(f"{b}.conv1.weight", (64, 3, 7, 7))] + _bn_keys(f"{b}.bn1", 64)
+    gn = cfg.norm == "group_bn"
+    out += [(f"{b}.conv1.weight", (64, 3, 7, 7))] + _bn_keys(f"{b}.bn1", 64, gn)
     cin = 64
     for li, (w, n, s) in enumerate(_RESNET50_STAGES, start=1):
         for k in range(n):
             p = f"{b}.layer{li}.{k}"
-            out += [(f"{p}.conv1.weight", (w, cin, 1, 1))] + _bn_keys(f"{p}.bn1", w)
-            out += [(f"{p}.conv2.weight", (w, w, 3, 3))] + _bn_keys(f"{p}.bn2", w)
-            out += [(f"{p}.conv3.weight", (4 * w, w, 1, 1))] + _bn_keys(f"{p}.bn3", 4 * w)
+            out += [(f"{p}.conv1.weight", (w, cin, 1, 1))] + _bn_keys(f"{p}.bn1", w, gn)
+            out += [(f"{p}.conv2.weight", (w, w, 3, 3))] + _bn_keys(f"{p}.bn2", w, gn)
+            out += [(f"{p}.conv3.weight", (4 * w, w, 1, 1))] + _bn_keys(f"{p}.bn3", 4 * w, gn)
             if k == 0:
-                out += [(f"{p}.downsample.0.weight", (4 * w, cin, 1, 1))] + _bn_keys(f"{p}.downsample.1", 4 * w)
+                out += [(f"{p}.downsample.0.weight", (4 * w, cin, 1, 1))] + _bn_keys(f"{p}.downsample.1", 4 * w, gn)
             cin = 4 * w
     if not s16:
         out += [("backbone.0.s8_latern.weight", (256, 512, 1, 1)),
@@ -90,7 +93,8 @@ def random_weights(cfg: SpeConfig, seed: int = 0):
     Conv weights are He-normal, linear/attention weights Xavier-uniform (the reference's
     `_reset_parameters`, REV/models/transformer.py:45-48), FrozenBN stats non-trivial and
     the residual-branch gain (bn3 weight) damped so activations stay O(1) through 13
-    bottlenecks without batch statistics."""
+    bottlenecks without batch statistics.  A group_bn config draws its GroupNorm gamma / beta like the BN affine
+    and no running statistics; a frozen_bn config's stream is untouched by that."""
     rng = np.random.Generator(np.random.PCG64(seed))
     w = {}
     for key, shape in param_shapes(cfg):
