@@ -373,11 +373,13 @@ int spe_jpeg_decode(void* stream, const uint8_t* data, const int64_t* offsets, c
 
 /* SetCriterion.forward with its HungarianMatcher (REV/models/detr_speed.py:214-261,
  * REV/models/matcher.py:60-88) for `layers` decoder layers (aux first, last layer last), the
- * logging half of evaluate() (REV/engine.py:99-112).  Device pointers: logits [L,B,Q,C] (C = 12),
- * points [L,B,Q,2], tgt_labels int32 [B,T], tgt_points [B,T,2] (crop-normalised), match int32
- * [L,B,T] (query matched to each target), losses fp64 [L,4] = loss_ce, class_error,
+ * logging half of evaluate() (REV/engine.py:99-112).  Device pointers: logits [L,B,Q,C] (C = 12 in
+ * the reference; class C-1 is no-object), points [L,B,Q,2], tgt_labels int32 [B,T] (a label outside
+ * [0,C) counts as class C-1, as in spe_criterion_sigma), tgt_points [B,T,2] (crop-normalised), match
+ * int32 [L,B,T] (query matched to each target), losses fp64 [L,4] = loss_ce, class_error,
  * cardinality_error, loss_points.  num_points: targets per rank averaged over ranks, >= 1
- * (REV/models/detr_speed.py:235-244).  Q <= 64, T <= min(Q, 32). */
+ * (REV/models/detr_speed.py:235-244), the divisor of loss_points alone.  1 <= Q <= 64,
+ * 1 <= T <= min(Q, 32), 2 <= C <= 32, num_points > 0, else SPE_E_ARG before any launch. */
 int spe_criterion(void* stream, const float* logits, const float* points, const int32_t* tgt_labels,
                   const float* tgt_points, int layers, int batch, int num_queries, int num_classes, int num_targets,
                   float cost_class, float cost_pts, float eos_coef, double num_points, int32_t* match, double* losses);
@@ -406,7 +408,10 @@ int spe_criterion_sigma(void* stream, const float* logits, const float* points, 
  * REV/gen_submission_multi.py:145-186): fuses M models' PostProcess outputs per image -- labels
  * in first-seen order, per label the mean of its points after the 3-sigma filter -- into
  * fused_points [B,C-1,2] + one-hot fused_probs [B,C-1,C], the input spe_pnp_batch then solves
- * (RANSAC_P3P_LM, like the reference).  points [M,B,Q,2] px, probs [M,B,Q,C]; M * Q <= 256. */
+ * (RANSAC_P3P_LM, like the reference).  points [M,B,Q,2] px, probs [M,B,Q,C]; M * Q <= 256 and
+ * 2 <= C <= 17, else SPE_E_ARG before any launch.  A label may pool all M * Q points: the fp64 sums of
+ * the filter's standard deviation follow numpy's pairwise summation over that whole range (one block
+ * up to 128 values, split in two above), so the fused points equal numpy's bit for bit. */
 int spe_ensemble_fuse(void* stream, const float* points_px, const float* probs, int models, int batch,
                       int num_queries, int num_classes, float* fused_points, float* fused_probs);
 
@@ -419,7 +424,8 @@ int spe_postprocess(void* stream, const float* logits, const float* points, cons
  * K: 3x3 row-major fp64; world: [C-1][3] fp64 landmarks (REV/all_result.json).
  * quat: [B,4] (float32 values, Blender order w,x,y,z); tvec/rvec: [B,3] fp64;
  * corr_label: [B,16] label of each correspondence in first-seen order (-1 padded);
- * inlier_mask: [B] bit i = correspondence i is an inlier.  repro_per_image: [B] fp32 thresholds that
+ * inlier_mask: [B] bit i = correspondence i is an inlier; 0 where the RANSAC modes end without a pose,
+ * the direct solve on exactly 4 (P3P) or 5 (EPnP) points included.  repro_per_image: [B] fp32 thresholds that
  * replace `repro` image by image (EPnPCeresSolver.get_repro_th of each image's box area).  Nullable:
  * sigmas, rvec, status, n_corr, corr_label, inlier_mask, repro_per_image. */
 int spe_pnp_batch(void* stream, const float* points_px, const float* probs, const float* sigmas, int batch,

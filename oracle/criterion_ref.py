@@ -113,12 +113,13 @@ def layer_losses(logits, points, tgt_labels, tgt_points, m, eos_coef=0.1, num_po
     """Losses of one decoder layer for a batch; m [B, T] matched query per target."""
     B, Q, C = logits.shape
     T = tgt_labels.shape[1]
-    tc = np.full((B, Q), NUM_CLASSES, np.int64)
+    noobj = C - 1                             # NUM_CLASSES at the reference's C = 12
+    tc = np.full((B, Q), noobj, np.int64)
     for b in range(B):
         tc[b, m[b]] = tgt_labels[b]
     lp = logits.astype(np.float64) - logits.max(-1, keepdims=True)
     lp = lp - np.log(np.exp(lp).sum(-1, keepdims=True))
-    w = np.where(tc == NUM_CLASSES, eos_coef, 1.0)
+    w = np.where(tc == noobj, eos_coef, 1.0)
     nll = -np.take_along_axis(lp, tc[..., None], -1)[..., 0]
     out = {"loss_ce": float((w * nll).sum() / w.sum())}
     if log:
@@ -135,9 +136,11 @@ def layer_losses(logits, points, tgt_labels, tgt_points, m, eos_coef=0.1, num_po
     return out
 
 
-def criterion(layers, tgt_labels, tgt_points, cost_class=1.0, cost_pts=5.0, eos_coef=0.1, solver=lsap):
-    """layers: list of (logits [B,Q,C], points [B,Q,2]), aux first, last layer last.
-    Returns (loss dict with the reference's keys, match [L, B, T])."""
+def criterion(layers, tgt_labels, tgt_points, cost_class=1.0, cost_pts=5.0, eos_coef=0.1, solver=lsap,
+              num_points=None):
+    """layers: list of (logits [B,Q,C], points [B,Q,2]), aux first, last layer last; num_points: the
+    loss_points divisor (None: B * T, one rank).  Returns (loss dict with the reference's keys,
+    match [L, B, T])."""
     L = len(layers)
     B = tgt_labels.shape[0]
     losses, ms = {}, []
@@ -146,6 +149,6 @@ def criterion(layers, tgt_labels, tgt_points, cost_class=1.0, cost_pts=5.0, eos_
                       for b in range(B)])
         ms.append(m)
         last = l == L - 1
-        d = layer_losses(lg, pt, tgt_labels, tgt_points, m, eos_coef, log=last)
+        d = layer_losses(lg, pt, tgt_labels, tgt_points, m, eos_coef, num_points=num_points, log=last)
         losses.update(d if last else {f"{k}_{l}": v for k, v in d.items()})
     return losses, np.stack(ms)

@@ -15,7 +15,8 @@ REV/gen_submission_multi.py:145-186):
 
 numpy's reductions are restated operation for operation: an axis-0 mean of an [n, 2] float32
 array accumulates row by row in float32 and divides in float32; np.std of the 1-D fp64
-distances uses numpy's pairwise summation (sequential below 8 elements, 8 accumulators above).
+distances uses numpy's pairwise summation (sequential below 8 elements, 8 accumulators up to 128,
+split in two above: a label can pool up to M * Q = 256 points).
 When no point is closer than 3 std (every point of a label coincides, std 0, or all distances
 are equal) the reference's inlier set is empty and np.mean gives a NaN point; so does this
 restatement, and the NaN point then goes to the solver like the reference's.  The reference module imports
@@ -28,9 +29,15 @@ import numpy as np
 
 
 def pairwise_sum(a):
-    """numpy's pairwise summation of a contiguous 1-D fp64 array (n < 128 block)."""
+    """numpy's pairwise summation of a contiguous 1-D fp64 array (pairwise_sum_DOUBLE): one block up
+    to 128 values, above that n2 = n // 2 rounded down to a multiple of 8 and
+    sum(a[:n2]) + sum(a[n2:]), recursively."""
     a = np.asarray(a, np.float64)
     n = len(a)
+    if n > 128:
+        n2 = n // 2
+        n2 -= n2 % 8
+        return pairwise_sum(a[:n2]) + pairwise_sum(a[n2:])
     if n < 8:
         res = 0.0
         for x in a:

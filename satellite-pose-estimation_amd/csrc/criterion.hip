@@ -31,11 +31,17 @@ __global__ __launch_bounds__(64) void criterion_match_kernel(CritArgs a) {
   __shared__ int col4row[QMAX], row4col[QMAX], path[QMAX], remaining[QMAX];
   __shared__ double u[QMAX], v[QMAX], spc[QMAX];
   __shared__ bool sr[QMAX], sc[QMAX];
-  __shared__ int mq[TMAX];
+  __shared__ int mq[TMAX], tl[TMAX];
   const float* lg = a.logits + ((size_t)l * a.B + b) * Q * C;
   const float* pt = a.points + ((size_t)l * a.B + b) * Q * 2;
-  const int* tl = a.tgt_labels + (size_t)b * T;
   const float* tp = a.tgt_points + (size_t)b * T * 2;
+  if (q < T) {
+    // a label outside [0, C) counts as no-object (like spe_criterion_sigma): it never indexes past a
+    // prob / logits row
+    const int lab = a.tgt_labels[(size_t)b * T + q];
+    tl[q] = lab >= 0 && lab < C ? lab : C - 1;
+  }
+  __syncthreads();
   float lse = 0.f, mx = 0.f;
   if (q < Q) {
     // softmax (fp32: max, exp(x - max), sum, divide) and the log-sum-exp for the cross entropy

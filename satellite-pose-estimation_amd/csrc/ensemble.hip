@@ -19,22 +19,44 @@ namespace {
 
 constexpr int KMAX = 16;     // labels (num_classes - 1)
 
-// numpy pairwise summation of n fp64 values produced by f(i) (n < 128)
+// numpy's pairwise summation (pairwise_sum_DOUBLE, block size 128) of the n fp64 values f(off) ..
+// f(off + n - 1).  One unsplit block, n <= 128: sequential below 8 values, 8 accumulators above.
 template <typename F>
-SPE_DEV double pairwise_sum(int n, F f) {
+SPE_DEV double pairwise_block(int off, int n, F f) {
   if (n < 8) {
     double r = 0.0;
-    for (int i = 0; i < n; ++i) r += f(i);
+    for (int i = 0; i < n; ++i) r += f(off + i);
     return r;
   }
   double r[8];
-  for (int j = 0; j < 8; ++j) r[j] = f(j);
+  for (int j = 0; j < 8; ++j) r[j] = f(off + j);
   int i = 8;
   for (; i < n - (n % 8); i += 8)
-    for (int j = 0; j < 8; ++j) r[j] += f(i + j);
+    for (int j = 0; j < 8; ++j) r[j] += f(off + i + j);
   double res = ((r[0] + r[1]) + (r[2] + r[3])) + ((r[4] + r[5]) + (r[6] + r[7]));
-  for (; i < n; ++i) res += f(i);
+  for (; i < n; ++i) res += f(off + i);
   return res;
+}
+
+// Above 128 values numpy splits: n2 = n / 2 rounded down to a multiple of 8, sum(a, n2) +
+// sum(a + n2, n - n2).  This level takes n <= 136 (both halves are single blocks) ...
+template <typename F>
+SPE_DEV double pairwise_split(int off, int n, F f) {
+  if (n <= 128) return pairwise_block(off, n, f);
+  int n2 = n / 2;
+  n2 -= n2 % 8;
+  return pairwise_block(off, n2, f) + pairwise_block(off + n2, n - n2, f);
+}
+
+// ... and this one n <= 256, the contract's M * Q: the first half is at most 128 values, the second at
+// most 136 (n = 250 .. 255 leave 130 .. 135 there, which split once more).  Written out instead of
+// recursing so that the kernel needs no call stack.
+template <typename F>
+SPE_DEV double pairwise_sum(int n, F f) {
+  if (n <= 128) return pairwise_block(0, n, f);
+  int n2 = n / 2;
+  n2 -= n2 % 8;
+  return pairwise_block(0, n2, f) + pairwise_split(n2, n - n2, f);
 }
 
 __global__ __launch_bounds__(64) void ensemble_fuse_kernel(EnsembleArgs a) {

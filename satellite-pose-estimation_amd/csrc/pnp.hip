@@ -640,7 +640,7 @@ __global__ __launch_bounds__(WAVE) void pnp_kernel(PnpArgs a) {
       __syncthreads();
       ok = s_ok[0];
       if (!ok) status = SPE_PNP_UNPINNED;
-      inl = all;
+      inl = ok ? all : 0u;                        // no pose, no inliers (as the RANSAC branch leaves it)
     } else {
       const int iters = a.ransac_iters < MAXIT ? a.ransac_iters : MAXIT;
       // 1. subset stream of cv::RNG((uint64)-1), drawn in order

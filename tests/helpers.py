@@ -4,12 +4,13 @@ import numpy as np
 from spe.config import world_points, project
 
 
-def solver_stress_set(B, seed=0, Q=11, C=12, noise=2.0, outlier_frac=0.1, degenerate_frac=0.05):
+def solver_stress_set(B, seed=0, Q=11, C=12, noise=2.0, outlier_frac=0.1, degenerate_frac=0.05, world=None):
     """Per image: labels a random permutation of 0..10 (+ duplicates / no-object queries), points
     = GT projection + N(0, noise px) + uniform outliers, a few images with <=3 or 0 foreground
-    labels.  Returns points [B,Q,2] f32 px, probs [B,Q,C] f32, q [B,4], t [B,3], sigmas [B,Q,2]."""
+    labels.  `world`: the C - 1 landmarks (default: the 11 real ones, C = 12).  Returns points [B,Q,2] f32
+    px, probs [B,Q,C] f32, q [B,4], t [B,3], sigmas [B,Q,2]."""
     rng = np.random.default_rng(seed)
-    W = world_points()
+    W = world_points() if world is None else np.asarray(world, np.float64)
     pts = np.zeros((B, Q, 2), np.float32)
     probs = np.zeros((B, Q, C), np.float32)
     qs, ts = np.zeros((B, 4)), np.zeros((B, 3))
