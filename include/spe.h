@@ -465,6 +465,52 @@ int spe_self_assess(void* stream, const float* probs, const float* sigmas, const
                     int num_classes, float score_th, float sigma_th, int min_inliers, float* mean_sigma,
                     int32_t* n_confident, uint8_t* reliable);
 
+/* Pose covariance from the keypoint sigmas: the first-order (Gauss-Newton) covariance of the solved
+ * pose under independent Gaussian keypoint noise with the predicted sigmas.  No reference code exists;
+ * this comment is the definition.  Inputs are spe_forward's probs / sigmas and a solver's status /
+ * corr_label / inlier_mask / rvec / tvec (spe_pnp_batch in any mode, spe_pnp_exhaustive); all device
+ * pointers; K and world as for spe_pnp_batch (world is read as fp64, as passed).
+ *
+ * Correspondences.  Correspondence i of image b has label corr_label[b][i]; its query is the one the
+ * solver selected for that label (highest foreground score, the first on ties: the selection
+ * spe_self_assess re-derives, the same code).  Only correspondences whose bit is set in inlier_mask
+ * take part, and only where the label is a landmark (0 <= label < num_classes - 1) that some query
+ * carries; the inlier count below counts those.
+ *
+ * Sigma.  sigmas [B,Q,2] is PostProcess's sigma, exp(pred_sigmas), in the caller's unit; sigma_scale
+ * [B,2] (nullable: sigma is in pixels already) multiplies it per image and axis into pixels, the product
+ * taken in fp64.  Effective sigma = max(sigma * scale, sigma_floor); sigma_floor must be positive and finite.
+ * A product that is not finite on either axis of a taking-part correspondence is a bad sigma.
+ *
+ * Perturbation.  R <- exp([dw]x) R, t <- t + dt in the camera frame; state order (dw, dt), rad then
+ * metres.  Per taking-part correspondence with landmark X: Xc = R X + t = (x, y, z) and
+ *     J = [[fx/z, 0, -fx x/z^2], [0, fy/z, -fy y/z^2]] . [ -[R X]x | I ]      (2x6, fp64; fx = K[0], fy = K[4])
+ * Information H = sum J^T diag(1/sx^2, 1/sy^2) J over the correspondences in fp64, by a fixed summation
+ * tree (correspondence i with i^8, then ^4, ^2, ^1; absent ones contribute 0), so two runs give the same
+ * bits.  Covariance = H^-1 by Cholesky of the Jacobi-scaled D^-1/2 H D^-1/2, D = diag H (the rad and
+ * metre blocks differ by about z^2), unscaled afterwards.
+ *
+ * Outputs: cov [B,6,6] fp64, symmetric, fully written; sigma_rot [B] = sqrt(tr cov_ww) rad; sigma_t [B,3]
+ * = sqrt of the translation diagonal, metres; pred_score [B] = sigma_rot + sqrt(tr cov_tt) / |t|, the
+ * first-order RMS prediction of the SPEED score (angle error + relative translation error); cov_status [B]:
+ *     0 ok
+ *     1 no pose (solver status not 0 or 3)
+ *     2 fewer than 3 taking-part inliers
+ *     3 bad sigma
+ *     4 singular: a taking-part point with z <= 0 (or not a number), a diagonal of H that is not positive
+ *       and finite, a pivot of the scaled matrix <= 64 * DBL_EPSILON, or a result that is not finite (|t| = 0)
+ * tested in this order, the first that applies.  For a non-zero status every numeric output of the image is
+ * 0: no NaN leaves the kernel.  num_queries <= 64, 2 <= num_classes <= 17, batch >= 1, else SPE_E_ARG
+ * before any launch.  One launch; no allocation, no scratch, no synchronisation. */
+int spe_pose_covariance(void* stream, const float* probs, const float* sigmas,
+                        const float* sigma_scale, const int32_t* status,
+                        const int32_t* corr_label, const uint32_t* inlier_mask,
+                        const double* rvec, const double* tvec, int batch,
+                        int num_queries, int num_classes, const double* K,
+                        const double* world, float sigma_floor, double* cov,
+                        float* sigma_rot, double* sigma_t, float* pred_score,
+                        int32_t* cov_status);
+
 /* speed_score per image (REV/utils/speed_eval.py:245-262), device pointers. */
 int spe_speed_score(void* stream, const float* quat, const double* tvec, const double* q_gt, const double* t_gt,
                     int batch, double* s_t, double* s_q);

@@ -197,6 +197,21 @@ int spe_self_assess(void* stream, const float* probs, const float* sigmas, const
   return 0;
 }
 
+int spe_pose_covariance(void* stream, const float* probs, const float* sigmas, const float* sigma_scale,
+                        const int32_t* status, const int32_t* corr_label, const uint32_t* inlier_mask,
+                        const double* rvec, const double* tvec, int B, int Q, int C, const double* K,
+                        const double* world, float sigma_floor, double* cov, float* sigma_rot, double* sigma_t,
+                        float* pred_score, int32_t* cov_status) {
+  if (!probs || !sigmas || !status || !corr_label || !inlier_mask || !rvec || !tvec || !K || !world || !cov ||
+      !sigma_rot || !sigma_t || !pred_score || !cov_status || B < 1 || Q <= 0 || Q > 64 || C < 2 || C > 17)
+    return fail(SPE_E_ARG, "bad argument");
+  if (!(sigma_floor > 0) || !(sigma_floor < INFINITY)) return fail(SPE_E_ARG, "sigma_floor must be positive and finite");
+  PoseCovArgs a{probs, sigmas, sigma_scale, status, corr_label, inlier_mask, rvec, tvec, B, Q, C, K, world,
+                sigma_floor, cov, sigma_rot, sigma_t, pred_score, cov_status};
+  CK(spe_launch_pose_cov(a, (hipStream_t)stream));
+  return 0;
+}
+
 int spe_speed_score(void* stream, const float* quat, const double* tvec, const double* q_gt, const double* t_gt, int B,
                     double* s_t, double* s_q) {
   if (!quat || !tvec || !q_gt || !t_gt || !s_t || !s_q || B < 0) return fail(SPE_E_ARG, "bad argument");

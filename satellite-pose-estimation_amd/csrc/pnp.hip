@@ -136,6 +136,21 @@ __device__ void epnp_solve_wave(EpnpShared& sh, const cam_t* k, const float* img
   __syncthreads();
 }
 
+// The two rules of the correspondence selection (REV/utils/speed_eval.py:152-206) that the solver,
+// the self-assessment and the pose covariance share: a query's label is the argmax of its C class
+// probabilities (the lower class on ties), and a label's query is the one with the highest such
+// score (the earlier query on ties).
+SPE_DEV int argmax_class(const float* p, int C, float* score) {
+  int lab = 0;
+  float sc = p[0];
+  for (int c = 1; c < C; ++c)
+    if (p[c] > sc) { sc = p[c]; lab = c; }
+  *score = sc;
+  return lab;
+}
+// does a later query with score `sc` replace the label's best so far (best_q < 0: none yet)
+SPE_DEV bool takes_over(int best_q, float best_s, float sc) { return best_q < 0 || sc > best_s; }
+
 // Correspondence selection (REV/utils/speed_eval.py:152-206): lane-parallel argmax over the C
 // class probabilities, then (lane 0) first-seen label order with the best-score query per label.
 struct SelShared {
@@ -148,11 +163,8 @@ struct SelShared {
 __device__ void select_correspondences(const PnpArgs& a, int b, int lane, SelShared& sh) {
   const int Q = a.Q, C = a.C;
   for (int q = lane; q < Q; q += WAVE) {
-    const float* p = a.probs + ((size_t)b * Q + q) * C;
-    int lab = 0;
-    float sc = p[0];
-    for (int c = 1; c < C; ++c)
-      if (p[c] > sc) { sc = p[c]; lab = c; }
+    float sc;
+    const int lab = argmax_class(a.probs + ((size_t)b * Q + q) * C, C, &sc);
     if (q < WAVE) { sh.lab[q] = lab; sh.score[q] = sc; }
   }
   __syncthreads();
@@ -198,13 +210,9 @@ struct LmShared {
   double x[6];               // fallback step
 };
 
-// S x = b for symmetric S (lower triangle read); false when S is not safely positive definite
-__device__ __forceinline__ bool chol6_solve(const double* S, const double* b, double* x) {
-  double L[6][6], y[6];
-  double maxd = 0;
-#pragma unroll
-  for (int i = 0; i < 6; ++i) maxd = fmax(maxd, fabs(S[i * 7]));
-  const double thr = maxd * 1e-10;
+// Cholesky factor L (lower) of symmetric S (lower triangle read); false at the first pivot that is
+// not above thr
+__device__ __forceinline__ bool chol6_factor(const double* S, double thr, double (*L)[6]) {
 #pragma unroll
   for (int j = 0; j < 6; ++j) {
     double s = S[j * 6 + j];
@@ -221,6 +229,12 @@ __device__ __forceinline__ bool chol6_solve(const double* S, const double* b, do
       L[i][j] = t * inv;
     }
   }
+  return true;
+}
+
+// L L^T x = b
+__device__ __forceinline__ void chol6_backsolve(const double (*L)[6], const double* b, double* x) {
+  double y[6];
 #pragma unroll
   for (int i = 0; i < 6; ++i) {
     double t = b[i];
@@ -235,6 +249,16 @@ __device__ __forceinline__ bool chol6_solve(const double* S, const double* b, do
     for (int p = i + 1; p < 6; ++p) t -= L[p][i] * x[p];
     x[i] = t / L[i][i];
   }
+}
+
+// S x = b for symmetric S (lower triangle read); false when S is not safely positive definite
+__device__ __forceinline__ bool chol6_solve(const double* S, const double* b, double* x) {
+  double L[6][6];
+  double maxd = 0;
+#pragma unroll
+  for (int i = 0; i < 6; ++i) maxd = fmax(maxd, fabs(S[i * 7]));
+  if (!chol6_factor(S, maxd * 1e-10, L)) return false;
+  chol6_backsolve(L, b, x);
   return true;
 }
 
@@ -801,13 +825,10 @@ __global__ void self_assess_kernel(SelfAssessArgs a) {
   float best_s[MAXN];
   for (int l = 0; l < MAXN; ++l) { best_q[l] = -1; best_s[l] = 0.f; }
   for (int q = 0; q < Q; ++q) {
-    const float* p = a.probs + ((size_t)b * Q + q) * C;
-    int lab = 0;
-    float sc = p[0];
-    for (int c = 1; c < C; ++c)
-      if (p[c] > sc) { sc = p[c]; lab = c; }
+    float sc;
+    const int lab = argmax_class(a.probs + ((size_t)b * Q + q) * C, C, &sc);
     if (lab == C - 1) continue;
-    if (best_q[lab] < 0 || sc > best_s[lab]) { best_q[lab] = q; best_s[lab] = sc; }
+    if (takes_over(best_q[lab], best_s[lab], sc)) { best_q[lab] = q; best_s[lab] = sc; }
   }
   const int st = a.status[b];
   const uint32_t inl = (st == SPE_PNP_OK || st == SPE_PNP_RANSAC_FALLBACK) ? a.inlier_mask[b] : 0u;
@@ -827,6 +848,165 @@ __global__ void self_assess_kernel(SelfAssessArgs a) {
   a.mean_sigma[b] = ms;
   a.n_confident[b] = nconf;
   a.reliable[b] = (n > 0 && nconf >= a.min_inliers && ms < a.sigma_th) ? 1 : 0;
+}
+
+// Pose covariance from the keypoint sigmas (definition: include/spe.h spe_pose_covariance).  One
+// wave per image, COV_WAVES images per work-group; no LDS, no barrier (the waves of a group share
+// nothing).  Lane q takes query q's label and score; lane i < 16 then owns correspondence i: it
+// finds its label's query by the selection's rule over the wave's (label, score) pairs, builds its
+// 2x6 Jacobian and its 21 upper-triangle terms of J^T W J (0 when the correspondence takes no part).
+// The xor butterfly 8, 4, 2, 1 sums them over the 16 lanes -- ((i, i^8), (.., ^4), (.., ^2), (.., ^1)),
+// a fixed tree -- and lane 0 factorises, inverts and writes.
+constexpr int COV_WAVES = 4;
+
+__global__ __launch_bounds__(WAVE * COV_WAVES) void pose_cov_kernel(PoseCovArgs a) {
+  const int lane = threadIdx.x & (WAVE - 1);
+  const int b = blockIdx.x * COV_WAVES + (int)(threadIdx.x / WAVE);
+  if (b >= a.B) return;                               // wave-uniform
+  const int Q = a.Q, C = a.C;
+
+  int lab_q = C - 1;
+  float sc_q = 0.f;
+  if (lane < Q) lab_q = argmax_class(a.probs + ((size_t)b * Q + lane) * C, C, &sc_q);
+  const int st = a.status[b];
+  const bool have_pose = st == SPE_PNP_OK || st == SPE_PNP_RANSAC_FALLBACK;
+  const uint32_t inl = have_pose ? a.inlier_mask[b] : 0u;
+  int mylab = -1;
+  if (lane < MAXN && ((inl >> lane) & 1u)) mylab = a.corr_label[MAXN * b + lane];
+  if (mylab >= C - 1) mylab = -1;                     // not a landmark: takes no part
+  int best_q = -1;
+  float best_s = 0.f;
+  for (int q = 0; q < Q; ++q) {
+    const int l = __shfl(lab_q, q);
+    const float s = __shfl(sc_q, q);
+    if (l == mylab && takes_over(best_q, best_s, s)) { best_q = q; best_s = s; }
+  }
+  const bool part = best_q >= 0;
+  const int n = __popcll(__ballot(part));
+
+  double t[3] = {0, 0, 0};
+  double h[21];
+#pragma unroll
+  for (int e = 0; e < 21; ++e) h[e] = 0;
+  bool bad_sigma = false, bad_z = false;
+  if (part) {
+    const float* sg = a.sigmas + ((size_t)b * Q + best_q) * 2;
+    double sx = (double)sg[0], sy = (double)sg[1];
+    if (a.sigma_scale) { sx *= (double)a.sigma_scale[2 * b]; sy *= (double)a.sigma_scale[2 * b + 1]; }
+    bad_sigma = !(fabs(sx) < (double)INFINITY) || !(fabs(sy) < (double)INFINITY);
+    sx = fmax(sx, (double)a.sigma_floor);
+    sy = fmax(sy, (double)a.sigma_floor);
+    const double wx = 1.0 / (sx * sx), wy = 1.0 / (sy * sy);
+    double R[9], r[3];
+    for (int i = 0; i < 3; ++i) { r[i] = a.rvec[3 * b + i]; t[i] = a.tvec[3 * b + i]; }
+    rodrigues_r2R(r, R);
+    const double* X = a.world + 3 * mylab;
+    const double rx = R[0] * X[0] + R[1] * X[1] + R[2] * X[2];
+    const double ry = R[3] * X[0] + R[4] * X[1] + R[5] * X[2];
+    const double rz = R[6] * X[0] + R[7] * X[1] + R[8] * X[2];
+    const double x = rx + t[0], y = ry + t[1], z = rz + t[2];
+    bad_z = !(z > 0);
+    const double iz = 1.0 / z;
+    const double ax = a.K[0] * iz, cx = -(a.K[0] * x) * iz * iz;     // d u / d (x, z)
+    const double ay = a.K[4] * iz, cy = -(a.K[4] * y) * iz * iz;     // d v / d (y, z)
+    // rows of [ax 0 cx; 0 ay cy] . [ -[R X]x | I ]
+    const double J0[6] = {cx * ry, ax * rz - cx * rx, -(ax * ry), ax, 0.0, cx};
+    const double J1[6] = {cy * ry - ay * rz, -(cy * rx), ay * rx, 0.0, ay, cy};
+    int e = 0;
+#pragma unroll
+    for (int i = 0; i < 6; ++i)
+#pragma unroll
+      for (int j = i; j < 6; ++j) h[e++] = (J0[i] * wx) * J0[j] + (J1[i] * wy) * J1[j];
+  }
+  const bool any_bad_sigma = __ballot(bad_sigma) != 0, any_bad_z = __ballot(bad_z) != 0;
+#pragma unroll
+  for (int off = 8; off >= 1; off >>= 1)
+#pragma unroll
+    for (int e = 0; e < 21; ++e) h[e] += __shfl_xor(h[e], off);
+  if (lane != 0) return;
+
+  int cs = !have_pose ? 1 : n < 3 ? 2 : any_bad_sigma ? 3 : any_bad_z ? 4 : 0;
+  double cov[21];
+#pragma unroll
+  for (int e = 0; e < 21; ++e) cov[e] = 0;
+  double srot = 0, strn = 0, pred = 0;
+  if (cs == 0) {
+    // lane 0 took part or not: its t[] is only set in the first case
+    for (int i = 0; i < 3; ++i) t[i] = a.tvec[3 * b + i];
+    double d[6], S[36], L[6][6];
+    bool ok = true;
+    {
+      int e = 0;
+#pragma unroll
+      for (int i = 0; i < 6; ++i) {
+        const double hii = h[e];
+        ok = ok && hii > 0 && hii < (double)INFINITY;
+        d[i] = 1.0 / sqrt(hii);
+        e += 6 - i;
+      }
+      e = 0;
+#pragma unroll
+      for (int i = 0; i < 6; ++i)
+#pragma unroll
+        for (int j = i; j < 6; ++j) {
+          const double v = (h[e++] * d[i]) * d[j];
+          S[i * 6 + j] = v;
+          S[j * 6 + i] = v;
+        }
+    }
+    ok = ok && chol6_factor(S, 64.0 * DBL_EPSILON, L);
+    if (ok) {
+      double inv[6][6];
+#pragma unroll
+      for (int c = 0; c < 6; ++c) {
+        double e6[6], x6[6];
+#pragma unroll
+        for (int i = 0; i < 6; ++i) e6[i] = i == c ? 1.0 : 0.0;
+        chol6_backsolve(L, e6, x6);
+#pragma unroll
+        for (int i = 0; i < 6; ++i) inv[i][c] = x6[i];
+      }
+      int e = 0;
+#pragma unroll
+      for (int i = 0; i < 6; ++i)
+#pragma unroll
+        for (int j = i; j < 6; ++j) {
+          cov[e] = (inv[i][j] * d[i]) * d[j];
+          ok = ok && fabs(cov[e]) < (double)INFINITY && (i != j || cov[e] > 0);
+          e++;
+        }
+      const double trw = cov[0] + cov[6] + cov[11], trt = cov[15] + cov[18] + cov[20];
+      const double tn = sqrt(t[0] * t[0] + t[1] * t[1] + t[2] * t[2]);
+      srot = sqrt(trw);
+      strn = sqrt(trt);
+      pred = srot + strn / tn;
+      ok = ok && fabs(pred) < (double)INFINITY;
+    }
+    if (!ok) {
+      cs = 4;
+#pragma unroll
+      for (int e = 0; e < 21; ++e) cov[e] = 0;
+      srot = strn = pred = 0;
+    }
+  }
+  double* o = a.cov + (size_t)b * 36;
+  {
+    int e = 0;
+#pragma unroll
+    for (int i = 0; i < 6; ++i)
+#pragma unroll
+      for (int j = i; j < 6; ++j) {
+        o[i * 6 + j] = cov[e];
+        o[j * 6 + i] = cov[e];
+        e++;
+      }
+  }
+  a.sigma_rot[b] = (float)srot;
+  a.sigma_t[3 * b] = sqrt(cov[15]);
+  a.sigma_t[3 * b + 1] = sqrt(cov[18]);
+  a.sigma_t[3 * b + 2] = sqrt(cov[20]);
+  a.pred_score[b] = (float)pred;
+  a.cov_status[b] = cs;
 }
 
 // ---------------------------------------------------------------- exhaustive four-point subsets
@@ -1068,6 +1248,13 @@ int spe_launch_self_assess(const SelfAssessArgs& a, hipStream_t s) {
   if (a.B <= 0) return 0;
   if (a.Q > WAVE || a.C < 2 || a.C - 1 > MAXN) return -7;
   hipLaunchKernelGGL(self_assess_kernel, dim3((a.B + 127) / 128), dim3(128), 0, s, a);
+  return (int)hipGetLastError();
+}
+
+int spe_launch_pose_cov(const PoseCovArgs& a, hipStream_t s) {
+  if (a.B <= 0) return 0;
+  if (a.Q > WAVE || a.C < 2 || a.C - 1 > MAXN || !(a.sigma_floor > 0)) return -7;
+  hipLaunchKernelGGL(pose_cov_kernel, dim3((a.B + COV_WAVES - 1) / COV_WAVES), dim3(WAVE * COV_WAVES), 0, s, a);
   return (int)hipGetLastError();
 }
 

@@ -62,5 +62,27 @@ struct SelfAssessArgs {
   uint8_t* reliable;          // [B]
 };
 int spe_launch_self_assess(const SelfAssessArgs& a, hipStream_t s);
+
+// Pose covariance from the keypoint sigmas (include/spe.h spe_pose_covariance)
+struct PoseCovArgs {
+  const float* probs;         // [B][Q][C]
+  const float* sigmas;        // [B][Q][2]
+  const float* sigma_scale;   // [B][2] or null
+  const int32_t* status;      // [B]     (solver outputs)
+  const int32_t* corr_label;  // [B][16]
+  const uint32_t* inlier_mask;// [B]
+  const double* rvec;         // [B][3]
+  const double* tvec;         // [B][3]
+  int B, Q, C;
+  const double* K;            // 3x3 row-major
+  const double* world;        // [C-1][3]
+  float sigma_floor;
+  double* cov;                // [B][6][6]
+  float* sigma_rot;           // [B]
+  double* sigma_t;            // [B][3]
+  float* pred_score;          // [B]
+  int32_t* cov_status;        // [B]
+};
+int spe_launch_pose_cov(const PoseCovArgs& a, hipStream_t s);
 int spe_launch_score(const float* quat, const double* tvec, const double* q_gt, const double* t_gt, int B,
                      double* s_t, double* s_q, hipStream_t s);

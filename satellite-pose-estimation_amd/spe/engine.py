@@ -93,7 +93,8 @@ def evaluate(model, criterion, postprocessors, data_loader, gt_file, solver, dev
 
 
 @torch.no_grad()
-def evaluate_rtdetr(model, criterion, postprocessors, data_loader, gt_file, solver, device, output_dir=None):
+def evaluate_rtdetr(model, criterion, postprocessors, data_loader, gt_file, solver, device, output_dir=None,
+                    pose_cov=False):
     """The UNC RT-DETR evaluation loop (UNC/solver/speed_engine.py:123-202) with evaluate()'s
     interface.  Per batch: one device pass (RTDETR.forward with clip_bbox, so RTDETRPostProcessor
     runs fused; `postprocessors` is accepted for the reference's signature), the device criterion
@@ -104,7 +105,9 @@ def evaluate_rtdetr(model, criterion, postprocessors, data_loader, gt_file, solv
     names) by weight_dict again, so "loss" and "<k>" carry the weight twice and "<k>_unscaled"
     once.  The log entries carry the reference's extra fields (UNC speed_dataset.py:424-438):
     "sigma" and "aux_points_0..2", the first three aux_outputs entries' pred_logits (the reference
-    stores logits under that name) rounded to 2 decimals."""
+    stores logits under that name) rounded to 2 decimals.  pose_cov: each entry also carries
+    "pred_score", the pose covariance's first-order prediction of the image's score
+    (PoseSolver.pose_covariance; 0 where cov_status is not 0, which "cov_status" tells)."""
     evaluator = SpeedEval(gt_file, solver)
     meters = {}
 
@@ -131,11 +134,22 @@ def evaluate_rtdetr(model, criterion, postprocessors, data_loader, gt_file, solv
         s_t, s_q = device_speed_score(poses["quat"], poses["tvec"], q_gt, t_gt)
         evaluator.update_batch(filenames, outputs["points_px"], outputs["probs"], poses, s_t, s_q, outputs["sigmas"],
                                aux_logits=[a["pred_logits"] for a in aux[:3]])
+        if pose_cov:
+            _log_pred_score(evaluator.log, filenames,
+                            solver.pose_covariance(outputs["probs"], outputs["sigmas"], poses, clip_bbox=clip))
     evaluator.log = spe_dist.all_gather_log(evaluator.log)
     evaluator.summarize()
     stats = {k: s / max(n, 1) for k, (s, n) in meters.items()}
     stats["speed_eval_pose"] = evaluator.stats
     return stats, evaluator
+
+
+def _log_pred_score(log, filenames, cov):
+    """pred_score / cov_status of PoseSolver.pose_covariance into the per-image records."""
+    ps, cs = cov["pred_score"].cpu().numpy(), cov["cov_status"].cpu().numpy()
+    for i, f in enumerate(filenames):
+        log[f]["pred_score"] = float(np.around(ps[i], decimals=8))
+        log[f]["cov_status"] = int(cs[i])
 
 
 def _host_decode(data, height, width, filename):
@@ -169,7 +183,7 @@ def _batch_frames(files, names, decoder, device):
 
 @torch.no_grad()
 def generate_submission(models, postprocessors, anns, read_file, solver, device, batch_size, input_size,
-                        decoder=None, transform=None):
+                        decoder=None, transform=None, pose_cov=False):
     """The reference's gen_submission loop (REV/gen_submission_single.py:113-187; with a list of
     models, gen_prediction + gen_submission of gen_submission_multi.py:123-186) over SpeedSubmission
     (REV/datasets/speed.py:44-160), from the files' bytes on.
@@ -189,7 +203,10 @@ def generate_submission(models, postprocessors, anns, read_file, solver, device,
     59-168, is this pad-to-square crop): its u8 stems take the crops, its sigmas go to the solver -- a sigma
     solver such as SimplePoseSolverSigma (epnp_ransac_sigma).  Not supported here: a list of RTDETR models
     (the reference has no sigma fusion rule), and EPnPCeresSolver, whose per-image thresholds the reference
-    derives from the ground-truth box areas a submission set does not have (ValueError)."""
+    derives from the ground-truth box areas a submission set does not have (ValueError).
+
+    pose_cov (a single model with a sigma head): each record also carries "pred_score" and "cov_status"
+    (PoseSolver.pose_covariance on the crop-scaled sigmas); a status-1 crop's are 0 and 1, like its pose."""
     from .datasets import JpegDecoder, SpeedSubmissionTransform
     multi = isinstance(models, (list, tuple))
     if multi and not hasattr(solver, "solve_batch_multi"):
@@ -198,6 +215,8 @@ def generate_submission(models, postprocessors, anns, read_file, solver, device,
         raise ValueError("generate_submission: EPnPCeresSolver takes one threshold per image from the ground-truth "
                          "box areas (UNC speed_dataset.py:366-399), which a submission set lacks; use a solver "
                          "without them (epnp_ransac_sigma)")
+    if pose_cov and multi:
+        raise ValueError("generate_submission: pose_cov needs a single model's sigmas (no fusion rule for sigmas)")
     decoder = decoder if decoder is not None else JpegDecoder()
     transform = transform if transform is not None else SpeedSubmissionTransform(input_size)
     names = list(anns)
@@ -221,4 +240,13 @@ def generate_submission(models, postprocessors, anns, read_file, solver, device,
         for f, r in zip(batch, rec):
             quat, tvec = (np.zeros(4), np.zeros(3)) if r[7] else (r[0:4], r[4:7])
             log[f] = {"quat_pr": np.around(quat, decimals=6).tolist(), "tvec_pr": np.around(tvec, decimals=6).tolist()}
+        if pose_cov:
+            if o.get("sigmas") is None:
+                raise ValueError("generate_submission: pose_cov needs a model with a sigma head")
+            cov = solver.pose_covariance(o["probs"], o["sigmas"], poses, clip_bbox=t["clip_bbox"])
+            bad = t["status"] != 0
+            cov["pred_score"] = cov["pred_score"].masked_fill(bad, 0.0)
+            cov["cov_status"] = torch.where(bad & (cov["cov_status"] == 0), torch.ones_like(cov["cov_status"]),
+                                            cov["cov_status"])
+            _log_pred_score(log, batch, cov)
     return log

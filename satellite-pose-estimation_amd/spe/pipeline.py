@@ -52,9 +52,14 @@ class PosePipeline:
 
     def __init__(self, model: "DETR | RTDETR", solver: PoseSolver, batch: int, device="cuda", use_graph: bool = False,
                  self_assess: bool = True, overlap: bool = False, raw_frames=None, overlap_decode: bool = False,
-                 jpeg_max_bytes: int = 0, overlap_backbone: bool = False, host_input: bool = False):
+                 jpeg_max_bytes: int = 0, overlap_backbone: bool = False, host_input: bool = False,
+                 pose_cov: bool = False):
         self.model, self.solver, self.B = model, solver, batch
         self.self_assess = self_assess
+        # pose_cov (models with a sigma head): one more launch on the solver's stream after the solve,
+        # PoseSolver.pose_covariance; run()'s output then also carries pose_cov [B,6,6], pred_score,
+        # sigma_t, sigma_rot and cov_status.  Off: no launch and no key is added.
+        self.pose_cov = pose_cov
         # overlap: the solver / score / self-assessment of batch i run on a second HIP stream
         # while the forward of batch i+1 runs on the caller's stream (the solver occupies one
         # wave per image, far from filling the chip, and its latency is fp64-bound).  Results of
@@ -144,7 +149,7 @@ class PosePipeline:
         self.out = None
         _ = Q
 
-    def _solve(self, fo, stream=None, q_gt=None, t_gt=None, repro=None):
+    def _solve(self, fo, stream=None, q_gt=None, t_gt=None, repro=None, clip=None):
         sig = fo.get("sigmas")
         if self.per_image_th:
             poses = self.solver.solve_batch(fo["points_px"], fo["probs"], sig, stream=stream,
@@ -157,6 +162,12 @@ class PosePipeline:
         out = {"forward": fo, "poses": poses, "s_t": s_t, "s_q": s_q}
         if sig is not None and self.self_assess:
             out["assess"] = self.solver.self_assess(fo["probs"], sig, poses, stream=stream)   # config-4 filter
+        if self.pose_cov:
+            if sig is None:
+                raise ValueError("pose_cov: the model has no sigma head")
+            # the model's sigmas are crop-normalised like its points: to pixels by the crop's size
+            out.update(self.solver.pose_covariance(fo["probs"], sig, poses, stream=stream,
+                                                   clip_bbox=self.clip_bbox if clip is None else clip))
         return out
 
     def _decode(self):
@@ -257,7 +268,7 @@ class PosePipeline:
             for t in _tensors(fo):
                 t.record_stream(s1)
             out = self._solve(fo, stream=s1, q_gt=self.slot_q[slot], t_gt=self.slot_t[slot],
-                              repro=self.slot_repro[slot])
+                              repro=self.slot_repro[slot], clip=self.slot_clip[slot])
             ev = torch.cuda.Event()
             ev.record(s1)
             self.solve_done[slot] = ev
@@ -288,11 +299,12 @@ class PosePipeline:
         # the ground truth is snapshotted on the caller's stream: a load() of the next batch may
         # overwrite q_gt / t_gt while this batch's score still runs on the solver stream
         q_gt, t_gt, repro = self.q_gt.clone(), self.t_gt.clone(), self.repro.clone()
+        clip = self.clip_bbox.clone() if self.pose_cov else None
         s1.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(s1):
-            for t in list(_tensors(fo)) + [q_gt, t_gt, repro]:
+            for t in list(_tensors(fo)) + [q_gt, t_gt, repro] + ([clip] if clip is not None else []):
                 t.record_stream(s1)          # consumed on the solver stream
-            out = self._solve(fo, stream=s1, q_gt=q_gt, t_gt=t_gt, repro=repro)
+            out = self._solve(fo, stream=s1, q_gt=q_gt, t_gt=t_gt, repro=repro, clip=clip)
         out["stream"] = s1
         return out
 

@@ -87,6 +87,39 @@ class PoseSolver:
         out["reliable"] = out["reliable"].bool()
         return out
 
+    def pose_covariance(self, probs, sigmas, poses, clip_bbox=None, sigma_floor=1e-3, stream=None):
+        """First-order covariance of a solve_batch result's poses from the keypoint sigmas (definition:
+        include/spe.h spe_pose_covariance).  `poses` is solve_batch's dict of any solver class (status,
+        corr_label, inlier_mask, rvec, tvec).  clip_bbox [B,4] (x1, y1, x2, y2): the sigmas are
+        crop-normalised and scale to pixels by the crop's width and height, the factor PostProcess
+        applies to the points; None: they are in pixels.  Returns device tensors pose_cov [B,6,6] f64
+        (state order: rotation rad, translation m), sigma_rot [B] f32, sigma_t [B,3] f64, pred_score [B]
+        f32 and cov_status [B] i32 (0 ok, 1 no pose, 2 fewer than 3 inliers, 3 bad sigma, 4 singular;
+        the numeric outputs of a non-zero status are 0)."""
+        B, Q, C = probs.shape
+        dev = probs.device
+        Kd, Wd = self._consts(dev)
+        if C - 1 > Wd.shape[0]:
+            raise ValueError(f"pose_covariance: {C} classes need {C - 1} landmarks, the solver holds {Wd.shape[0]}")
+        out = dict(pose_cov=torch.empty(B, 6, 6, dtype=torch.float64, device=dev), sigma_rot=torch.empty(B, device=dev),
+                   sigma_t=torch.empty(B, 3, dtype=torch.float64, device=dev), pred_score=torch.empty(B, device=dev),
+                   cov_status=torch.empty(B, dtype=torch.int32, device=dev))
+        if B == 0:
+            return out
+        scale = None
+        if clip_bbox is not None:
+            # made on the stream the kernel reads it on
+            with torch.cuda.stream(stream if stream is not None else torch.cuda.current_stream()):
+                cb = clip_bbox.to(device=dev, dtype=torch.float32)
+                scale = torch.stack((cb[:, 2] - cb[:, 0], cb[:, 3] - cb[:, 1]), 1).contiguous()
+        _lib.check(_lib.lib().spe_pose_covariance(
+            _lib.stream_ptr(stream), _lib.ptr(probs.contiguous()), _lib.ptr(sigmas.contiguous()), _lib.ptr(scale),
+            _lib.ptr(poses["status"]), _lib.ptr(poses["corr_label"]), _lib.ptr(poses["inlier_mask"]),
+            _lib.ptr(poses["rvec"]), _lib.ptr(poses["tvec"]), B, Q, C, _lib.ptr(Kd), _lib.ptr(Wd), float(sigma_floor),
+            _lib.ptr(out["pose_cov"]), _lib.ptr(out["sigma_rot"]), _lib.ptr(out["sigma_t"]), _lib.ptr(out["pred_score"]),
+            _lib.ptr(out["cov_status"])), "spe_pose_covariance")
+        return out
+
     def find_index(self, logits):
         return logits.argmax(1), logits.max(1)
 
