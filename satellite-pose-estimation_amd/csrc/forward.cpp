@@ -95,6 +95,17 @@ struct BlockIn {
   bool x_compact;            // x holds only the even pixels, [B][H/2][H/2][ld]: all this block's stride-2 downsample reads
 };
 
+// a fused bottleneck tail (btail.hip, btail_wide.hip): y = relu(c3 over A (+ R)), then z = the second 1x1 conv c2
+// (the next block's permuted conv1, or the permuted input_proj) over y; the caller sets y and what its form adds
+BtailArgs btail_args(const Conv& c3, const void* A, int lda, const void* R, const Conv& c2, void* z, int ldz, int M) {
+  BtailArgs t{};
+  t.A = A; t.lda = lda; t.k1 = c3.K; t.R = R; t.ldr = c3.N;
+  t.w3 = c3.w; t.ld3 = c3.Kpad; t.b3 = c3.bias; t.ldy = c3.N; t.n1 = c3.N;
+  t.w1 = c2.w; t.ld1 = c2.Kpad; t.b1 = c2.bias; t.z = z; t.ldz = ldz; t.n2 = c2.N;
+  t.M = M;
+  return t;
+}
+
 // conv3 (+ residual R) + relu of a block: with the next block's conv1 as one launch (btail.hip, or
 // btail_wide.hip for layers 2 and 3) when the next block carries permuted conv1 weights (registry.cpp c1p) and the shapes are served
 // (*tailed), else the GEMM.  c3 over A is either Block::c3 over t2 or Block::c3ds over [t2 | x].
@@ -106,11 +117,8 @@ int conv3_tail_or_gemm(Fwd& f, const Block* nb, const Conv& c3, const void* A, i
   spe_model* m = f.m;
   int rc = 1;
   if (nb) {
-    BtailArgs t{};
-    t.A = A; t.lda = lda; t.k1 = c3.K; t.R = R; t.ldr = c3.N;
-    t.w3 = c3.w; t.ld3 = c3.Kpad; t.b3 = c3.bias; t.y = out; t.ldy = c3.N; t.n1 = c3.N;
-    t.w1 = nb->c1p.w; t.ld1 = nb->c1p.Kpad; t.b1 = nb->c1p.bias; t.z = f.P(f.w.t1); t.ldz = nb->c1.N; t.n2 = nb->c1.N;
-    t.M = M;
+    BtailArgs t = btail_args(c3, A, lda, R, nb->c1p, f.P(f.w.t1), nb->c1.N, M);
+    t.y = out;
     t.rows = m->btail_rows;
     // (below one 16-row tile per wave of the persistent grid the launch is latency, not store traffic: y stays
     // whole there, and the launch tables of the small golden cases stay as recorded)
@@ -154,11 +162,7 @@ int final_tail(Fwd& f, const Conv& c3, const void* A, int lda, const void* R, in
   spe_model* m = f.m;
   *done = false;
   if (!m->ipp.w || !spe_btail_wide_proj_enabled()) return 0;
-  BtailArgs t{};
-  t.A = A; t.lda = lda; t.k1 = c3.K; t.R = R; t.ldr = c3.N;
-  t.w3 = c3.w; t.ld3 = c3.Kpad; t.b3 = c3.bias; t.y = nullptr; t.ldy = c3.N; t.n1 = c3.N;
-  t.w1 = m->ipp.w; t.ld1 = m->ipp.Kpad; t.b1 = m->ipp.bias; t.z = f.P(f.w.src); t.ldz = f.d; t.n2 = m->ipp.N;
-  t.M = M;
+  const BtailArgs t = btail_args(c3, A, lda, R, m->ipp, f.P(f.w.src), f.d, M);   // (y stays null: never stored)
   if (t.n2 != f.d || !spe_btail_wide_proj_serves(t) || spe_btail_wide_tiles(t) < spe_cu_count() / 2) return 0;
   const double flops = 2.0 * M * ((double)c3.N * c3.K + (double)t.n2 * c3.N);
   const double bytes = ((double)M * (c3.K + t.n2) + (R ? (double)M * c3.N : 0.0)) * m->esz;
@@ -168,6 +172,28 @@ int final_tail(Fwd& f, const Conv& c3, const void* A, int lda, const void* R, in
   return 0;
 }
 
+// what both bottleneck forms derive from block bi and its input: where the output goes, its edge Ho, and a first
+// block's downsample conv over the whole input into w.ds (the 1x1 as a linear GEMM, the stride-2 1x1 as a conv)
+struct BlockPlan {
+  size_t outbuf;
+  int Ho, ds_mode;
+  const char* ds_kind;
+  GemmArgs ds;
+};
+BlockPlan block_plan(const Fwd& f, size_t bi, const BlockIn& in) {
+  const Ws& w = f.w;
+  const Block& blk = f.m->blocks[bi];
+  // layer1: blocks 0-2, layer2: 3-6 (its output xs8 is kept for the neck; the stride-16 model has none), layer3: 7-12
+  const bool keep8 = bi == 6 && f.m->backbone != SPE_BACKBONE_RESNET50_S16;
+  BlockPlan p{keep8 ? w.xs8 : (in.x == w.bufA ? w.bufB : w.bufA), (in.H + 2 - 3) / blk.stride + 1, GEMM_LINEAR, "conv.1x1", {}};
+  if (blk.has_ds && blk.stride == 1) p.ds = linear_args(blk.ds, f.P(in.x), in.ld, f.B * in.H * in.H, f.P(w.ds), blk.ds.N);
+  if (blk.has_ds && blk.stride != 1) {
+    p.ds_mode = GEMM_CONV; p.ds_kind = "conv.1x1s2";
+    p.ds = conv_args(blk.ds, f.P(in.x), f.B, in.H, in.H, f.P(w.ds), blk.ds.N);
+  }
+  return p;
+}
+
 // bottleneck block bi over `in`, which becomes the block's output; activation-scale slots 2 + 3 bi ...
 int bottleneck(Fwd& f, size_t bi, BlockIn& in) {
   spe_model* m = f.m;
@@ -175,16 +201,14 @@ int bottleneck(Fwd& f, size_t bi, BlockIn& in) {
   hipStream_t s = f.s;
   const int B = f.B, H = in.H;
   const Block& blk = m->blocks[bi];
+  const BlockPlan bp = block_plan(f, bi, in);
+  const size_t outbuf = bp.outbuf; const int Ho = bp.Ho;
   // bf16: layer1 block 0's conv3 + downsample run as one GEMM over [conv2 output | pool output]
   // (Block::c3ds): conv2 writes the left half of that concatenation (w.ds region, row stride c3ds.K),
   // the max-pool wrote the right half (backbone_stage)
   const bool fused = bi == 0 && blk.c3ds.w != nullptr;
   const Block* nb = bi + 1 < m->blocks.size() && m->blocks[bi + 1].c1p.w ? &m->blocks[bi + 1] : nullptr;
-  // layer1: blocks 0-2, layer2: 3-6 (its output xs8 is kept for the neck; the stride-16 model has none),
-  // layer3: 7-12
   const bool s16bb = m->backbone == SPE_BACKBONE_RESNET50_S16;
-  const size_t outbuf = (bi == 6 && !s16bb) ? w.xs8 : (in.x == w.bufA ? w.bufB : w.bufA);
-  const int Ho = (H + 2 - 3) / blk.stride + 1;
   float* const t1_amax = f.slot(2 + 3 * (int)bi);
   float* const t2_amax = f.slot(2 + 3 * (int)bi + 1);
   float* const out_amax = f.slot(2 + 3 * (int)bi + 2);
@@ -206,11 +230,7 @@ int bottleneck(Fwd& f, size_t bi, BlockIn& in) {
   } else {
     size_t res = in.x;
     if (blk.has_ds) {
-      if (blk.stride == 1) {
-        GemmArgs g = linear_args(blk.ds, f.P(in.x), in.ld, B * H * H, f.P(w.ds), blk.ds.N);
-        g.amax_a = in.amax;
-        CK(run_gemm(m, "conv.1x1", g, GEMM_LINEAR, s));
-      } else if (in.x_compact) {
+      if (blk.stride == 2 && in.x_compact) {
         // the previous tail stored exactly the pixels this conv reads, densely: the same conv kernel at stride 1
         // over [B][Ho][Ho] (the same rows in the same K order, so the same bits; the streaming GEMM_LINEAR
         // kernels sum K in another order and were not tried)
@@ -219,9 +239,9 @@ int bottleneck(Fwd& f, size_t bi, BlockIn& in) {
         GemmArgs g = conv_args(d1, f.P(in.x), B, Ho, Ho, f.P(w.ds), blk.ds.N);
         CK(run_gemm(m, "conv.1x1s2", g, GEMM_CONV, s));
       } else {
-        GemmArgs g = conv_args(blk.ds, f.P(in.x), B, H, H, f.P(w.ds), blk.ds.N);
+        GemmArgs g = bp.ds;
         g.amax_a = in.amax;
-        CK(run_gemm(m, "conv.1x1s2", g, GEMM_CONV, s));
+        CK(run_gemm(m, bp.ds_kind, g, bp.ds_mode, s));
       }
       res = w.ds;
     }
@@ -279,9 +299,8 @@ int bottleneck_gn(Fwd& f, size_t bi, BlockIn& in) {
   const Ws& w = f.w;
   const int B = f.B, H = in.H;
   const Block& blk = m->blocks[bi];
-  const bool s16bb = m->backbone == SPE_BACKBONE_RESNET50_S16;
-  const size_t outbuf = (bi == 6 && !s16bb) ? w.xs8 : (in.x == w.bufA ? w.bufB : w.bufA);
-  const int Ho = (H + 2 - 3) / blk.stride + 1;
+  const BlockPlan bp = block_plan(f, bi, in);
+  const size_t outbuf = bp.outbuf; const int Ho = bp.Ho;
   CK(bare_gemm(f, "conv.1x1", linear_args(blk.c1, f.P(in.x), in.ld, B * H * H, f.P(w.t1), blk.c1.N), GEMM_LINEAR));
   TRY(group_norm(f, f.P(w.t1), blk.c1.N, H, blk.c1.N, blk.n1, nullptr, 0, true));
   CK(bare_gemm(f, "conv.3x3", conv_args(blk.c2, f.P(w.t1), B, H, H, f.P(w.t2), blk.c2.N), GEMM_CONV));
@@ -289,10 +308,7 @@ int bottleneck_gn(Fwd& f, size_t bi, BlockIn& in) {
   size_t res = in.x;
   int ldr = in.ld;
   if (blk.has_ds) {
-    if (blk.stride == 1)
-      CK(bare_gemm(f, "conv.1x1", linear_args(blk.ds, f.P(in.x), in.ld, B * H * H, f.P(w.ds), blk.ds.N), GEMM_LINEAR));
-    else
-      CK(bare_gemm(f, "conv.1x1s2", conv_args(blk.ds, f.P(in.x), B, H, H, f.P(w.ds), blk.ds.N), GEMM_CONV));
+    CK(bare_gemm(f, bp.ds_kind, bp.ds, bp.ds_mode));
     TRY(group_norm(f, f.P(w.ds), blk.ds.N, Ho, blk.ds.N, blk.nds, nullptr, 0, false));
     res = w.ds;
     ldr = blk.ds.N;
@@ -387,15 +403,19 @@ int backbone_stage(Fwd& f, const ImageSrc& images) {
   const bool fuse0 = b0.c3ds.w != nullptr;
   const int uld = fuse0 ? b0.c3ds.K : 64;
   const size_t pool_at = fuse0 ? w.ds + (size_t)b0.c2.N * m->esz : w.pool;
-  if (m->group_norm) {
-    // 7x7/2 -> GN + ReLU -> max-pool: the unfused stem, its norm in place over the stem output
-    GemmArgs g = pairs ? conv_args(m->stem, f.P(w.x0), B, S + 6, S + 6, f.P(w.stem), 64)
-                       : conv_args(m->stem, f.P(w.x0), B, S, S, f.P(w.stem), 64);
-    CK(bare_gemm(f, "conv.stem", g, GEMM_CONV));
-    TRY(group_norm(f, f.P(w.stem), 64, H, 64, m->stem_n, nullptr, 0, true));
-    CK(run_other(m, "eltwise.maxpool", 0.0, (double)B * 64 * (H * H + Hp * Hp) * m->esz, s, [&] {
+  // the unfused stem: the 7x7/2 conv as a GEMM into w.stem (the pair-packed input carries its border), its max-pool
+  const int Sin = pairs ? S + 6 : S;
+  auto stem_args = [&] { return conv_args(m->stem, f.P(w.x0), B, Sin, Sin, f.P(w.stem), 64); };
+  auto maxpool = [&] {
+    return run_other(m, "eltwise.maxpool", 0.0, (double)B * 64 * (H * H + Hp * Hp) * m->esz, s, [&] {
       return spe_launch_maxpool3s2(f.P(w.stem), f.P(pool_at), B, H, H, 64, Hp, Hp, dt, s, uld);
-    }));
+    });
+  };
+  if (m->group_norm) {
+    // GN + ReLU between the two, in place over the stem output
+    CK(bare_gemm(f, "conv.stem", stem_args(), GEMM_CONV));
+    TRY(group_norm(f, f.P(w.stem), 64, H, 64, m->stem_n, nullptr, 0, true));
+    CK(maxpool());
   } else if (pairs && spe_stempool_enabled() && spe_stempool_fits(S)) {
     // stem + bias + ReLU + max-pool in one pass (stempool.hip): the stem output stays in registers
     const double flops = 2.0 * B * H * H * 64 * 7 * 8 * 4;
@@ -404,14 +424,11 @@ int backbone_stage(Fwd& f, const ImageSrc& images) {
       return spe_launch_stempool(f.P(w.x0), m->stem.w, m->stem.Kpad, m->stem.bias, f.P(pool_at), uld, B, S, s);
     }));
   } else {
-    GemmArgs g = pairs ? conv_args(m->stem, f.P(w.x0), B, S + 6, S + 6, f.P(w.stem), 64)
-                       : conv_args(m->stem, f.P(w.x0), B, S, S, f.P(w.stem), 64);
+    GemmArgs g = stem_args();
     g.act = ACT_RELU;
     g.amax_a = x0_amax; g.amax_c = stem_amax;
     CK(run_gemm(m, "conv.stem", g, GEMM_CONV, s));
-    CK(run_other(m, "eltwise.maxpool", 0.0, (double)B * 64 * (H * H + Hp * Hp) * m->esz, s, [&] {
-      return spe_launch_maxpool3s2(f.P(w.stem), f.P(pool_at), B, H, H, 64, Hp, Hp, dt, s, uld);
-    }));
+    CK(maxpool());
   }
   BlockIn x{pool_at, uld, Hp, stem_amax, false, false, false};  // (the max-pool's maximum is the stem's)
   const float* xs8_amax = nullptr;
@@ -628,11 +645,34 @@ int encoder_layer_pre(Fwd& f, const Enc& e, int li, const EncAttn& ea) {
   return 0;
 }
 
+// The tail of both encoder stages unless the decoder attends to the memory itself (xattn): all decoder layers'
+// cross-attention K (memory + pos) and V^T (memory) from `mem` (src; a pre-norm model's nrm) into ck / cvt.
+// mem_amax: mem's fp32h3 scale input; v_amax: the slot the V^T GEMM raises, bounding every cross-attention output
+int cross_kv_projection(Fwd& f, const void* mem, const float* mem_amax, float* v_amax) {
+  spe_model* m = f.m;
+  const Ws& w = f.w;
+  const int T = f.T, d = f.d, L = f.L, Mt = f.Mt;
+  {
+    // bf16 fused path: the last FFN wrote memory + pos (rounded once, like the reference's
+    // fp32 add) -> plain GEMM; its 8 MB pos.W^T table would not stay L2-resident
+    const bool have_srcpos = use_fused_ffn(m) && !m->enc.empty();
+    GemmArgs g = linear_args(m->crossK, have_srcpos ? f.P(w.srcpos) : mem, d, Mt, f.P(w.ck), L * d);
+    const int mode = have_srcpos ? GEMM_LINEAR : add_pos(m, g, m->pos, d, T, m->pos_crossK, L * d);
+    if (!have_srcpos) g.amax_a = mem_amax;
+    CK(run_gemm(m, "gemm.cross_kv", g, mode, f.s));
+  }
+  GemmArgs g = linear_args(m->crossV, mem, d, Mt, f.P(w.cvt), 8);
+  g.vt_T = T; g.vt_B = f.B;
+  g.amax_a = mem_amax; g.amax_c = v_amax;
+  CK(run_gemm(m, "gemm.cross_kv", g, GEMM_LINEAR, f.s));
+  return 0;
+}
+
 int encoder_stage_pre(Fwd& f) {
   spe_model* m = f.m;
   const Ws& w = f.w;
   hipStream_t s = f.s;
-  const int B = f.B, T = f.T, d = f.d, L = f.L, Mt = f.Mt;
+  const int d = f.d, Mt = f.Mt;
   const EncAttn ea = enc_attn_forms(f);
   // layer 0's norm1(src); without encoder layers the memory is encoder.norm(src)
   CK(run_layernorm(m, "ln.enc", f.P(w.src), m->enc.empty() ? m->eng : m->enc[0].n1g,
@@ -640,23 +680,14 @@ int encoder_stage_pre(Fwd& f) {
   int li = 0;
   for (const Enc& e : m->enc) TRY(encoder_layer_pre(f, e, li++, ea));
   if (spe_use_xattn(m)) return 0;               // (bf16: the last FFN wrote memory + pos into srcpos)
-  {
-    const bool have_srcpos = use_fused_ffn(m) && !m->enc.empty();
-    GemmArgs g = linear_args(m->crossK, f.P(have_srcpos ? w.srcpos : w.nrm), d, Mt, f.P(w.ck), L * d);
-    const int mode = have_srcpos ? GEMM_LINEAR : add_pos(m, g, m->pos, d, T, m->pos_crossK, L * d);
-    CK(run_gemm(m, "gemm.cross_kv", g, mode, s));
-  }
-  GemmArgs g = linear_args(m->crossV, f.P(w.nrm), d, Mt, f.P(w.cvt), 8);
-  g.vt_T = T; g.vt_B = B;
-  CK(run_gemm(m, "gemm.cross_kv", g, GEMM_LINEAR, s));
-  return 0;
+  return cross_kv_projection(f, f.P(w.nrm), nullptr, nullptr);
 }
 
 int encoder_stage(Fwd& f) {
   spe_model* m = f.m;
   const Ws& w = f.w;
   hipStream_t s = f.s;
-  const int B = f.B, T = f.T, d = f.d, L = f.L, Mt = f.Mt;
+  const int B = f.B, T = f.T, d = f.d, Mt = f.Mt;
   TRY(zero_slots(f, SPE_AMAX_BB, SPE_AMAX_DEC - SPE_AMAX_BB));
   const float* src_amax = f.slot(SPE_AMAX_BB - 1);
   const EncAttn ea = enc_attn_forms(f);
@@ -675,20 +706,7 @@ int encoder_stage(Fwd& f) {
     }));
     return 0;
   }
-  {
-    // bf16 fused path: the last FFN wrote memory + pos (rounded once, like the reference's
-    // fp32 add) -> plain GEMM; its 8 MB pos.W^T table would not stay L2-resident
-    const bool have_srcpos = use_fused_ffn(m) && !m->enc.empty();
-    GemmArgs g = linear_args(m->crossK, f.P(have_srcpos ? w.srcpos : w.src), d, Mt, f.P(w.ck), L * d);
-    const int mode = have_srcpos ? GEMM_LINEAR : add_pos(m, g, m->pos, d, T, m->pos_crossK, L * d);
-    if (!have_srcpos) g.amax_a = src_amax;
-    CK(run_gemm(m, "gemm.cross_kv", g, mode, s));
-  }
-  GemmArgs g = linear_args(m->crossV, f.P(w.src), d, Mt, f.P(w.cvt), 8);
-  g.vt_T = T; g.vt_B = B;
-  g.amax_a = src_amax; g.amax_c = f.slot(SPE_AMAX_DEC - 1);   // bounds every cross-attention output
-  CK(run_gemm(m, "gemm.cross_kv", g, GEMM_LINEAR, s));
-  return 0;
+  return cross_kv_projection(f, f.P(w.src), src_amax, f.slot(SPE_AMAX_DEC - 1));
 }
 
 // ---------------- decoder (REV/models/transformer.py:100-129,218-239)
@@ -725,6 +743,35 @@ int dec_proj_ln(Fwd& f, const Conv& wo, const void* fwo, const float* lg, const 
   return linear_residual_ln(f, "gemm.dec", "ln.dec", wo, f.P(w.dao), d, x_amax, Mq, f.P(w.tgt), f.P(w.dtmp), lg, lb);
 }
 
+// q/k (x + query_pos) and V^T projections + self-attention of the rows x (tgt; a pre-norm model's norm1(t)) into
+// dao; x_amax: x's fp32h3 scale input, o_amax: the slot the V^T projection raises, which bounds the attention output
+int dec_self_attention(Fwd& f, const Dec& e, const void* x, const float* x_amax, float* o_amax) {
+  spe_model* m = f.m;
+  const Ws& w = f.w;
+  hipStream_t s = f.s;
+  const int B = f.B, Q = f.Q, d = f.d, Mq = f.Mq;
+  {
+    GemmArgs g = linear_args(e.sqk, x, d, Mq, f.P(w.dqkv), 3 * d);
+    const int mode = add_pos(m, g, m->qpos, d, Q, e.qpos_sqk, 2 * d);
+    g.amax_a = x_amax;
+    CK(run_gemm(m, "gemm.dec", g, mode, s));
+  }
+  {
+    GemmArgs g = linear_args(e.sv, x, d, Mq, f.P(w.dvt), 8);
+    g.vt_T = Q; g.vt_B = B;
+    g.amax_a = x_amax; g.amax_c = o_amax;
+    CK(run_gemm(m, "gemm.dec", g, GEMM_LINEAR, s));
+  }
+  AttnArgs a{};
+  a.q = f.P(w.dqkv); a.ldq = 3 * d;
+  a.k = (char*)f.P(w.dqkv) + d * m->esz; a.ldk = 3 * d;
+  a.vt = f.P(w.dvt);
+  a.o = f.P(w.dao); a.ldo = d;
+  a.B = B; a.H = m->cfg.nheads; a.Tq = Q; a.Tk = Q; a.scale = f.scale;
+  CK(run_attn(m, "attn.dec_self", a, f.dt, s));
+  return 0;
+}
+
 // self-attention block of layer l: projections, attention, out-projection, norm1 over tgt
 int dec_self_block(Fwd& f, const Dec& e, int l, const float* tgt_amax) {
   spe_model* m = f.m;
@@ -748,27 +795,7 @@ int dec_self_block(Fwd& f, const Dec& e, int l, const float* tgt_amax) {
     return 0;
   }
   float* const o_amax = f.slot(SPE_AMAX_DEC + 2 * l);   // the sv GEMM's published maximum
-  {
-    GemmArgs g = linear_args(e.sqk, f.P(w.tgt), d, Mq, f.P(w.dqkv), 3 * d);
-    const int mode = add_pos(m, g, m->qpos, d, Q, e.qpos_sqk, 2 * d);
-    g.amax_a = tgt_amax;
-    CK(run_gemm(m, "gemm.dec", g, mode, s));
-  }
-  {
-    GemmArgs g = linear_args(e.sv, f.P(w.tgt), d, Mq, f.P(w.dvt), 8);
-    g.vt_T = Q; g.vt_B = B;
-    g.amax_a = tgt_amax; g.amax_c = o_amax;
-    CK(run_gemm(m, "gemm.dec", g, GEMM_LINEAR, s));
-  }
-  {
-    AttnArgs a{};
-    a.q = f.P(w.dqkv); a.ldq = 3 * d;
-    a.k = (char*)f.P(w.dqkv) + d * m->esz; a.ldk = 3 * d;
-    a.vt = f.P(w.dvt);
-    a.o = f.P(w.dao); a.ldo = d;
-    a.B = B; a.H = m->cfg.nheads; a.Tq = Q; a.Tk = Q; a.scale = f.scale;
-    CK(run_attn(m, "attn.dec_self", a, f.dt, s));
-  }
+  TRY(dec_self_attention(f, e, f.P(w.tgt), tgt_amax, o_amax));
   return dec_proj_ln(f, e.so, e.fso, e.n1g, e.n1b, o_amax);
 }
 
@@ -787,6 +814,29 @@ XattnArgs xattn_args(const Fwd& f, const Dec& e, const void* k, int ldk, const v
   return x;
 }
 
+// q' = (x + query_pos) . Wqk^T + bqk into xq: the query-side fold of Wq and Wk (xattn.hip) over the rows x (tgt; a
+// pre-norm model's norm2(t)); x_amax: the h3 GEMM's scale input (fp32h3)
+int dec_cross_query(Fwd& f, const Dec& e, const void* x, const float* x_amax) {
+  spe_model* m = f.m;
+  hipStream_t s = f.s;
+  const int Q = f.Q, d = f.d, Mq = f.Mq;
+  if (e.fxq && decffn_on()) {
+    // (16 rows, 256 columns) workgroups over the packed weights (decsa.hip)
+    DecQArgs qa{};
+    qa.x = x; qa.ldx = d; qa.M = Mq; qa.N = 8 * d;
+    qa.w = e.fxq; qa.bias = e.xq.bias; qa.R = e.xq_r; qa.ldr = 8 * d; qa.period = Q;
+    qa.y = f.P(f.w.xq); qa.ldy = 8 * d;
+    CK(run_other(m, "gemm.dec", 2.0 * Mq * d * 8.0 * d, 2.0 * Mq * (d + 8.0 * d) * m->esz + 2.0 * 8 * d * d * m->esz, s,
+                 [&] { return spe_launch_decq(qa, s); }));
+    return 0;
+  }
+  GemmArgs g = linear_args(e.xq, x, d, Mq, f.P(f.w.xq), 8 * d);
+  g.R = e.xq_r; g.ldr = 8 * d; g.r_period = Q;
+  g.amax_a = x_amax;
+  CK(run_gemm(m, "gemm.dec", g, GEMM_LINEAR, s));
+  return 0;
+}
+
 // cross-attention of layer l against the memory (spe_use_xattn) into dao, or straight through the
 // out-projection + norm2 into tgt (*xtail); *o_amax: the out-projection's fp32h3 scale input
 int dec_xattn(Fwd& f, const Dec& e, int l, const float* tgt_amax, const float** o_amax, bool* xtail) {
@@ -794,21 +844,7 @@ int dec_xattn(Fwd& f, const Dec& e, int l, const float* tgt_amax, const float** 
   const Ws& w = f.w;
   hipStream_t s = f.s;
   const int B = f.B, Q = f.Q, T = f.T, d = f.d, L = f.L, Mq = f.Mq;
-  // q' = (tgt + query_pos) . Wqk^T + bqk: the query-side fold of Wq and Wk (xattn.hip)
-  if (e.fxq && decffn_on()) {
-    // (16 rows, 256 columns) workgroups over the packed weights (decsa.hip)
-    DecQArgs qa{};
-    qa.x = f.P(w.tgt); qa.ldx = d; qa.M = Mq; qa.N = 8 * d;
-    qa.w = e.fxq; qa.bias = e.xq.bias; qa.R = e.xq_r; qa.ldr = 8 * d; qa.period = Q;
-    qa.y = f.P(w.xq); qa.ldy = 8 * d;
-    CK(run_other(m, "gemm.dec", 2.0 * Mq * d * 8.0 * d, 2.0 * Mq * (d + 8.0 * d) * m->esz + 2.0 * 8 * d * d * m->esz, s,
-                 [&] { return spe_launch_decq(qa, s); }));
-  } else {
-    GemmArgs g = linear_args(e.xq, f.P(w.tgt), d, Mq, f.P(w.xq), 8 * d);
-    g.R = e.xq_r; g.ldr = 8 * d; g.r_period = Q;
-    g.amax_a = tgt_amax;                    // fp32h3: the h3 GEMM's scale input
-    CK(run_gemm(m, "gemm.dec", g, GEMM_LINEAR, s));
-  }
+  TRY(dec_cross_query(f, e, f.P(w.tgt), tgt_amax));
   if (m->h3) {
     // fp32h3: scores and value sums against the memory's fp16 planes, three products each; the
     // merge applies Wv / bv in fp32 and raises max |o| for the out-projection
@@ -870,32 +906,37 @@ int dec_attn_map(Fwd& f, int l, float* map) {
   return 0;
 }
 
+// cross-attention of layer l against the memory's projected K / V^T (layer l's slices of ck / cvt) into dao: the
+// query projection of the rows x + query_pos (tgt; a pre-norm model's norm2(t)) into dqc, then the attention
+int dec_cross_attention_projected(Fwd& f, const Dec& e, int l, const void* x, const float* x_amax) {
+  spe_model* m = f.m;
+  const Ws& w = f.w;
+  const int B = f.B, Q = f.Q, T = f.T, d = f.d, L = f.L;
+  GemmArgs g = linear_args(e.cq, x, d, f.Mq, f.P(w.dqc), d);
+  const int mode = add_pos(m, g, m->qpos, d, Q, e.qpos_cq, d);
+  g.amax_a = x_amax;
+  CK(run_gemm(m, "gemm.dec", g, mode, f.s));
+  AttnArgs a{};
+  a.q = f.P(w.dqc); a.ldq = d;
+  a.k = (char*)f.P(w.ck) + (size_t)l * d * m->esz; a.ldk = L * d;
+  a.vt = (char*)f.P(w.cvt) + (size_t)l * B * d * T * m->esz;
+  a.o = f.P(w.dao); a.ldo = d;
+  a.B = B; a.H = m->cfg.nheads; a.Tq = Q; a.Tk = T; a.scale = f.scale;
+  CK(run_attn(m, "attn.dec_cross", a, f.dt, f.s));
+  return 0;
+}
+
 // cross-attention block of layer l: attention against the memory or its projected K / V^T (ck / cvt),
 // out-projection, norm2 over tgt
 int dec_cross_block(Fwd& f, const Dec& e, int l, const float* tgt_amax) {
   spe_model* m = f.m;
-  const Ws& w = f.w;
-  hipStream_t s = f.s;
-  const int B = f.B, Q = f.Q, T = f.T, d = f.d, L = f.L, Mq = f.Mq;
   bool xtail = false;                         // the merge + value + out-projection + norm2 ran in one launch
   // fp32h3: the out-projection's scale input (the crossV GEMM's published maximum, transformer stage)
   const float* cross_o_amax = f.slot(SPE_AMAX_DEC - 1);
   if (spe_use_xattn(m)) {
     TRY(dec_xattn(f, e, l, tgt_amax, &cross_o_amax, &xtail));
   } else {
-    {
-      GemmArgs g = linear_args(e.cq, f.P(w.tgt), d, Mq, f.P(w.dqc), d);
-      const int mode = add_pos(m, g, m->qpos, d, Q, e.qpos_cq, d);
-      g.amax_a = tgt_amax;
-      CK(run_gemm(m, "gemm.dec", g, mode, s));
-    }
-    AttnArgs a{};
-    a.q = f.P(w.dqc); a.ldq = d;
-    a.k = (char*)f.P(w.ck) + (size_t)l * d * m->esz; a.ldk = L * d;
-    a.vt = (char*)f.P(w.cvt) + (size_t)l * B * d * T * m->esz;
-    a.o = f.P(w.dao); a.ldo = d;
-    a.B = B; a.H = m->cfg.nheads; a.Tq = Q; a.Tk = T; a.scale = f.scale;
-    CK(run_attn(m, "attn.dec_cross", a, f.dt, s));
+    TRY(dec_cross_attention_projected(f, e, l, f.P(f.w.tgt), tgt_amax));
   }
   if (f.tap && f.tap->dec_map && f.tap->dec_layer == l) TRY(dec_attn_map(f, l, f.tap->dec_map));
   if (!xtail) TRY(dec_proj_ln(f, e.co, e.fco, e.n2g, e.n2b, cross_o_amax));
@@ -954,6 +995,14 @@ int run_heads(Fwd& f, const void* tgt, float* hs, float* logits, float* points, 
   return 0;
 }
 
+// the aux output of decoder layer l (every layer but the last, when the call asks for aux outputs): the heads
+// over the layer's output rows tgt, into layer l's slices of the aux outputs
+int aux_heads(Fwd& f, int l, const void* tgt, const spe_forward_outputs& out) {
+  if (!out.aux_logits || !out.aux_points || l + 1 >= f.L) return 0;
+  return run_heads(f, tgt, (float*)f.P(f.w.hs), out.aux_logits + (size_t)l * f.Mq * 12,
+                   out.aux_points + (size_t)l * f.Mq * 2, false, out);
+}
+
 // (reads only the memory -- src, srcpos, or ck / cvt -- that the encode stage left in the
 // workspace, so the two stages may run on different streams, e.g. batch i's decoder beside
 // batch i+1's backbone with two workspaces)
@@ -974,9 +1023,7 @@ int decoder_stage(Fwd& f, const spe_forward_outputs& out) {
     if (m->h3) tgt_amax = e.n2_bound;
     TRY(dec_ffn_block(f, e, l, tgt_amax));
     if (m->h3) tgt_amax = e.n3_bound;
-    if (out.aux_logits && out.aux_points && l + 1 < L)   // aux output of layer l, into the aux slices
-      TRY(run_heads(f, f.P(f.w.tgt), (float*)f.P(f.w.hs), out.aux_logits + (size_t)l * Mq * 12,
-                    out.aux_points + (size_t)l * Mq * 2, false, out));
+    TRY(aux_heads(f, l, f.P(f.w.tgt), out));
   }
   CK(run_heads(f, f.P(f.w.tgt), out.hs ? out.hs : (float*)f.P(f.w.hs), out.logits, out.points, true, out));
   return 0;
@@ -1005,63 +1052,23 @@ int decoder_layer_pre(Fwd& f, const Dec& e, int l, size_t* cur) {
   spe_model* m = f.m;
   const Ws& w = f.w;
   hipStream_t s = f.s;
-  const int B = f.B, Q = f.Q, T = f.T, d = f.d, L = f.L, Mq = f.Mq;
+  const int B = f.B, Q = f.Q, T = f.T, d = f.d, Mq = f.Mq;
   void* const n = f.P(w.dnrm);
   // ---- self-attention
   CK(run_layernorm(m, "ln.dec", f.P(*cur), e.n1g, e.n1b, n, nullptr, Mq, d, f.dt, s));
-  {
-    GemmArgs g = linear_args(e.sqk, n, d, Mq, f.P(w.dqkv), 3 * d);
-    const int mode = add_pos(m, g, m->qpos, d, Q, e.qpos_sqk, 2 * d);
-    CK(run_gemm(m, "gemm.dec", g, mode, s));
-  }
-  {
-    GemmArgs g = linear_args(e.sv, n, d, Mq, f.P(w.dvt), 8);
-    g.vt_T = Q; g.vt_B = B;
-    CK(run_gemm(m, "gemm.dec", g, GEMM_LINEAR, s));
-  }
-  {
-    AttnArgs a{};
-    a.q = f.P(w.dqkv); a.ldq = 3 * d;
-    a.k = (char*)f.P(w.dqkv) + d * m->esz; a.ldk = 3 * d;
-    a.vt = f.P(w.dvt);
-    a.o = f.P(w.dao); a.ldo = d;
-    a.B = B; a.H = m->cfg.nheads; a.Tq = Q; a.Tk = Q; a.scale = f.scale;
-    CK(run_attn(m, "attn.dec_self", a, f.dt, s));
-  }
+  TRY(dec_self_attention(f, e, n, nullptr, nullptr));
   TRY(dec_residual_gemm(f, e.so, f.P(w.dao), d, cur));
   // ---- cross-attention
   CK(run_layernorm(m, "ln.dec", f.P(*cur), e.n2g, e.n2b, n, nullptr, Mq, d, f.dt, s));
   if (spe_use_xattn(m)) {
-    // bf16, against the memory itself: q' = (n + query_pos) . Wqk^T + bqk, the memory in nrm, memory + pos in srcpos
-    if (e.fxq && decffn_on()) {
-      DecQArgs qa{};
-      qa.x = n; qa.ldx = d; qa.M = Mq; qa.N = 8 * d;
-      qa.w = e.fxq; qa.bias = e.xq.bias; qa.R = e.xq_r; qa.ldr = 8 * d; qa.period = Q;
-      qa.y = f.P(w.xq); qa.ldy = 8 * d;
-      CK(run_other(m, "gemm.dec", 2.0 * Mq * d * 8.0 * d, 2.0 * Mq * (d + 8.0 * d) * m->esz + 2.0 * 8 * d * d * m->esz, s,
-                   [&] { return spe_launch_decq(qa, s); }));
-    } else {
-      GemmArgs g = linear_args(e.xq, n, d, Mq, f.P(w.xq), 8 * d);
-      g.R = e.xq_r; g.ldr = 8 * d; g.r_period = Q;
-      CK(run_gemm(m, "gemm.dec", g, GEMM_LINEAR, s));
-    }
+    // bf16, against the memory itself: q' from n, the memory in nrm, memory + pos in srcpos
+    TRY(dec_cross_query(f, e, n, nullptr));
     XattnArgs x = xattn_args(f, e, f.P(w.srcpos), d, f.P(w.nrm), d);
     const double fl = 4.0 * B * 8.0 * Q * (double)T * d + 2.0 * Mq * 8.0 * d * 32;
     const double by = 2.0 * B * (double)T * d * m->esz + 2.0 * Mq * 8.0 * d * m->esz;
     CK(run_other(m, "attn.dec_cross", fl, by, s, [&] { return spe_launch_xattn(x, s); }));
   } else {
-    {
-      GemmArgs g = linear_args(e.cq, n, d, Mq, f.P(w.dqc), d);
-      const int mode = add_pos(m, g, m->qpos, d, Q, e.qpos_cq, d);
-      CK(run_gemm(m, "gemm.dec", g, mode, s));
-    }
-    AttnArgs a{};
-    a.q = f.P(w.dqc); a.ldq = d;
-    a.k = (char*)f.P(w.ck) + (size_t)l * d * m->esz; a.ldk = L * d;
-    a.vt = (char*)f.P(w.cvt) + (size_t)l * B * d * T * m->esz;
-    a.o = f.P(w.dao); a.ldo = d;
-    a.B = B; a.H = m->cfg.nheads; a.Tq = Q; a.Tk = T; a.scale = f.scale;
-    CK(run_attn(m, "attn.dec_cross", a, f.dt, s));
+    TRY(dec_cross_attention_projected(f, e, l, n, nullptr));
   }
   if (f.tap && f.tap->dec_map && f.tap->dec_layer == l) TRY(dec_attn_map(f, l, f.tap->dec_map));
   TRY(dec_residual_gemm(f, e.co, f.P(w.dao), d, cur));
@@ -1082,9 +1089,7 @@ int decoder_stage_pre(Fwd& f, const spe_forward_outputs& out) {
   size_t cur = f.w.tgt;
   for (int l = 0; l < L; ++l) {
     TRY(decoder_layer_pre(f, m->dec[l], l, &cur));
-    if (out.aux_logits && out.aux_points && l + 1 < L)
-      TRY(run_heads(f, f.P(cur), (float*)f.P(f.w.hs), out.aux_logits + (size_t)l * Mq * 12,
-                    out.aux_points + (size_t)l * Mq * 2, false, out));
+    TRY(aux_heads(f, l, f.P(cur), out));
   }
   CK(run_heads(f, f.P(cur), out.hs ? out.hs : (float*)f.P(f.w.hs), out.logits, out.points, true, out));
   return 0;

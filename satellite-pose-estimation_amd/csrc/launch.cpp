@@ -164,10 +164,9 @@ int add_pos(const spe_model* m, GemmArgs& g, const void* pos, int ldp, int perio
   return GEMM_LINEAR_ADD;
 }
 
-// Fused linear1 -> ReLU -> linear2 -> +residual -> LayerNorm over x (in place), bf16 models.
-int run_ffn(spe_model* m, const char* kind, const Conv& l1, const Conv& l2, const float* g, const float* b,
-            void* x, int M, hipStream_t s, const void* pos, void* ypos, int period, float* partial,
-            const void* w2_chunked) {
+// what both forms of the fused bf16 FFN (ffn.hip) take: M rows of x through l1 / l2 into y, LayerNorm g / b
+static FfnArgs ffn_args(const Conv& l1, const Conv& l2, const float* g, const float* b, const void* x, void* y, int M,
+                        const void* pos, void* ypos, int period, float* partial, const void* w2_chunked) {
   FfnArgs a{};
   a.pos = pos; a.ypos = ypos; a.pos_period = period;
   a.splits = partial ? spe_ffn_splits(M, l1.N) : 1;
@@ -177,8 +176,16 @@ int run_ffn(spe_model* m, const char* kind, const Conv& l1, const Conv& l2, cons
   a.w2 = w2_chunked ? w2_chunked : l2.w; a.ld2 = l2.Kpad; a.b2 = l2.bias;
   a.w2_chunked = w2_chunked != nullptr;        // W2 chunk-packed at finalize (ffn.hip)
   a.gamma = g; a.beta = b;
-  a.y = x; a.ldy = l1.K;
+  a.y = y; a.ldy = l1.K;
   a.M = M; a.D = l1.K; a.F = l1.N;
+  return a;
+}
+
+// Fused linear1 -> ReLU -> linear2 -> +residual -> LayerNorm over x (in place), bf16 models.
+int run_ffn(spe_model* m, const char* kind, const Conv& l1, const Conv& l2, const float* g, const float* b,
+            void* x, int M, hipStream_t s, const void* pos, void* ypos, int period, float* partial,
+            const void* w2_chunked) {
+  const FfnArgs a = ffn_args(l1, l2, g, b, x, x, M, pos, ypos, period, partial, w2_chunked);
   const double flops = 4.0 * M * (double)l1.K * l1.N;
   const double bytes = 2.0 * M * l1.K * m->esz + 2.0 * (double)l1.K * l1.N * m->esz;
   return run_other(m, kind, flops, bytes, s, [&] { return spe_launch_ffn_ln(a, s); });
@@ -189,18 +196,8 @@ int run_ffn(spe_model* m, const char* kind, const Conv& l1, const Conv& l2, cons
 int run_ffn_pre(spe_model* m, const char* kind, const Conv& l1, const Conv& l2, const float* g, const float* b,
                 const void* x, void* y, const float* g2, const float* b2n, void* y2, int M, hipStream_t s, const void* pos,
                 void* ypos, int period, float* partial, const void* w2_chunked) {
-  FfnArgs a{};
-  a.pos = pos; a.ypos = ypos; a.pos_period = period;
-  a.splits = partial ? spe_ffn_splits(M, l1.N) : 1;
-  a.partial = a.splits > 1 ? partial : nullptr;
-  a.x = x; a.ldx = l1.K;
-  a.w1 = l1.w; a.ld1 = l1.Kpad; a.b1 = l1.bias;
-  a.w2 = w2_chunked ? w2_chunked : l2.w; a.ld2 = l2.Kpad; a.b2 = l2.bias;
-  a.w2_chunked = w2_chunked != nullptr;
-  a.gamma = g; a.beta = b;
+  FfnArgs a = ffn_args(l1, l2, g, b, x, y, M, pos, ypos, period, partial, w2_chunked);
   a.gamma2 = g2; a.beta2 = b2n; a.y2 = y2;
-  a.y = y; a.ldy = l1.K;
-  a.M = M; a.D = l1.K; a.F = l1.N;
   const double flops = 4.0 * M * (double)l1.K * l1.N;
   const double bytes = (2.0 + (y2 ? 1.0 : 0.0) + (ypos ? 1.0 : 0.0)) * M * l1.K * m->esz + 2.0 * (double)l1.K * l1.N * m->esz;
   return run_other(m, kind, flops, bytes, s, [&] { return spe_launch_ffn_pre(a, s); });

@@ -116,6 +116,17 @@ static float bf2f(uint16_t b) {
   return f;
 }
 
+// fp32h3 row scale of K weights: max |w| 2^e in [2^12, 2^13); sc = 2^e scales the row before its fp16 split,
+// sinv = 2^-e undoes it in the epilogue (an all-zero row: 1, 1)
+struct RowScale { float sc, sinv; };
+static RowScale row_scale(const float* w, int K) {
+  float am = 0.f;
+  for (int k = 0; k < K; ++k) am = std::max(am, std::fabs(w[k]));
+  int ex = 0;
+  if (am > 0.f && std::isfinite(am)) std::frexp(am, &ex);
+  return {am > 0.f ? std::ldexp(1.f, 13 - ex) : 1.f, am > 0.f ? std::ldexp(1.f, ex - 13) : 1.f};
+}
+
 // pack host fp32 [N][K] rows (already in K order) into device T [N][Kpad]; fp32x6 models also
 // get the rows' three-way bf16 split x = hi + mid + lo (RNE each, remainders exact in fp32) as
 // planes [3][N][Kpad] right after them, registered in m->w6 for the x6 GEMM
@@ -154,15 +165,11 @@ void* upload_rows(spe_model* m, const std::vector<float>& rows, int N, int K, in
       std::vector<_Float16> b(2 * n, (_Float16)0.f);
       std::vector<float> si(N, 1.f);
       for (int r = 0; r < N; ++r) {
-        float am = 0.f;
-        for (int k = 0; k < K; ++k) am = std::max(am, std::fabs(h[(size_t)r * Kpad + k]));
-        int ex = 0;
-        if (am > 0.f && std::isfinite(am)) std::frexp(am, &ex);
-        const float sc = am > 0.f ? std::ldexp(1.f, 13 - ex) : 1.f;
-        si[r] = am > 0.f ? std::ldexp(1.f, ex - 13) : 1.f;
+        const RowScale rs = row_scale(&h[(size_t)r * Kpad], K);
+        si[r] = rs.sinv;
         for (int k = 0; k < K; ++k) {
           const size_t i = (size_t)r * Kpad + k;
-          const float x = h[i] * sc;
+          const float x = h[i] * rs.sc;
           const _Float16 hi = (_Float16)x;
           b[i] = hi;
           b[n + i] = (_Float16)(x - (float)hi);
@@ -180,6 +187,16 @@ float* upload_f32(spe_model* m, const float* p, size_t n) {
   float* dst = (float*)dalloc(m, n * 4);
   if (m->dmem) m->upload_err |= (int)hipMemcpy(dst, p, n * 4, hipMemcpyHostToDevice);
   return dst;
+}
+
+// host rows [N][K] (already in K order) + bias as a packed linear: Cin = K, the 1x1 geometry of a default Conv
+// (a conv's caller sets its own); a null bias uploads nothing
+Conv rows_conv(spe_model* m, const std::vector<float>& rows, int N, int K, const float* bias, size_t nbias) {
+  Conv c;
+  c.N = N; c.K = K; c.Kpad = pad64(K); c.Cin = K;
+  c.w = upload_rows(m, rows, N, K, c.Kpad);
+  if (bias) c.bias = upload_f32(m, bias, nbias);
+  return c;
 }
 
 // fp32h3, the one-pass encoder FFN (ffn_h3.hip): e.ffn_meta1 = (2^-e1, b1) per 32-unit hidden chunk
@@ -206,17 +223,10 @@ static void ffn_h3_prepare(spe_model* m, Enc& e, const std::string& p, int d, in
   std::vector<float> meta((size_t)ff * 2);
   double bound = 0.0;
   for (int j = 0; j < ff; ++j) {
-    float am = 0.f;
     double nn = 0.0;
-    for (int k = 0; k < d; ++k) {
-      const float v = w1[(size_t)j * d + k];
-      am = std::max(am, std::fabs(v));
-      nn += (double)v * v;
-    }
-    int ex = 0;
-    if (am > 0.f && std::isfinite(am)) std::frexp(am, &ex);
+    for (int k = 0; k < d; ++k) nn += (double)w1[(size_t)j * d + k] * w1[(size_t)j * d + k];
     const int c = j / 32, u = j % 32;
-    meta[(size_t)c * 64 + u] = am > 0.f ? std::ldexp(1.f, ex - 13) : 1.f;
+    meta[(size_t)c * 64 + u] = row_scale(&w1[(size_t)j * d], d).sinv;
     meta[(size_t)c * 64 + 32 + u] = b1[j];
     bound = std::max(bound, std::fabs((double)b1[j]) + std::sqrt(nn) * rx);
   }
@@ -225,11 +235,7 @@ static void ffn_h3_prepare(spe_model* m, Enc& e, const std::string& p, int d, in
   e.ffn_sh = std::ldexp(1.f, 13 - eb);
   std::vector<_Float16> planes(2 * n2);
   for (int n = 0; n < d; ++n) {
-    float am = 0.f;
-    for (int k = 0; k < ff; ++k) am = std::max(am, std::fabs(w2[(size_t)n * ff + k]));
-    int ex = 0;
-    if (am > 0.f && std::isfinite(am)) std::frexp(am, &ex);
-    const float sc = am > 0.f ? std::ldexp(1.f, 13 - ex) : 1.f;
+    const float sc = row_scale(&w2[(size_t)n * ff], ff).sc;
     for (int k = 0; k < ff; ++k) {
       const int src = (k / 32) * 32 + spe_ffn_h3_perm(k % 32);
       const float x = w2[(size_t)n * ff + src] * sc;
@@ -286,10 +292,8 @@ Conv pack_conv(spe_model* m, const std::vector<float>& w, const std::vector<floa
             const int k = cblk ? ((ci / 64) * kh * kw + tap) * 64 + ci % 64 : tap * cp + ci;
             rows[(size_t)co * K + k] = w[(((size_t)co * cin + ci) * kh + y) * kw + x];
           }
-  Conv c;
-  c.N = cout; c.K = K; c.Kpad = pad64(K); c.Cin = cp; c.KH = kh; c.KW = kw; c.stride = stride; c.pad = pad;
-  c.w = upload_rows(m, rows, c.N, c.K, c.Kpad);
-  c.bias = upload_f32(m, bias.data(), bias.size());
+  Conv c = rows_conv(m, rows, cout, K, bias.data(), bias.size());
+  c.Cin = cp; c.KH = kh; c.KW = kw; c.stride = stride; c.pad = pad;
   return c;
 }
 
@@ -299,6 +303,22 @@ std::vector<int64_t> param_shape(const spe_model* m, const std::string& key) {
   return {};
 }
 
+// eval BatchNorm `bn` (weight, bias, running_mean, running_var; eps 1e-5) over C channels as y = x * scale + shift,
+// in double; an empty key (a bare conv) is the identity
+void bn_fold(spe_model* m, const std::string& bn, int C, std::vector<double>& scale, std::vector<double>& shift) {
+  scale.assign(C, 1.0);
+  shift.assign(C, 0.0);
+  if (bn.empty()) return;
+  const auto& g = m->host[bn + ".weight"];
+  const auto& b = m->host[bn + ".bias"];
+  const auto& rm = m->host[bn + ".running_mean"];
+  const auto& rv = m->host[bn + ".running_var"];
+  for (int c = 0; c < C; ++c) {
+    scale[c] = (double)g[c] / std::sqrt((double)rv[c] + 1e-5);
+    shift[c] = (double)b[c] - (double)rm[c] * scale[c];
+  }
+}
+
 // conv weight `wkey` [cout][cin][kh][kw] with an eval BatchNorm `bnkey` (weight, bias,
 // running_mean, running_var; eps 1e-5) and/or a conv bias folded in (double arithmetic)
 void fold_conv(spe_model* m, const std::string& wkey, const std::string& bnkey, const std::string& biaskey,
@@ -306,18 +326,9 @@ void fold_conv(spe_model* m, const std::string& wkey, const std::string& bnkey, 
   const auto sh = param_shape(m, wkey);
   const int64_t cout = sh[0], per = sh[1] * sh[2] * sh[3];
   const auto& src = m->host[wkey];
-  std::vector<double> scale(cout, 1.0), shift(cout, 0.0);
-  if (!bnkey.empty()) {
-    const auto& g = m->host[bnkey + ".weight"];
-    const auto& b = m->host[bnkey + ".bias"];
-    const auto& rm = m->host[bnkey + ".running_mean"];
-    const auto& rv = m->host[bnkey + ".running_var"];
-    for (int64_t c = 0; c < cout; ++c) {
-      scale[c] = (double)g[c] / std::sqrt((double)rv[c] + 1e-5);
-      shift[c] = (double)b[c] - (double)rm[c] * scale[c];
-    }
-  }
-  if (!biaskey.empty()) {
+  std::vector<double> scale, shift;
+  bn_fold(m, bnkey, (int)cout, scale, shift);
+  if (!biaskey.empty()) {                          // (a conv bias is added as it is, not scaled)
     const auto& bb = m->host[biaskey];
     for (int64_t c = 0; c < cout; ++c) shift[c] += bb[c];
   }
@@ -341,11 +352,8 @@ Conv make_conv(spe_model* m, const std::string& wkey, const std::string& bnkey, 
 Conv make_linear(spe_model* m, const std::string& wkey, const std::string& bkey, int r0, int n, int K) {
   const auto& w = m->host[wkey];
   std::vector<float> rows(w.begin() + (size_t)r0 * K, w.begin() + (size_t)(r0 + n) * K);
-  Conv c;
-  c.N = n; c.K = K; c.Kpad = pad64(K); c.Cin = K;
-  c.w = upload_rows(m, rows, n, K, c.Kpad);
   const auto& b = m->host[bkey];
-  c.bias = upload_f32(m, b.data() + r0, n);
+  Conv c = rows_conv(m, rows, n, K, b.data() + r0, n);
   for (int r = 0; r < n; ++r) {
     double s = 0.0;
     for (int k = 0; k < K; ++k) s += std::fabs(rows[(size_t)r * K + k]);
@@ -436,27 +444,35 @@ void fold_cross_attention(spe_model* m, const std::string& p, Dec& e) {
         rqk[(size_t)q * HD + j] = (float)sum;
       }
   }
-  e.xq.N = HD; e.xq.K = d; e.xq.Kpad = pad64(d); e.xq.Cin = d;
-  e.xq.w = upload_rows(m, wqk, HD, d, e.xq.Kpad);
-  e.xq.bias = nullptr;
+  e.xq = rows_conv(m, wqk, HD, d, nullptr, 0);
   e.xq_r = upload_T(m, rqk);
   e.xv = make_linear(m, p + ".multihead_attn.in_proj_weight", p + ".multihead_attn.in_proj_bias", 2 * d, d, d);
 }
 
-int build_device(spe_model* m) {
-  const auto& c = m->cfg;
-  const int d = c.hidden_dim, ff = c.dim_feedforward, Q = c.num_queries;
-  const std::string b = "backbone.0.body";
-  // group_norm models fold nothing into the body convs (the statistics are per image): every conv is packed bare,
-  // with a zero bias the launch sequence never reads, and its norm layer's gamma / beta are uploaded beside it
-  const bool gn = m->group_norm != 0;
-  auto norm = [&](const std::string& key) { return gn ? std::string() : key; };
-  auto affine = [&](const std::string& key) {
-    GnAffine a;
-    if (gn) { a.g = upload_key(m, key + ".weight"); a.b = upload_key(m, key + ".bias"); }
-    return a;
-  };
-  m->stem_n = affine(b + ".bn1");
+// ---- build_device, one function per stage of forward.cpp; finalize runs them twice (sizing, then filling), so the
+// order of their dalloc / upload calls is the weight block's layout
+const std::string kBody = "backbone.0.body";
+
+// group_norm models fold nothing into the body convs (the statistics are per image): every conv is packed bare,
+// with a zero bias the launch sequence never reads, and its norm layer's gamma / beta are uploaded beside it
+std::string bn_key(const spe_model* m, const std::string& key) { return m->group_norm ? std::string() : key; }
+GnAffine gn_affine(spe_model* m, const std::string& key) {
+  GnAffine a;
+  if (m->group_norm) { a.g = upload_key(m, key + ".weight"); a.b = upload_key(m, key + ".bias"); }
+  return a;
+}
+
+// rows [n][K] of a folded 1x1 conv with column c taken from column perm(c) (the fused tails' weight orders)
+template <class Perm>
+std::vector<float> permuted_rows(const std::vector<float>& w, int n, int K, Perm perm) {
+  std::vector<float> rows((size_t)n * K);
+  for (int r = 0; r < n; ++r)
+    for (int c = 0; c < K; ++c) rows[(size_t)r * K + c] = w[(size_t)r * K + perm(c)];
+  return rows;
+}
+
+void build_stem(spe_model* m) {
+  m->stem_n = gn_affine(m, kBody + ".bn1");
   static const int stem_pairs = spe_env_int("SPE_STEM_PAIRS", 1);
   if (m->esz == 2 && stem_pairs) {
     // bf16: the pair-packed stem (SPE_STEM_PAIRS=0: the 8-channel tap-major stem, A/B knob).  The 7x7/s2/p3 conv over 3 channels runs as a 7x8/s2 conv
@@ -464,7 +480,7 @@ int build_device(spe_model* m) {
     // kw = 7 and ci = 3 have zero weights, K = 224 (4 K-steps) instead of 7*7*8 = 392 (7 K-steps),
     // and each 16-byte chunk is the taps kw, kw+1 of one row.
     std::vector<float> w, bias;
-    fold_conv(m, b + ".conv1.weight", norm(b + ".bn1"), "", w, bias);
+    fold_conv(m, kBody + ".conv1.weight", bn_key(m, kBody + ".bn1"), "", w, bias);
     constexpr int KH = 7, KW = 8, CI = 4, K = KH * KW * CI;
     std::vector<float> rows((size_t)64 * K, 0.f);
     if (m->dmem)
@@ -473,33 +489,34 @@ int build_device(spe_model* m) {
           for (int y = 0; y < 7; ++y)
             for (int x = 0; x < 7; ++x)
               rows[(size_t)co * K + (y * KW + x) * CI + ci] = w[(((size_t)co * 3 + ci) * 7 + y) * 7 + x];
-    Conv c;
-    c.N = 64; c.K = K; c.Kpad = pad64(K); c.Cin = CI; c.KH = KH; c.KW = KW; c.stride = 2; c.pad = 0;
-    c.w = upload_rows(m, rows, c.N, c.K, c.Kpad);
-    c.bias = upload_f32(m, bias.data(), bias.size());
-    m->stem = c;
+    m->stem = rows_conv(m, rows, 64, K, bias.data(), bias.size());
+    m->stem.Cin = CI; m->stem.KH = KH; m->stem.KW = KW; m->stem.stride = 2; m->stem.pad = 0;
   } else {
     // fp32 models: 3 channels padded to 4 (K = 7*7*4 = 196: half the 8-channel form's products; the
     // 16-byte chunk is one pixel); bf16 with SPE_STEM_PAIRS=0: 8 channels (a 16-byte bf16 chunk)
-    m->stem = make_conv(m, b + ".conv1.weight", norm(b + ".bn1"), "", m->esz == 4 ? 4 : 8, 2, 3);
+    m->stem = make_conv(m, kBody + ".conv1.weight", bn_key(m, kBody + ".bn1"), "", m->esz == 4 ? 4 : 8, 2, 3);
   }
+}
+
+void build_blocks(spe_model* m) {
+  const bool gn = m->group_norm != 0;
   m->blocks.clear();
   m->btail_rows = spe_btail_rows_enabled();
   m->btail_ycompact = spe_btail_ycompact_enabled();
   const int nblk[3] = {3, 4, 6};
   for (int li = 0; li < 3; ++li)
     for (int k = 0; k < nblk[li]; ++k) {
-      std::string p = b + ".layer" + std::to_string(li + 1) + "." + std::to_string(k);
+      std::string p = kBody + ".layer" + std::to_string(li + 1) + "." + std::to_string(k);
       Block blk;
       blk.stride = (k == 0 && li > 0) ? 2 : 1;
-      blk.c1 = make_conv(m, p + ".conv1.weight", norm(p + ".bn1"), "", 0, 1, 0);
-      blk.c2 = make_conv(m, p + ".conv2.weight", norm(p + ".bn2"), "", 0, blk.stride, 1);
-      blk.c3 = make_conv(m, p + ".conv3.weight", norm(p + ".bn3"), "", 0, 1, 0);
-      blk.n1 = affine(p + ".bn1"); blk.n2 = affine(p + ".bn2"); blk.n3 = affine(p + ".bn3");
+      blk.c1 = make_conv(m, p + ".conv1.weight", bn_key(m, p + ".bn1"), "", 0, 1, 0);
+      blk.c2 = make_conv(m, p + ".conv2.weight", bn_key(m, p + ".bn2"), "", 0, blk.stride, 1);
+      blk.c3 = make_conv(m, p + ".conv3.weight", bn_key(m, p + ".bn3"), "", 0, 1, 0);
+      blk.n1 = gn_affine(m, p + ".bn1"); blk.n2 = gn_affine(m, p + ".bn2"); blk.n3 = gn_affine(m, p + ".bn3");
       if (k == 0) {
         blk.has_ds = true;
-        blk.ds = make_conv(m, p + ".downsample.0.weight", norm(p + ".downsample.1"), "", 0, blk.stride, 0);
-        blk.nds = affine(p + ".downsample.1");
+        blk.ds = make_conv(m, p + ".downsample.0.weight", bn_key(m, p + ".downsample.1"), "", 0, blk.stride, 0);
+        blk.nds = gn_affine(m, p + ".downsample.1");
         if (blk.stride == 1 && m->esz == 2 && !gn) {
           // conv3 + downsample of a stride-1 first block as ONE K = w + cin GEMM over the
           // channel concatenation [conv2 output | block input] (forward.cpp lays them out side by
@@ -516,10 +533,7 @@ int build_device(spe_model* m) {
             }
           std::vector<float> bias(n);
           for (int r = 0; r < n; ++r) bias[r] = b3[r] + bd[r];
-          Conv& f = blk.c3ds;
-          f.N = n; f.K = k3 + kd; f.Kpad = pad64(f.K); f.Cin = f.K;
-          f.w = upload_rows(m, rows, f.N, f.K, f.Kpad);
-          f.bias = upload_f32(m, bias.data(), bias.size());
+          blk.c3ds = rows_conv(m, rows, n, k3 + kd, bias.data(), bias.size());
         }
       }
       // conv1 of the blocks whose input is a layer-1 block output (blocks 1-3: layer 1 blocks 1
@@ -537,34 +551,26 @@ int build_device(spe_model* m) {
         std::vector<float> w1, b1;
         fold_conv(m, p + ".conv1.weight", p + ".bn1", "", w1, b1);
         const int n = blk.c1.N, K = blk.c1.K;
-        std::vector<float> rows((size_t)n * K, 0.f);
-        if (m->dmem)
-          for (int r = 0; r < n; ++r)
-            for (int c = 0; c < K; ++c) rows[(size_t)r * K + c] = w1[(size_t)r * K + (wide ? spe_btail_wide_perm(K, c) : spe_btail_perm(c))];
-        Conv& f = blk.c1p;
-        f.N = n; f.K = K; f.Kpad = pad64(K); f.Cin = K;
-        f.w = upload_rows(m, rows, f.N, f.K, f.Kpad);
-        f.bias = upload_f32(m, b1.data(), b1.size());
+        const auto rows = permuted_rows(w1, n, K, [&](int c) { return wide ? spe_btail_wide_perm(K, c) : spe_btail_perm(c); });
+        blk.c1p = rows_conv(m, rows, n, K, b1.data(), b1.size());
       }
       m->blocks.push_back(blk);
     }
+}
+
+// the stride-8 fusion neck and input_proj; the stride-16 model: input_proj alone, over block 12's output
+void build_neck(spe_model* m) {
   m->s8 = m->s16 = m->s16taps = m->outc = m->neckip = m->ipp = Conv{};
   if (m->backbone == SPE_BACKBONE_RESNET50_S16) {
     m->inproj = make_conv(m, "input_proj.weight", "", "input_proj.bias", 0, 1, 0);   // K = 1024, over block 12's output
     // Nobody but input_proj reads the last bottleneck's output, so bf16 models take input_proj as the
     // second product of that block's tail (btail_wide.hip's final form): its weights like a c1p
-    if (m->esz == 2 && spe_btail_wide_enabled() && m->inproj.K == 1024 && m->blocks.back().c3.N == 1024 && !gn) {
+    if (m->esz == 2 && spe_btail_wide_enabled() && m->inproj.K == 1024 && m->blocks.back().c3.N == 1024 && !m->group_norm) {
       std::vector<float> w, bias;
       fold_conv(m, "input_proj.weight", "", "input_proj.bias", w, bias);
       const int n = m->inproj.N, K = m->inproj.K;
-      std::vector<float> rows((size_t)n * K, 0.f);
-      if (m->dmem)
-        for (int r = 0; r < n; ++r)
-          for (int c = 0; c < K; ++c) rows[(size_t)r * K + c] = w[(size_t)r * K + spe_btail_wide_perm(K, c)];
-      Conv& f = m->ipp;
-      f.N = n; f.K = K; f.Kpad = pad64(K); f.Cin = K;
-      f.w = upload_rows(m, rows, f.N, f.K, f.Kpad);
-      f.bias = upload_f32(m, bias.data(), bias.size());
+      const auto rows = permuted_rows(w, n, K, [&](int c) { return spe_btail_wide_perm(K, c); });
+      m->ipp = rows_conv(m, rows, n, K, bias.data(), bias.size());
     }
   } else {
     m->s8 = make_conv(m, "backbone.0.s8_latern.weight", "", "", 0, 1, 0);
@@ -583,9 +589,7 @@ int build_device(spe_model* m) {
             for (int ci = 0; ci < ci_n; ++ci)
               rows[((size_t)t * co_n + co) * ci_n + ci] = src[((size_t)co * ci_n + ci) * 9 + t];
       }
-      Conv& c = m->s16taps;
-      c.N = 9 * co_n; c.K = ci_n; c.Kpad = pad64(ci_n); c.Cin = ci_n;
-      c.w = upload_rows(m, rows, c.N, c.K, c.Kpad);
+      m->s16taps = rows_conv(m, rows, 9 * co_n, ci_n, nullptr, 0);
     }
     m->outc = make_conv(m, "backbone.0.output_conv.weight", "", "backbone.0.output_conv.bias", 0, 1, 1);
     m->inproj = make_conv(m, "input_proj.weight", "", "input_proj.bias", 0, 1, 0);
@@ -616,9 +620,12 @@ int build_device(spe_model* m) {
       m->neckip = pack_conv(m, w, bias, co_n, ci_n, (int)so[2], (int)so[3], 0, 1, 1);
     }
   }
+}
 
+void build_encoder(spe_model* m) {
+  const int d = m->cfg.hidden_dim, ff = m->cfg.dim_feedforward;
   m->enc.clear();
-  for (int i = 0; i < c.enc_layers; ++i) {
+  for (int i = 0; i < m->cfg.enc_layers; ++i) {
     std::string p = "transformer.encoder.layers." + std::to_string(i);
     Enc e;
     e.qk = make_linear(m, p + ".self_attn.in_proj_weight", p + ".self_attn.in_proj_bias", 0, 2 * d, d);
@@ -637,6 +644,11 @@ int build_device(spe_model* m) {
     if (m->cfg.dtype == SPE_DTYPE_BF16_ && d == 256 && ff % 32 == 0) e.ffn_w2c = dalloc(m, (size_t)d * ff * 2);
     m->enc.push_back(e);
   }
+}
+
+void build_decoder(spe_model* m) {
+  const auto& c = m->cfg;
+  const int d = c.hidden_dim, ff = c.dim_feedforward;
   m->dec.clear();
   std::vector<float> kall, vall, kb, vb;
   for (int i = 0; i < c.dec_layers; ++i) {
@@ -683,15 +695,15 @@ int build_device(spe_model* m) {
   // all decoder layers' cross-attention K/V projections of the (fixed) memory, batched
   // (not needed when the cross-attention runs against the memory itself)
   if (spe_use_xattn(m)) { kall.clear(); vall.clear(); kb.clear(); vb.clear(); }
-  m->crossK.N = m->crossV.N = spe_use_xattn(m) ? 0 : c.dec_layers * d;
-  m->crossK.K = m->crossV.K = d;
-  m->crossK.Kpad = m->crossV.Kpad = pad64(d);
-  m->crossK.w = upload_rows(m, kall, m->crossK.N, d, m->crossK.Kpad);
-  m->crossK.bias = upload_f32(m, kb.data(), kb.size());
-  m->crossV.w = upload_rows(m, vall, m->crossV.N, d, m->crossV.Kpad);
-  m->crossV.bias = upload_f32(m, vb.data(), vb.size());
+  const int n = spe_use_xattn(m) ? 0 : c.dec_layers * d;
+  m->crossK = rows_conv(m, kall, n, d, kb.data(), kb.size());
+  m->crossV = rows_conv(m, vall, n, d, vb.data(), vb.size());
+}
 
-  const int fs = c.input_size / spe_feat_stride(m);
+// the position tables, the (pos . W^T) residual slots, the closing norms and the heads
+void build_heads(spe_model* m) {
+  const auto& c = m->cfg;
+  const int d = c.hidden_dim, fs = c.input_size / spe_feat_stride(m);
   m->pos = upload_T(m, sine_pos(fs, fs, d));
   m->qpos = upload_T(m, m->host["query_embed.weight"]);
   if (m->esz == 2 || m->x6) {
@@ -727,7 +739,15 @@ int build_device(spe_model* m) {
   } else {
     h.sg_w0t = h.sg_b0 = h.sg_w1t = h.sg_b1 = h.sg_w2t = h.sg_b2 = nullptr;
   }
-  (void)Q;
+}
+
+int build_device(spe_model* m) {
+  build_stem(m);
+  build_blocks(m);
+  build_neck(m);
+  build_encoder(m);
+  build_decoder(m);
+  build_heads(m);
   return 0;
 }
 

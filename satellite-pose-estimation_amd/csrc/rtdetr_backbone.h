@@ -58,8 +58,6 @@ inline const RtBackbone* rt_backbone_for(const spe_rtdetr_config& c) {   // null
 inline double image_px_bytes(const ImageSrc& img) { return img.u8 ? (double)img.ch : 12.0; }
 
 // ---- packing and launches the light backbones share (defined in rtdetr_mbv3.cpp, beside mbv3.hip's first user)
-// eval BatchNorm (eps 1e-5) as scale / shift in double, like fold_conv; an empty key (a bare conv): identity
-void bn_fold(spe_model* m, const std::string& bn, int C, std::vector<double>& scale, std::vector<double>& shift);
 Conv mb_conv(spe_model* m, const std::string& wkey, const std::string& bn, const std::string& biaskey, int stride,
              int pad, bool pool2 = false);
 MbDw mb_dw(spe_model* m, const std::string& wkey, const std::string& bn, int stride);

@@ -93,11 +93,7 @@ Conv gh_pw(spe_model* m, const std::string& conv, const std::string& bn, bool ha
     bias[n] = (float)shift[co];
     for (int ci = 0; ci < cin; ++ci) rows[(size_t)n * K + li.phys(ci)] = (float)((double)w[(size_t)co * cin + ci] * scale[co]);
   }
-  Conv c;
-  c.N = N; c.K = K; c.Kpad = pad64(K); c.Cin = K; c.KH = 1; c.KW = 1; c.stride = 1; c.pad = 0;
-  c.w = upload_rows(m, rows, c.N, c.K, c.Kpad);
-  c.bias = upload_f32(m, bias.data(), bias.size());
-  return c;
+  return rows_conv(m, rows, N, K, bias.data(), bias.size());
 }
 
 // depthwise conv [C][1][kh][kw] + BatchNorm -> fp32 taps [kh*kw][Cp] and bias [Cp]; half: C is a ghost half

@@ -8,21 +8,7 @@
 
 #define fail spe_fail
 
-// ---- shared with GhostNetV2: eval BatchNorm (eps 1e-5) folded in double, like fold_conv
-void bn_fold(spe_model* m, const std::string& bn, int C, std::vector<double>& scale, std::vector<double>& shift) {
-  scale.assign(C, 1.0);
-  shift.assign(C, 0.0);
-  if (bn.empty()) return;            // a bare conv (MobileNetV3_Small's Conv1 / Conv2): identity
-  const auto& g = m->host[bn + ".weight"];
-  const auto& b = m->host[bn + ".bias"];
-  const auto& rm = m->host[bn + ".running_mean"];
-  const auto& rv = m->host[bn + ".running_var"];
-  for (int c = 0; c < C; ++c) {
-    scale[c] = (double)g[c] / std::sqrt((double)rv[c] + 1e-5);
-    shift[c] = (double)b[c] - (double)rm[c] * scale[c];
-  }
-}
-
+// ---- shared with GhostNetV2 (the BatchNorm fold is registry.cpp's bn_fold; MobileNetV3_Small's bare Conv1 / Conv2: "")
 // conv [cout][cin][kh][kw] (+ a bias in front of the norm) + BatchNorm -> rows [cout][(y*kw + x)*cin + ci]
 // (the plain tap-major K order mb_gemm's A loader walks), folded bias.  pool2: the conv reads a 2x2 mean
 // of its input -- folded into a (2kh)x(2kw) kernel of stride 2*stride, pad 2*pad, w/4 per tap (exact).
@@ -44,10 +30,8 @@ Conv mb_conv(spe_model* m, const std::string& wkey, const std::string& bn, const
           rows[(size_t)co * K + (size_t)(y * KW + x) * cin + ci] =
               (float)((double)w[(((size_t)co * cin + ci) * kh + y / f) * kw + x / f] * scale[co] / (f * f));
   }
-  Conv c;
-  c.N = cout; c.K = K; c.Kpad = pad64(K); c.Cin = cin; c.KH = KH; c.KW = KW; c.stride = stride * f; c.pad = pad * f;
-  c.w = upload_rows(m, rows, c.N, c.K, c.Kpad);
-  c.bias = upload_f32(m, bias.data(), bias.size());
+  Conv c = rows_conv(m, rows, cout, K, bias.data(), bias.size());
+  c.Cin = cin; c.KH = KH; c.KW = KW; c.stride = stride * f; c.pad = pad * f;
   return c;
 }
 

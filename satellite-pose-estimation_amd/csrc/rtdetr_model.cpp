@@ -96,11 +96,7 @@ Conv stack_linears(spe_model* m, const std::vector<std::pair<std::string, std::s
     bias.insert(bias.end(), b.begin(), b.end());
     N += (int)b.size();
   }
-  Conv c;
-  c.N = N; c.K = K; c.Kpad = pad64(K); c.Cin = K;
-  c.w = upload_rows(m, rows, N, K, c.Kpad);
-  c.bias = upload_f32(m, bias.data(), bias.size());
-  return c;
+  return rows_conv(m, rows, N, K, bias.data(), bias.size());
 }
 
 RtHead make_head(spe_model* m, const std::string& cls, const std::string& box, const std::string& sigma) {

@@ -78,6 +78,16 @@ LAUNCH_TABLE_MODES = {"bf16": ("bf16", None), "bf16_attn_fp16": ("bf16", "fp16")
 # s128_q11_l2 in bf16 and fp32h3, also: encode then decode as two calls (their tables concatenated), the
 # 8-bit crop entry, and a call that fills the aux outputs
 LAUNCH_TABLE_VARIANTS = ["split", "u8", "aux"]
+# the stride-16, pre-norm and GroupNorm models, "<golden>-<mode>[-<variant>]": the smallest configs that reach each
+# of their branches (Q = 30: the projected-K/V cross-attention; l3 with aux: the pre-norm decoder's aux-head call)
+LAUNCH_TABLE_MODEL_VARIANTS = [
+    "prenorm_s8_s128_q11_l1-bf16", "prenorm_s8_s128_q11_l1-fp32",
+    "prenorm_s16_s224_q30_l2-bf16", "prenorm_s16_s224_q30_l2-fp32",
+    "prenorm_s8_s128_q11_l3-bf16", "prenorm_s8_s128_q11_l3-bf16-aux",
+    "groupnorm_s8_s128_q11_l1-bf16", "groupnorm_s8_s128_q11_l1-fp32",
+    "groupnorm_s16_s224_q30_l2-bf16",
+    "groupnorm_prenorm_s8_s128_q11_l1-bf16",
+    "r50s16_s128_q11_l2-bf16", "r50s16_s128_q11_l2-fp32", "r50s16_s128_q11_l2-fp32h3"]
 # RT-DETR cases, "<golden>-<dtype>": BasicBlock and BottleNeck PResNet, then the three light backbones (the
 # MobileNetV3_Small case takes the default fused entry)
 LAUNCH_TABLE_RTDETR = ["rtdetr_r18_s128-fp32", "rtdetr_r50_s256-bf16", "rtdetr_mbv3l_s256-fp32", "rtdetr_mbv3s_s256-bf16",
@@ -88,7 +98,7 @@ def launch_table_cases():
     """Case names of tests/golden/launch_tables.json."""
     names = [f"{t}-{m}" for t in LAUNCH_TABLE_TAGS for m in LAUNCH_TABLE_MODES]
     names += [f"s128_q11_l2-{m}-{v}" for m in ("bf16", "fp32h3") for v in LAUNCH_TABLE_VARIANTS]
-    return names + LAUNCH_TABLE_RTDETR
+    return names + LAUNCH_TABLE_RTDETR + LAUNCH_TABLE_MODEL_VARIANTS
 
 
 _lt_models = {}

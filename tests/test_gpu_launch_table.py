@@ -33,5 +33,6 @@ def test_launch_table_matches_golden(gpu_device, golden_tables, name):
         # encode then decode as two calls make the launches of the single call
         assert got == golden_tables[name[:-len("-split")]]
     if name.endswith("-aux"):
-        # a decoder_norm + heads pair per decoder layer but the last (s128_q11_l2: two layers)
-        assert len(got) == len(golden_tables[name[:-len("-aux")]]) + 2
+        # a decoder_norm + heads pair per decoder layer but the last (the golden's name ends in _l<layers>)
+        layers = int(name.split("-")[0].rsplit("_l", 1)[1])
+        assert len(got) == len(golden_tables[name[:-len("-aux")]]) + 2 * (layers - 1)
