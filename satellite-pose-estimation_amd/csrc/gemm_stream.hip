@@ -18,12 +18,19 @@
 //   current tile is multiplied, so every wave always has a tile in flight, epilogue included.
 //   No barrier after the prologue: W is read-only, the waves run independently.
 // * Epilogue straight from the accumulators.  Row-major outputs use MFMA(W, A) so a lane owns 4
-//   consecutive columns of one row (8-byte stores, residual read the same way); a row's BN
-//   columns live in one wave, so the fused post-norm LayerNorm (encoder norm1) is two
-//   shuffle reductions.  The head-transposed V^T store uses MFMA(A, W): 4 consecutive tokens of
-//   one column per lane.
+//   consecutive columns of one row per 16-column fragment.  ROWS: the W rows of the LDS image
+//   are permuted (on the source side of the copy, like the swizzle) so that the two fragments of
+//   a pair give a lane 8 consecutive columns, which leave as one 16-byte store -- a row's
+//   128-byte line in 4 x 2 stores instead of 4 x 4 -- with the residual read and the bias taken
+//   at the same columns; every output is the same dot product in the same order, bit for bit.
+//   Without ROWS (strides or bases that are not 16-byte multiples, SPE_SGEMM_ROWS=0, the
+//   LayerNorm epilogue, the shapes launch_kbn names): 8-byte stores, residual read the same way.
+//   A row's BN columns live in one wave, so the fused post-norm LayerNorm (encoder norm1) is two
+//   shuffle reductions (its per-lane partial sums fix which columns a lane owns: no ROWS).  The
+//   head-transposed V^T store uses MFMA(A, W): 4 consecutive tokens of one column per lane.
 // N > BN: the NS slices of W go to NS adjacent workgroups of the XCD-remapped grid (same XCD),
 // which walk the same row tiles in step, so A comes from HBM once and from L2 for the others.
+#include <cstdint>
 #include <cstdlib>
 #include <type_traits>
 
@@ -47,7 +54,7 @@ __device__ __attribute__((aligned(256))) uint32_t g_sg_sink[64];
 // 7x8 window: 8 adjacent 4-channel pixels of the zero-bordered input, contiguous.  So A row m
 // (output pixel b, oh, ow) is 8 pieces of 64 B at a stride of one input row; piece 7 (kh = 7,
 // zero weights) stays inside the bordered image.
-template <int K, int BN, int RF, int OCC, int NB, bool HAS_R, int EPI, bool CP = false>
+template <int K, int BN, int RF, int OCC, int NB, bool HAS_R, int EPI, bool CP = false, bool ROWS = false>
 __global__ __launch_bounds__(256, OCC) void sgemm_kernel(GemmArgs g, int ns_count, int row_tiles) {
   constexpr int KB = K * 2;                          // bytes of one W / A row
   constexpr int KF = K / 32, JF = BN / 16;           // K fragments, 16-column fragments
@@ -56,6 +63,9 @@ __global__ __launch_bounds__(256, OCC) void sgemm_kernel(GemmArgs g, int ns_coun
   constexpr int JGMAX = (OCC >= 2 || (HAS_R && EPI == EPI_LN)) ? 4 : 8;   // W fragments per LDS read group
   constexpr int NW = 4, NT = 256;                    // 4 waves; OCC workgroups per CU: 512/OCC registers per wave
   static_assert(!HAS_R || NB % 2 == 0, "residual buffers alternate with the A buffers");
+  static_assert(!ROWS || (EPI == EPI_ROW && JF % 2 == 0), "16-byte row pieces: fragment pairs of the plain epilogue");
+  constexpr int RV = ROWS ? JF / 2 : JF;             // residual pieces per row: 16 or 8 bytes each
+  using rvec_t = std::conditional_t<ROWS, u32x4, u32x2>;
   // EXACT: identical memory instructions on every path (see g_sg_sink).  The residual variants
   // skip instead: the always-live buffers would not fit their registers.
   constexpr bool EXACT = !HAS_R;
@@ -75,13 +85,17 @@ __global__ __launch_bounds__(256, OCC) void sgemm_kernel(GemmArgs g, int ns_coun
 
   // ---- W slice -> LDS.  Row n, 16-byte chunk c (of K/8) at n*KB + (c ^ (n & wkey_mask(KB)))*16.
   // One direct-to-LDS wave instruction fills 1 KB linearly; the swizzle is applied on the source.
+  // ROWS: LDS row n = 16j + 4q + i (fragment j, accumulator element i of the lanes fg = q) holds
+  // the slice's column 32(j/2) + 8q + 4(j%2) + i, so fragments 2p, 2p+1 give lane (fg, fr) the 8
+  // consecutive columns 32p + 8fg .. + 7 of row fr.  The key stays that of the LDS row.
   {
     constexpr int INS = BN * KB / 1024;
     for (int q = wid; q < INS; q += NW) {
       const int o = q * 1024 + lane * 16;
       const int n = o / KB, within = o - n * KB;
       const int chunk = (within >> 4) ^ (n & wkey_mask(KB));
-      const int nn = n0 + n < g.N ? n0 + n : g.N - 1;     // (N % BN == 0 on every launch)
+      const int col = ROWS ? ((n >> 5) << 5) + (((n >> 2) & 3) << 3) + (((n >> 4) & 1) << 2) + (n & 3) : n;
+      const int nn = n0 + col < g.N ? n0 + col : g.N - 1;   // (N % BN == 0 on every launch)
       const char* src = (const char*)g.B + (size_t)nn * g.ldb * 2 + chunk * 16;
       __builtin_amdgcn_global_load_lds((const void*)src, (lds_ptr_t)(wl + q * 1024), 16, 0, 0);
     }
@@ -125,7 +139,7 @@ __global__ __launch_bounds__(256, OCC) void sgemm_kernel(GemmArgs g, int ns_coun
       }
     }
   };
-  auto load_r = [&](int t, u32x2 (&r)[RF][JF]) {
+  auto load_r = [&](int t, rvec_t (&r)[RF][RV]) {
     if constexpr (HAS_R) {
       if (t >= row_tiles) return;
 #pragma unroll
@@ -133,14 +147,20 @@ __global__ __launch_bounds__(256, OCC) void sgemm_kernel(GemmArgs g, int ns_coun
         int m = row0(t) + 16 * rf + fr;
         m = m < g.M ? m : g.M - 1;
         const int rm = g.r_period > 0 ? m % g.r_period : m;
-        const char* p = (const char*)g.R + ((size_t)rm * g.ldr + n0 + 4 * fg) * 2;
+        if constexpr (ROWS) {
+          const char* p = (const char*)g.R + ((size_t)rm * g.ldr + n0 + 8 * fg) * 2;
 #pragma unroll
-        for (int j = 0; j < JF; ++j) r[rf][j] = ld8(p + j * 32);
+          for (int pr = 0; pr < RV; ++pr) r[rf][pr] = ld16(p + pr * 64);
+        } else {
+          const char* p = (const char*)g.R + ((size_t)rm * g.ldr + n0 + 4 * fg) * 2;
+#pragma unroll
+          for (int j = 0; j < JF; ++j) r[rf][j] = ld8(p + j * 32);
+        }
       }
     }
   };
 
-  auto tile = [&](int t, const u32x4 (&a)[RF][KF], const u32x2 (&r)[RF][JF]) {
+  auto tile = [&](int t, const u32x4 (&a)[RF][KF], const rvec_t (&r)[RF][RV]) {
     // (a compiler-only fence: W, bias and the LayerNorm affine are loop-invariant LDS reads, and
     // hoisting all of them out of the tile loop would pin hundreds of registers)
     asm volatile("" ::: "memory");
@@ -205,13 +225,23 @@ __global__ __launch_bounds__(256, OCC) void sgemm_kernel(GemmArgs g, int ns_coun
   #pragma unroll
           for (int j = 0; j < JF; ++j) {
             float rv[4] = {0.f, 0.f, 0.f, 0.f};
+            // columns of acc[rf][j][0..3] within the slice: cj .. cj + 3
+            const int cj = ROWS ? 32 * (j >> 1) + 8 * fg + 4 * (j & 1) : 16 * j + 4 * fg;
             if constexpr (HAS_R) {
-              rv[0] = __uint_as_float(r[rf][j].x << 16);
-              rv[1] = __uint_as_float(r[rf][j].x & 0xffff0000u);
-              rv[2] = __uint_as_float(r[rf][j].y << 16);
-              rv[3] = __uint_as_float(r[rf][j].y & 0xffff0000u);
+              uint32_t lo, hi;
+              if constexpr (ROWS) {
+                lo = j & 1 ? r[rf][j >> 1].z : r[rf][j >> 1].x;
+                hi = j & 1 ? r[rf][j >> 1].w : r[rf][j >> 1].y;
+              } else {
+                lo = r[rf][j].x;
+                hi = r[rf][j].y;
+              }
+              rv[0] = __uint_as_float(lo << 16);
+              rv[1] = __uint_as_float(lo & 0xffff0000u);
+              rv[2] = __uint_as_float(hi << 16);
+              rv[3] = __uint_as_float(hi & 0xffff0000u);
             }
-            const f32x4 bv = *reinterpret_cast<const f32x4*>(sb + 16 * j + 4 * fg);
+            const f32x4 bv = *reinterpret_cast<const f32x4*>(sb + cj);
   #pragma unroll
             for (int e = 0; e < 4; ++e) v[j][e] = acc[rf][j][e] + bv[e] + rv[e];
           }
@@ -248,11 +278,21 @@ __global__ __launch_bounds__(256, OCC) void sgemm_kernel(GemmArgs g, int ns_coun
           }
           const bool ok = m < g.M;
           if (!EXACT && !ok) continue;
-          char* cp = ok ? (char*)g.C + ((size_t)m * g.ldc + n0 + 4 * fg) * 2 : (char*)g_sg_sink;
-          const int cstep = ok ? 32 : 0;
+          if constexpr (ROWS) {
+            char* cp = ok ? (char*)g.C + ((size_t)m * g.ldc + n0 + 8 * fg) * 2 : (char*)g_sg_sink;
+            const int cstep = ok ? 64 : 0;
   #pragma unroll
-          for (int j = 0; j < JF; ++j)
-            st8(cp + j * cstep, u32x2{pack_out2(v[j][0], v[j][1], F16), pack_out2(v[j][2], v[j][3], F16)});
+            for (int p = 0; p < JF / 2; ++p)
+              st16(cp + p * cstep, u32x4{pack_out2(v[2 * p][0], v[2 * p][1], F16), pack_out2(v[2 * p][2], v[2 * p][3], F16),
+                                         pack_out2(v[2 * p + 1][0], v[2 * p + 1][1], F16),
+                                         pack_out2(v[2 * p + 1][2], v[2 * p + 1][3], F16)});
+          } else {
+            char* cp = ok ? (char*)g.C + ((size_t)m * g.ldc + n0 + 4 * fg) * 2 : (char*)g_sg_sink;
+            const int cstep = ok ? 32 : 0;
+  #pragma unroll
+            for (int j = 0; j < JF; ++j)
+              st8(cp + j * cstep, u32x2{pack_out2(v[j][0], v[j][1], F16), pack_out2(v[j][2], v[j][3], F16)});
+          }
         }
       }
     };
@@ -268,7 +308,7 @@ __global__ __launch_bounds__(256, OCC) void sgemm_kernel(GemmArgs g, int ns_coun
   // NB A register sets in rotation: tiles i+1 .. i+NB-1 are in flight while tile i is
   // multiplied and stored; the residual of tile i+1 is requested as tile i starts (two sets).
   u32x4 ab[NB][RF][KF];
-  u32x2 rb[HAS_R ? 2 : 1][RF][JF];
+  rvec_t rb[HAS_R ? 2 : 1][RF][RV];
   const int rt0 = rt;
   if (rt0 >= row_tiles) return;
 #pragma unroll
@@ -311,12 +351,22 @@ bool sgemm_enabled() {
   return on;
 }
 
-template <int K, int BN, int RF, int OCC, int NB, bool HAS_R, int EPI, bool CP = false>
+// 16-byte row pieces (sgemm_kernel ROWS): row strides and bases that are 16-byte multiples (the
+// column offset n0 + 32p + 8fg is one by construction); SPE_SGEMM_ROWS=0 keeps the 8-byte pieces
+bool sgemm_rows_ok(const GemmArgs& g) {
+  static const bool on = spe_env_int("SPE_SGEMM_ROWS", 1) != 0;
+  return on && g.ldc % 8 == 0 && (uintptr_t)g.C % 16 == 0 && (!g.R || (g.ldr % 8 == 0 && (uintptr_t)g.R % 16 == 0));
+}
+
+template <int K, int BN, int RF, int OCC, int NB, bool HAS_R, int EPI, bool CP = false, bool ROWS = false>
 int launch_k(const GemmArgs& g, hipStream_t s) {
+  if constexpr (ROWS) {
+    if (!sgemm_rows_ok(g)) return launch_k<K, BN, RF, OCC, NB, HAS_R, EPI, CP, false>(g, s);
+  }
   const int row_tiles = (g.M + RF * 16 - 1) / (RF * 16), nsc = g.N / BN;
   const int G = (spe_cu_count() * OCC / nsc) * nsc;
   if ((long)row_tiles < 2L * (G / nsc) * 4) return 1;    // fewer than two tiles per wave
-  hipLaunchKernelGGL((sgemm_kernel<K, BN, RF, OCC, NB, HAS_R, EPI, CP>), dim3(G), dim3(256), 0, s, g, nsc, row_tiles);
+  hipLaunchKernelGGL((sgemm_kernel<K, BN, RF, OCC, NB, HAS_R, EPI, CP, ROWS>), dim3(G), dim3(256), 0, s, g, nsc, row_tiles);
   spe_gemm_last_path = 2;
   return (int)hipGetLastError();
 }
@@ -324,7 +374,13 @@ int launch_k(const GemmArgs& g, hipStream_t s) {
 // Per (K, BN): row fragments per wave tile RF, workgroups per CU OCC (LDS: BN*K*2 bytes each;
 // registers: 512/OCC per wave), A register sets NB -- for the plain (0) and the residual (1)
 // epilogues.  Registers per wave ~ RF*BN/4 accumulators + NB*RF*K/4 A + 2*JG*4 W + RF*BN/4 R.
-template <int K, int BN, int RF0, int OCC0, int NB0, int RF1, int OCC1, int NB1>
+// ROWS0 / ROWS1: the plain / the residual epilogue moves 16-byte row pieces where the launch qualifies.
+// Measured at B = 64 (profiles/sgemm_rows_ab_ms_per_step.json), ms per launch, 8-byte -> 16-byte pieces, parent's
+// spread in brackets: <256, 256> + residual, the encoder q/k 0.099 -> 0.078 (0.002) and the 1x1 ahead of the neck
+// 0.056 -> 0.046 (0.003); <512, 128> plain (s8_latern) 0.083 -> 0.073 (0.001); <64, 64> plain (layer-1 entry)
+// 0.039 -> 0.033 (0.002).  Every (K, BN, residual) the bf16 step launches cleared its rule and no BN lost, so the
+// shapes it does not launch take the 16-byte form too.
+template <int K, int BN, int RF0, int OCC0, int NB0, int RF1, int OCC1, int NB1, bool ROWS0 = true, bool ROWS1 = true>
 int launch_kbn(const GemmArgs& g, hipStream_t s) {
   if (g.N % BN) return 1;
   if (g.vt_T > 0) return g.R ? 1 : launch_k<K, BN, RF0, OCC0, NB0, false, EPI_VT>(g, s);
@@ -333,7 +389,8 @@ int launch_kbn(const GemmArgs& g, hipStream_t s) {
       return g.R ? launch_k<K, BN, 1, 1, 2, true, EPI_LN>(g, s) : 1;
     return 1;
   }
-  return g.R ? launch_k<K, BN, RF1, OCC1, NB1, true, EPI_ROW>(g, s) : launch_k<K, BN, RF0, OCC0, NB0, false, EPI_ROW>(g, s);
+  return g.R ? launch_k<K, BN, RF1, OCC1, NB1, true, EPI_ROW, false, ROWS1>(g, s)
+             : launch_k<K, BN, RF0, OCC0, NB0, false, EPI_ROW, false, ROWS0>(g, s);
 }
 
 }  // namespace
@@ -346,7 +403,8 @@ int spe_launch_sgemm(const GemmArgs& g, int mode, hipStream_t s) {
     if (on && g.Cin == 4 && g.KH == 7 && g.KW == 8 && g.pad == 0 && g.K == 224 && g.ldb == 256 && g.N == 64 &&
         !g.R && !g.ln_g && g.vt_T == 0 && g.act <= ACT_RELU && !g.res_post && !g.out_f32 && g.ldc % 4 == 0 &&
         (g.Ho - 1) * g.stride + 8 <= g.H && (g.Wo - 1) * g.stride + 8 <= g.W)
-      return launch_k<256, 64, 1, 2, 4, false, EPI_ROW, true>(g, s);
+      // 8-byte pieces: not measured (the bf16 step's stem runs fused with the max-pool, stempool.hip)
+      return launch_k<256, 64, 1, 2, 4, false, EPI_ROW, true, false>(g, s);
     return 1;
   }
   if (!sgemm_enabled() || mode != GEMM_LINEAR || g.M <= 0) return 1;
