@@ -415,6 +415,51 @@ int spe_criterion_sigma(void* stream, const float* logits, const float* points, 
 int spe_ensemble_fuse(void* stream, const float* points_px, const float* probs, int models, int batch,
                       int num_queries, int num_classes, float* fused_points, float* fused_probs);
 
+/* Sigma-weighted multi-checkpoint ensemble: fuses M sigma models' PostProcess outputs per image into one
+ * keypoint set WITH a sigma, so that an ensemble can feed the sigma-weighted solvers, spe_self_assess and
+ * spe_pose_covariance.  No reference code exists (UNC/utils/speed_eval_ceres.py:405-462 is the unweighted
+ * mean of spe_ensemble_fuse); this comment is the definition (parity unpinned).  All pointers are device
+ * memory: points_px [M,B,Q,2], probs [M,B,Q,C], sigmas [M,B,Q,2] fp32 (sigmas in the model's unit);
+ * sigma_scale [B,2] (nullable: scale 1) is the number of pixels per sigma unit and axis, the crop's width
+ * and height as spe_pose_covariance takes it.  K = C - 1 landmarks.
+ *
+ * Measurements.  A query's label is the argmax of its probability row (the lower class on ties) and its
+ * score that maximum; background (label K) is dropped.  Per model and label the measurement is the
+ * label's highest-score query (the earlier query on ties): spe_pnp_batch's selection, so a model gives at
+ * most one measurement per label and the measurements of a label are independent (unlike the REV rule,
+ * which pools every foreground query).  With x, y the query's point and u = sigma * scale per axis (the
+ * product taken in fp64), the measurement is usable when the image's two scales are finite and positive
+ * and x, y, ux, uy and the score are all finite; its effective sigma is s = max(u, sigma_floor) per axis.
+ * n_pooled counts a label's measurements, usable or not.  A label without a usable one is not emitted.
+ *
+ * Fusion, per emitted label, in fp64, every sum taken one term after the other in ascending model order
+ * and without contraction.  Over the kept measurements (at first the usable ones), per axis:
+ *     w_i = 1 / (s_i * s_i),   mu = (sum w_i * x_i) / (sum w_i)
+ * Gate: while 3 or more are kept, d_i^2 = dx * dx + dy * dy with dx = (x_i - mu_x) / s_ix and dy alike;
+ * if sqrt of the largest d_i^2 (the lowest model on ties) exceeds `gate`, that measurement is dropped, mu
+ * is recomputed over the rest and the test repeats.  Two measurements are never gated.  n_kept counts
+ * what is left.  Fused sigma per axis:
+ *     sqrt(1 / sum w_i) * f / scale,   f = max(1, sqrt(chi2 / (n_kept - 1))),   chi2 = sum w_i * (e_i * e_i),
+ * e_i = x_i - mu; f = 1 when n_kept = 1.  f is the Birge ratio: scatter beyond what the sigmas predict
+ * widens the result.  The division by the scale returns the sigma in the input's unit, so downstream
+ * calls pass clip_bbox exactly as for one model.  Fused score = (sum score_i) / n_kept.
+ *
+ * Outputs.  Row r of an image is its r-th emitted label in first-seen order (spe_ensemble_fuse's order:
+ * model-major, then by query, over all foreground queries of the emitted labels), the layout
+ * spe_pnp_batch, spe_self_assess and spe_pose_covariance read.  fused_points [B,K,2]; fused_probs
+ * [B,K,C]: the fused score in the label's column and 0 elsewhere (the row need not sum to 1; its argmax
+ * is the label for a positive score); fused_sigmas [B,K,2]; n_pooled, n_kept [B,K].  Each fp32 output is
+ * the fp64 value rounded once.  The rows after the last emitted label are unused: probability 1 at
+ * background and 0 in every other output.  No NaN leaves the kernel.
+ *
+ * 1 <= M <= 16, M * Q <= 256, 2 <= C <= 17, B >= 1, every pointer but sigma_scale non-NULL, gate > 0,
+ * sigma_floor positive and finite, else SPE_E_ARG before any launch with the outputs untouched.  One
+ * launch; no allocation, no scratch, no synchronisation. */
+int spe_ensemble_fuse_sigma(void* stream, const float* points_px, const float* probs, const float* sigmas,
+                            const float* sigma_scale, int models, int batch, int num_queries, int num_classes,
+                            float sigma_floor, float gate, float* fused_points, float* fused_probs,
+                            float* fused_sigmas, int32_t* n_pooled, int32_t* n_kept);
+
 /* PostProcess alone (REV/models/detr_speed.py:266-293). */
 int spe_postprocess(void* stream, const float* logits, const float* points, const float* clip_bbox, int batch,
                     int num_queries, float* probs, float* points_px);

@@ -93,6 +93,22 @@ int spe_ensemble_fuse(void* stream, const float* points_px, const float* probs, 
   return 0;
 }
 
+int spe_ensemble_fuse_sigma(void* stream, const float* points_px, const float* probs, const float* sigmas,
+                            const float* sigma_scale, int models, int batch, int num_queries, int num_classes,
+                            float sigma_floor, float gate, float* fused_points, float* fused_probs,
+                            float* fused_sigmas, int32_t* n_pooled, int32_t* n_kept) {
+  if (!points_px || !probs || !sigmas || !fused_points || !fused_probs || !fused_sigmas || !n_pooled || !n_kept ||
+      models < 1 || models > 16 || batch < 1 || num_queries < 1 || num_classes < 2 || num_classes > 17 ||
+      (int64_t)models * num_queries > 256)
+    return fail(SPE_E_ARG, "bad argument");
+  if (!(gate > 0)) return fail(SPE_E_ARG, "gate must be positive");
+  if (!(sigma_floor > 0) || !(sigma_floor < INFINITY)) return fail(SPE_E_ARG, "sigma_floor must be positive and finite");
+  EnsembleSigmaArgs a{points_px, probs, sigmas, sigma_scale, models, batch, num_queries, num_classes, sigma_floor,
+                      gate, fused_points, fused_probs, fused_sigmas, n_pooled, n_kept};
+  CK(spe_launch_ensemble_fuse_sigma(a, (hipStream_t)stream));
+  return 0;
+}
+
 int spe_preprocess(void* stream, const uint8_t* frames, int batch, int height, int width, int channels,
                    const double* bbox_xxyy, int size, float* images, float* clip_bbox, int32_t* status) {
   if (!frames || !bbox_xxyy || !images || !clip_bbox || batch < 0 || height <= 0 || width <= 0 || size <= 0 ||

@@ -412,6 +412,22 @@ struct EnsembleArgs {
   float* fused_probs;              // [B][C-1][C] one-hot rows (background padding)
 };
 int spe_launch_ensemble_fuse(const EnsembleArgs& a, hipStream_t s);
+// The sigma-weighted fusion (include/spe.h spe_ensemble_fuse_sigma): one measurement per model and
+// label, gated inverse-variance mean, fused sigma; the same output layout plus sigmas and counts.
+struct EnsembleSigmaArgs {
+  const float* points;             // [M][B][Q][2] image px
+  const float* probs;              // [M][B][Q][C]
+  const float* sigmas;             // [M][B][Q][2] in the model's unit
+  const float* sigma_scale;        // [B][2] px per sigma unit, or nullptr (1)
+  int M, B, Q, C;
+  float sigma_floor, gate;
+  float* fused_points;             // [B][C-1][2]
+  float* fused_probs;              // [B][C-1][C] fused score in the label's column (background padding)
+  float* fused_sigmas;             // [B][C-1][2] in the input's unit
+  int32_t* n_pooled;               // [B][C-1]
+  int32_t* n_kept;                 // [B][C-1]
+};
+int spe_launch_ensemble_fuse_sigma(const EnsembleSigmaArgs& a, hipStream_t s);
 int spe_launch_postprocess(const float* logits, const float* points, const float* clip_bbox, int B, int Q,
                            float* probs, float* points_px, hipStream_t s);
 

@@ -201,22 +201,30 @@ def generate_submission(models, postprocessors, anns, read_file, solver, device,
 
     A single spe.rtdetr.RTDETR works the same way (UNC's SpeedSubmission, src/data/speed/speed_dataset.py:
     59-168, is this pad-to-square crop): its u8 stems take the crops, its sigmas go to the solver -- a sigma
-    solver such as SimplePoseSolverSigma (epnp_ransac_sigma).  Not supported here: a list of RTDETR models
-    (the reference has no sigma fusion rule), and EPnPCeresSolver, whose per-image thresholds the reference
-    derives from the ground-truth box areas a submission set does not have (ValueError).
+    solver such as SimplePoseSolverSigma (epnp_ransac_sigma).  A list of RTDETR models takes a
+    SigmaEnsemblePoseSolver: every model's sigmas and the batch's clip_bbox go to its solve_batch_multi, which
+    fuses them into one keypoint set with a sigma (the reference has no sigma fusion rule; include/spe.h
+    spe_ensemble_fuse_sigma defines one) and solves it with its backend; a model without sigmas is a
+    ValueError.  Any other ensemble solver is called as solve_batch_multi(points, probs).  Not supported
+    here: EPnPCeresSolver, also as an ensemble's backend, whose per-image thresholds the reference derives
+    from the ground-truth box areas a submission set does not have (ValueError).
 
-    pose_cov (a single model with a sigma head): each record also carries "pred_score" and "cov_status"
+    pose_cov (a single model with a sigma head, or a list with a SigmaEnsemblePoseSolver, whose fused probs
+    and sigmas it then reads): each record also carries "pred_score" and "cov_status"
     (PoseSolver.pose_covariance on the crop-scaled sigmas); a status-1 crop's are 0 and 1, like its pose."""
     from .datasets import JpegDecoder, SpeedSubmissionTransform
+    from .solver import SigmaEnsemblePoseSolver
     multi = isinstance(models, (list, tuple))
     if multi and not hasattr(solver, "solve_batch_multi"):
-        raise ValueError("a list of models needs an ensemble solver (Multi_Mean_PoseSolver)")
+        raise ValueError("a list of models needs an ensemble solver (Multi_Mean_PoseSolver, SigmaEnsemblePoseSolver)")
     if getattr(solver, "mode", None) == _lib.SPE_PNP_EPNP_CERES:
         raise ValueError("generate_submission: EPnPCeresSolver takes one threshold per image from the ground-truth "
                          "box areas (UNC speed_dataset.py:366-399), which a submission set lacks; use a solver "
                          "without them (epnp_ransac_sigma)")
-    if pose_cov and multi:
-        raise ValueError("generate_submission: pose_cov needs a single model's sigmas (no fusion rule for sigmas)")
+    sigma_multi = multi and isinstance(solver, SigmaEnsemblePoseSolver)
+    if pose_cov and multi and not sigma_multi:
+        raise ValueError("generate_submission: pose_cov needs a single model's sigmas (no fusion rule for sigmas) "
+                         "or a SigmaEnsemblePoseSolver")
     decoder = decoder if decoder is not None else JpegDecoder()
     transform = transform if transform is not None else SpeedSubmissionTransform(input_size)
     names = list(anns)
@@ -228,7 +236,15 @@ def generate_submission(models, postprocessors, anns, read_file, solver, device,
         t = transform(frames, bbox, crops=True, images=False)
         if multi:
             outs = [m(t["crops"], clip_bbox=t["clip_bbox"]) for m in models]
-            poses = solver.solve_batch_multi([o["points_px"] for o in outs], [o["probs"] for o in outs])
+            if sigma_multi:
+                if any(o.get("sigmas") is None for o in outs):
+                    raise ValueError("generate_submission: SigmaEnsemblePoseSolver needs models with a sigma head")
+                poses = solver.solve_batch_multi([o["points_px"] for o in outs], [o["probs"] for o in outs],
+                                                 [o["sigmas"] for o in outs], clip_bbox=t["clip_bbox"])
+                # what pose_cov reads below: the fused keypoint set in one model's layout
+                o = {"probs": poses["fused"]["probs"], "sigmas": poses["fused"]["sigmas"]}
+            else:
+                poses = solver.solve_batch_multi([o["points_px"] for o in outs], [o["probs"] for o in outs])
         else:
             o = models(t["crops"], clip_bbox=t["clip_bbox"])
             poses = solver.solve_batch(o["points_px"], o["probs"], o.get("sigmas"))

@@ -306,9 +306,99 @@ class Multi_Mean_PoseSolver(PoseSolver):
         return PoseSolver.__call__(self, fp[0].cpu().numpy(), fr[0].cpu().numpy(), device=dev)
 
 
+class SigmaEnsemblePoseSolver:
+    """Multi-checkpoint ensemble of sigma models: per label one measurement per model, fused by a gated
+    inverse-variance mean into a point with a sigma (spe_ensemble_fuse_sigma; the rule, which has no
+    reference counterpart, is defined in include/spe.h), then solved by `backend` -- any solver object of
+    this module, SimplePoseSolverSigma by default -- with the fused sigma.  The fused arrays have
+    solve_batch's layout, so the backend's self_assess and pose_covariance take them as they take one
+    model's."""
+
+    def __init__(self, backend=None, gate=3.0, sigma_floor=1e-3):
+        self.backend = backend if backend is not None else SimplePoseSolverSigma()
+        if not hasattr(self.backend, "solve_batch"):
+            raise ValueError("SigmaEnsemblePoseSolver: the backend must be a solver object (solve_batch)")
+        self.gate = float(gate)
+        self.sigma_floor = float(sigma_floor)
+        if not self.gate > 0:
+            raise ValueError(f"gate must be positive, got {gate}")
+        if not 0 < self.sigma_floor < float("inf"):
+            raise ValueError(f"sigma_floor must be positive and finite, got {sigma_floor}")
+
+    @property
+    def mode(self):
+        return self.backend.mode
+
+    def fuse_batch(self, multi_points_px, multi_probs, multi_sigmas, clip_bbox=None, stream=None):
+        """lists of M device tensors [B,Q,2] / [B,Q,C] / [B,Q,2] -> dict of device tensors points
+        [B,C-1,2], probs [B,C-1,C], sigmas [B,C-1,2] f32, n_pooled, n_kept [B,C-1] i32.  clip_bbox [B,4]
+        (x1, y1, x2, y2): the sigmas are crop-normalised and weigh in pixels, by the crop's width and
+        height; the fused sigma is crop-normalised again.  None: they are in the points' unit."""
+        if multi_sigmas is None:
+            raise ValueError("SigmaEnsemblePoseSolver needs every model's sigmas (multi_sigmas)")
+        with torch.cuda.stream(stream if stream is not None else torch.cuda.current_stream()):
+            pts = torch.stack(list(multi_points_px)).float().contiguous()
+            prb = torch.stack(list(multi_probs)).float().contiguous()
+            sig = torch.stack(list(multi_sigmas)).float().contiguous()
+            M, B, Q, C = prb.shape
+            dev = prb.device
+            scale = None
+            if clip_bbox is not None:
+                cb = clip_bbox.to(device=dev, dtype=torch.float32)
+                scale = torch.stack((cb[:, 2] - cb[:, 0], cb[:, 3] - cb[:, 1]), 1).contiguous()
+        if pts.shape != (M, B, Q, 2) or sig.shape != (M, B, Q, 2):
+            raise ValueError(f"points {tuple(pts.shape)} / sigmas {tuple(sig.shape)} do not match probs {tuple(prb.shape)}")
+        out = dict(points=torch.empty(B, C - 1, 2, device=dev), probs=torch.empty(B, C - 1, C, device=dev),
+                   sigmas=torch.empty(B, C - 1, 2, device=dev),
+                   n_pooled=torch.empty(B, C - 1, dtype=torch.int32, device=dev),
+                   n_kept=torch.empty(B, C - 1, dtype=torch.int32, device=dev))
+        if B == 0:
+            return out
+        _lib.check(_lib.lib().spe_ensemble_fuse_sigma(
+            _lib.stream_ptr(stream), _lib.ptr(pts), _lib.ptr(prb), _lib.ptr(sig), _lib.ptr(scale), M, B, Q, C,
+            self.sigma_floor, self.gate, _lib.ptr(out["points"]), _lib.ptr(out["probs"]), _lib.ptr(out["sigmas"]),
+            _lib.ptr(out["n_pooled"]), _lib.ptr(out["n_kept"])), "spe_ensemble_fuse_sigma")
+        if stream is not None:
+            # the kernel may still read its inputs on `stream` after this returns
+            for t in (pts, prb, sig) + ((scale,) if scale is not None else ()):
+                t.record_stream(stream)
+        return out
+
+    def solve_batch_multi(self, multi_points_px, multi_probs, multi_sigmas=None, clip_bbox=None, area=None,
+                          repro_per_image=None, stream=None):
+        """Fuses, then the backend's solve_batch on the fused arrays with the fused sigma.  area /
+        repro_per_image go to the solvers that take them (EPnPCeresSolver, ExhaustivePoseSolver).  Returns
+        the backend's pose dict plus "fused", fuse_batch's dict."""
+        fused = self.fuse_batch(multi_points_px, multi_probs, multi_sigmas, clip_bbox=clip_bbox, stream=stream)
+        kw = {}
+        if area is not None:
+            kw["area"] = area
+        if repro_per_image is not None:
+            kw["repro_per_image"] = repro_per_image
+        poses = self.backend.solve_batch(fused["points"], fused["probs"], fused["sigmas"], stream=stream, **kw)
+        poses["fused"] = fused
+        return poses
+
+    def self_assess(self, probs, sigmas, poses, **kw):
+        return self.backend.self_assess(probs, sigmas, poses, **kw)
+
+    def pose_covariance(self, probs, sigmas, poses, **kw):
+        return self.backend.pose_covariance(probs, sigmas, poses, **kw)
+
+
 def build_solver(args=None):
-    """REV/utils/speed_eval.py:21-22 (SimplePoseSolver); `args.solver` selects the variant."""
+    """REV/utils/speed_eval.py:21-22 (SimplePoseSolver); `args.solver` selects the variant.
+    "ensemble_sigma" wraps the solver `args.backend` names (epnp_ransac_sigma by default) in a
+    SigmaEnsemblePoseSolver with `args.gate` / `args.sigma_floor`."""
     name = getattr(args, "solver", "ransac_p3p_lm") if args is not None else "ransac_p3p_lm"
+    if name == "ensemble_sigma":
+        import argparse
+        backend = getattr(args, "backend", "epnp_ransac_sigma")
+        if backend == "ensemble_sigma":
+            raise ValueError("ensemble_sigma cannot be its own backend")
+        inner = argparse.Namespace(**{**vars(args), "solver": backend})
+        return SigmaEnsemblePoseSolver(build_solver(inner), getattr(args, "gate", 3.0),
+                                       getattr(args, "sigma_floor", 1e-3))
     if name == "ransac_p3p_lm":
         return SimplePoseSolver(args)
     if name == "epnp_ransac_sigma":
