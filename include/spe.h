@@ -460,6 +460,64 @@ int spe_ensemble_fuse_sigma(void* stream, const float* points_px, const float* p
                             float sigma_floor, float gate, float* fused_points, float* fused_probs,
                             float* fused_sigmas, int32_t* n_pooled, int32_t* n_kept);
 
+/* Lens distortion in front of the solvers.  The reference hands Camera.dist to cv2.solvePnPRansac,
+ * cv2.solvePnPGeneric and cv2.undistortPoints (UNC/utils/speed_eval.py, speed_eval_ceres.py,
+ * val_p_which_p.py); the solver entries above take K alone.  spe_undistort_points turns distorted pixel
+ * points into ideal pixel points K . undistort(K^-1 p) and maps the per-axis sigma alongside, so every
+ * solver entry, spe_self_assess, spe_pose_covariance and the ensemble fusions then run unchanged on a
+ * pinhole problem.  All pointers are device memory; points and sigmas [B,Q,2] fp32, 8-byte aligned;
+ * K 3x3 row-major fp64 (fx = K[0], fy = K[4], cx = K[2], cy = K[5]); dist = (k1, k2, p1, p2, k3) fp64,
+ * OpenCV's five-coefficient model.  Everything is computed in fp64, each step rounded on its own.
+ *
+ * Distort, of an ideal normalised point x, y with r2 = x * x + y * y:
+ *     rad = 1 + ((k3 * r2 + k2) * r2 + k1) * r2
+ *     xd  = x * rad + 2 * p1 * x * y + p2 * (r2 + 2 * x * x)
+ *     yd  = y * rad + p1 * (r2 + 2 * y * y) + 2 * p2 * x * y
+ *     ud  = fx * xd + cx,  vd = fy * yd + cy
+ * Undistort: cv2.undistortPoints' fixed-point iteration, run for exactly `iters` rounds with no early
+ * exit on a tolerance (5 = cv2's TermCriteria(MAX_ITER, 5, ...)).  x0 = (u - cx) / fx, y0 = (v - cy) / fy,
+ * x, y start at x0, y0, and each round computes
+ *     icd = 1 / rad(x, y),  dx = 2 * p1 * x * y + p2 * (r2 + 2 * x * x),  dy = p1 * (r2 + 2 * y * y) + 2 * p2 * x * y
+ *     x = (x0 - dx) * icd,  y = (y0 - dy) * icd
+ * The ideal point is (fx * x + cx, fy * y + cy), rounded once to fp32.
+ *
+ * Sigma.  sigmas is in the caller's unit and sigma_scale [B,2] (nullable: 1) the pixels per unit and
+ * axis, as spe_pose_covariance takes them.  D = d(ud, vd) / d(ui, vi) is the distort map's Jacobian in
+ * pixels, in closed form at the undistorted point (g = d rad / d r2 = (3 * k3 * r2 + 2 * k2) * r2 + k1,
+ * c = 2 * x * y * g + 2 * p1 * x + 2 * p2 * y):
+ *     D11 = rad + 2 * x * x * g + 2 * p1 * y + 6 * p2 * x      D12 = c * (fx / fy)
+ *     D21 = c * (fy / fx)                                      D22 = rad + 2 * y * y * g + 6 * p1 * y + 2 * p2 * x
+ * and A = D^-1.  With ux = sigma_x * sx, uy = sigma_y * sy:
+ *     sigma_x' = sqrt(A11^2 * ux^2 + A12^2 * uy^2) / sx,   sigma_y' = sqrt(A21^2 * ux^2 + A22^2 * uy^2) / sy
+ * The cross term of A Sigma A^T is dropped: the solvers and the covariance take one sigma per axis.  A
+ * scale that is not positive and finite gives a sigma that is not finite, which spe_pose_covariance
+ * reports as its status 3.
+ *
+ * status [B,Q] (nullable): 0, or 1 where icd is not positive and finite in some round (cv2's icdist < 0
+ * bail-out) or |det D| is not positive and finite; such a point and its sigma are returned as they came.
+ * When all five coefficients are exactly zero the points and sigmas are copied bit for bit.  sigmas,
+ * sigma_scale, sigmas_ideal and status are nullable; sigmas_ideal without sigmas, batch < 1,
+ * num_queries < 1, batch * num_queries > 2^30, iters outside [1, 64] or a misaligned array is SPE_E_ARG
+ * before any launch.  points_ideal may be points_px and sigmas_ideal may be sigmas (in place).  One launch,
+ * one thread per point; no allocation, no scratch, no synchronisation.
+ *
+ * PARITY UNPINNED: cv2 is absent here; tests/lens_ref.py restates this comment in numpy.  One place
+ * differs from cv2 by design.  cv2 undistorts before it minimises (EPnP, P3P, the ITERATIVE LM, the
+ * reference's ceres_pnp all work on undistortPoints' output), so the minimisers see what they see here.
+ * But cv2's RANSAC inlier test (projectPoints with distCoeffs against the observed points) and the
+ * reference's epnp_init error measure distance in the distorted image, and the solvers here measure it
+ * between ideal points.  The two differ by the local stretch of the lens: max |D - I| = 0.043 over a
+ * 1920 x 1200 frame (0.047 with a 200 px margin) for k1 = -0.224, k2 = 0.514, p1 = -6.6e-4, p2 = -2.1e-4,
+ * k3 = -0.131 at the SPEED K, so only a residual within about 4 % of the threshold is classified
+ * differently. */
+int spe_undistort_points(void* stream, const float* points_px, const float* sigmas, const float* sigma_scale,
+                         int batch, int num_queries, const double* K, const double* dist, int iters,
+                         float* points_ideal, float* sigmas_ideal, uint8_t* status);
+/* The distort map above on ideal pixel points [B,Q,2] -> distorted pixel points (fp32, rounded once);
+ * points_px may be points_ideal.  The same argument checks. */
+int spe_distort_points(void* stream, const float* points_ideal, int batch, int num_queries, const double* K,
+                       const double* dist, float* points_px);
+
 /* PostProcess alone (REV/models/detr_speed.py:266-293). */
 int spe_postprocess(void* stream, const float* logits, const float* points, const float* clip_bbox, int batch,
                     int num_queries, float* probs, float* points_px);

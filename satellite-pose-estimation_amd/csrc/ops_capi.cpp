@@ -109,6 +109,37 @@ int spe_ensemble_fuse_sigma(void* stream, const float* points_px, const float* p
   return 0;
 }
 
+// the lens kernels move points and sigmas as float2
+static bool aligned8(const void* p) { return ((uintptr_t)p & 7) == 0; }
+
+int spe_undistort_points(void* stream, const float* points_px, const float* sigmas, const float* sigma_scale,
+                         int batch, int num_queries, const double* K, const double* dist, int iters,
+                         float* points_ideal, float* sigmas_ideal, uint8_t* status) {
+  if (!points_px || !K || !dist || !points_ideal || batch < 1 || num_queries < 1 ||
+      (int64_t)batch * num_queries > ((int64_t)1 << 30))
+    return fail(SPE_E_ARG, "bad argument");
+  if (iters < 1 || iters > 64) return fail(SPE_E_ARG, "iters must be in [1, 64]");
+  if (sigmas_ideal && !sigmas) return fail(SPE_E_ARG, "sigmas_ideal needs sigmas");
+  if (!aligned8(points_px) || !aligned8(sigmas) || !aligned8(points_ideal) || !aligned8(sigmas_ideal))
+    return fail(SPE_E_ARG, "points and sigmas must be 8-byte aligned");
+  LensArgs a{points_px, sigmas, sigma_scale, (size_t)batch * num_queries, num_queries, K, dist, iters,
+             points_ideal, sigmas_ideal, status};
+  CK(spe_launch_undistort_points(a, (hipStream_t)stream));
+  return 0;
+}
+
+int spe_distort_points(void* stream, const float* points_ideal, int batch, int num_queries, const double* K,
+                       const double* dist, float* points_px) {
+  if (!points_ideal || !K || !dist || !points_px || batch < 1 || num_queries < 1 ||
+      (int64_t)batch * num_queries > ((int64_t)1 << 30))
+    return fail(SPE_E_ARG, "bad argument");
+  if (!aligned8(points_ideal) || !aligned8(points_px)) return fail(SPE_E_ARG, "points must be 8-byte aligned");
+  LensArgs a{points_ideal, nullptr, nullptr, (size_t)batch * num_queries, num_queries, K, dist, 1, points_px,
+             nullptr, nullptr};
+  CK(spe_launch_distort_points(a, (hipStream_t)stream));
+  return 0;
+}
+
 int spe_preprocess(void* stream, const uint8_t* frames, int batch, int height, int width, int channels,
                    const double* bbox_xxyy, int size, float* images, float* clip_bbox, int32_t* status) {
   if (!frames || !bbox_xxyy || !images || !clip_bbox || batch < 0 || height <= 0 || width <= 0 || size <= 0 ||

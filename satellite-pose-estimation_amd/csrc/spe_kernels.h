@@ -428,6 +428,23 @@ struct EnsembleSigmaArgs {
   int32_t* n_kept;                 // [B][C-1]
 };
 int spe_launch_ensemble_fuse_sigma(const EnsembleSigmaArgs& a, hipStream_t s);
+// Lens distortion in front of the solvers (lens.hip; include/spe.h spe_undistort_points /
+// spe_distort_points): one thread per point, n = B * Q points, every array 8-byte aligned.
+struct LensArgs {
+  const float* points;             // [n][2] px (undistort: distorted, distort: ideal)
+  const float* sigmas;             // [n][2] in the caller's unit, or nullptr
+  const float* sigma_scale;        // [B][2] px per sigma unit, or nullptr (1)
+  size_t n;
+  int Q;
+  const double* K;                 // 3x3 row-major
+  const double* dist;              // k1, k2, p1, p2, k3
+  int iters;
+  float* points_out;               // [n][2] px; may be `points`
+  float* sigmas_out;               // [n][2] or nullptr; may be `sigmas`
+  uint8_t* status;                 // [n] or nullptr
+};
+int spe_launch_undistort_points(const LensArgs& a, hipStream_t s);
+int spe_launch_distort_points(const LensArgs& a, hipStream_t s);
 int spe_launch_postprocess(const float* logits, const float* points, const float* clip_bbox, int B, int Q,
                            float* probs, float* points_px, hipStream_t s);
 

@@ -99,6 +99,40 @@ class Camera:
     dist = np.zeros(5)
 
 
+@dataclass(frozen=True, eq=False)
+class LensModel:
+    """A camera with lens distortion: K and OpenCV's coefficients dist = (k1, k2, p1, p2, k3), what the
+    reference hands to cv2 as Camera.K / Camera.dist (UNC/utils/speed_eval_ceres.py).  Four coefficients
+    are (k1, k2, p1, p2) with k3 = 0.  iters: the rounds of the fixed-point undistortion
+    (include/spe.h spe_undistort_points; 5 is cv2.undistortPoints' default criterion).  A solver built
+    with lens= undistorts its keypoints and their sigmas on the device before it solves (spe.solver)."""
+    K: np.ndarray = None
+    dist: np.ndarray = None
+    iters: int = 5
+
+    def __post_init__(self):
+        K = np.array(Camera.K if self.K is None else self.K, dtype=np.float64)
+        d = np.zeros(5) if self.dist is None else np.array(self.dist, dtype=np.float64).ravel()
+        if K.shape != (3, 3):
+            raise ValueError(f"K must be 3x3, got {K.shape}")
+        if d.size not in (4, 5):
+            raise ValueError(f"dist takes 4 (k1, k2, p1, p2) or 5 (+ k3) coefficients, got {d.size}")
+        if not 1 <= int(self.iters) <= 64:
+            raise ValueError(f"iters must be in [1, 64], got {self.iters}")
+        d = np.concatenate([d, np.zeros(5 - d.size)])
+        K.setflags(write=False)
+        d.setflags(write=False)
+        object.__setattr__(self, "K", K)
+        object.__setattr__(self, "dist", d)
+        object.__setattr__(self, "iters", int(self.iters))
+
+    @classmethod
+    def from_args(cls, args) -> "LensModel":
+        """From a reference-style argparse.Namespace: args.dist (4 or 5 coefficients) when present,
+        zero distortion otherwise."""
+        return cls(dist=getattr(args, "dist", None))
+
+
 def world_points() -> np.ndarray:
     """The 11 satellite landmarks (REV/all_result.json 'pt', REV/utils/speed_eval.py:33-39)."""
     with open(os.path.join(_DATA, "world_points.json")) as f:
@@ -116,10 +150,20 @@ def quat_to_matrix(q) -> np.ndarray:
         [2 * (x * z - w * y), 2 * (y * z + w * x), 1 - 2 * (x * x + y * y)]])
 
 
-def project(pts, q, t, K=None) -> np.ndarray:
-    """Pinhole projection K [R|t] X (REV/utils/utils.py:56-69)."""
+def project(pts, q, t, K=None, dist=None) -> np.ndarray:
+    """Pinhole projection K [R|t] X (REV/utils/utils.py:56-69).  dist (k1, k2, p1, p2[, k3]): the
+    normalised point goes through OpenCV's distortion model first (the distort map of include/spe.h
+    spe_distort_points), as cv2.projectPoints does with distCoeffs."""
     K = Camera.K if K is None else K
     R = quat_to_matrix(q)
     pc = np.asarray(pts, np.float64) @ R.T + np.asarray(t, np.float64).reshape(1, 3)
+    if dist is not None:
+        k1, k2, p1, p2, k3 = LensModel(K, dist).dist
+        x, y = pc[:, 0] / pc[:, 2], pc[:, 1] / pc[:, 2]
+        r2 = x * x + y * y
+        rad = 1.0 + ((k3 * r2 + k2) * r2 + k1) * r2
+        xd = x * rad + 2.0 * p1 * x * y + p2 * (r2 + 2.0 * x * x)
+        yd = y * rad + p1 * (r2 + 2.0 * y * y) + 2.0 * p2 * x * y
+        return np.stack((K[0][0] * xd + K[0][2], K[1][1] * yd + K[1][2]), 1)
     uv = pc @ K.T
     return uv[:, :2] / uv[:, 2:3]

@@ -12,6 +12,9 @@ same pieces, with spe.rtdetr.SetCriterion and the reference's extra log fields.
 
 generate_submission() is the reference's gen_submission loop (REV/gen_submission_single.py:113-187,
 gen_submission_multi.py:123-186) from the JPEG files' bytes to the {filename: pose} log.
+
+A camera with lens distortion comes with the solver (spe.solver, lens=): the three loops hand it the
+crop's size as the sigmas' scale and everything downstream reads the undistorted keypoints.
 """
 from __future__ import annotations
 
@@ -76,9 +79,10 @@ def evaluate(model, criterion, postprocessors, data_loader, gt_file, solver, dev
             # EPnPCeresSolver: one threshold per image from its ground-truth box area (UNC SpeedEval
             # passes ground_truth[filename]["area"], src/data/speed/speed_dataset.py:396-399)
             poses = solver.solve_batch(outputs["points_px"], outputs["probs"], outputs.get("sigmas"),
-                                       area=[g["area"] for g in gt])
+                                       area=[g["area"] for g in gt], **_lens_kw(solver, outputs.get("sigmas"), clip))
         else:
-            poses = solver.solve_batch(outputs["points_px"], outputs["probs"], outputs.get("sigmas"))
+            poses = solver.solve_batch(outputs["points_px"], outputs["probs"], outputs.get("sigmas"),
+                                       **_lens_kw(solver, outputs.get("sigmas"), clip))
         q_gt = torch.tensor([g["quat"] for g in gt], dtype=torch.float64, device=device)
         t_gt = torch.tensor([g["tvec"] for g in gt], dtype=torch.float64, device=device)
         s_t, s_q = device_speed_score(poses["quat"], poses["tvec"], q_gt, t_gt)
@@ -127,7 +131,8 @@ def evaluate_rtdetr(model, criterion, postprocessors, data_loader, gt_file, solv
         if criterion is not None:
             ld = criterion(outputs, [{k: v.to(device) for k, v in t.items() if torch.is_tensor(v)} for t in targets])
             _log_losses(ld, criterion.weight_dict, device, log)
-        poses = solver.solve_batch(outputs["points_px"], outputs["probs"], outputs["sigmas"])
+        poses = solver.solve_batch(outputs["points_px"], outputs["probs"], outputs["sigmas"],
+                                   **_lens_kw(solver, outputs["sigmas"], clip))
         gt = [evaluator.ground_truth[f] for f in filenames]
         q_gt = torch.tensor([g["quat"] for g in gt], dtype=torch.float64, device=device)
         t_gt = torch.tensor([g["tvec"] for g in gt], dtype=torch.float64, device=device)
@@ -142,6 +147,14 @@ def evaluate_rtdetr(model, criterion, postprocessors, data_loader, gt_file, solv
     stats = {k: s / max(n, 1) for k, (s, n) in meters.items()}
     stats["speed_eval_pose"] = evaluator.stats
     return stats, evaluator
+
+
+def _lens_kw(solver, sigmas, clip):
+    """solve_batch's sigma_scale for a solver with a lens: the crop's size, as the covariance takes it."""
+    if sigmas is None or getattr(solver, "lens", None) is None:
+        return {}
+    from .solver import sigma_scale_of
+    return {"sigma_scale": sigma_scale_of(clip, sigmas.device)}
 
 
 def _log_pred_score(log, filenames, cov):
@@ -247,7 +260,8 @@ def generate_submission(models, postprocessors, anns, read_file, solver, device,
                 poses = solver.solve_batch_multi([o["points_px"] for o in outs], [o["probs"] for o in outs])
         else:
             o = models(t["crops"], clip_bbox=t["clip_bbox"])
-            poses = solver.solve_batch(o["points_px"], o["probs"], o.get("sigmas"))
+            poses = solver.solve_batch(o["points_px"], o["probs"], o.get("sigmas"),
+                                       **_lens_kw(solver, o.get("sigmas"), t["clip_bbox"]))
         # failed images carry the zero pose, as in SpeedEval.update_batch: every solver status but OK
         # and RANSAC_FALLBACK, and here a status-1 crop too
         st = poses["status"]

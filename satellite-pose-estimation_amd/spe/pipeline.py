@@ -12,7 +12,7 @@ import torch
 
 from . import _lib
 from .models import DETR
-from .solver import PoseSolver
+from .solver import PoseSolver, sigma_scale_of
 from .speed_eval import device_speed_score
 
 
@@ -48,7 +48,8 @@ class PosePipeline:
     """model: a DETR or an spe.rtdetr.RTDETR -- the pipeline uses cfg.input_size, cfg.num_queries, workspace,
     new_workspace, encode, decode and __call__, which the two share; an RTDETR's sigmas reach the solver
     (the sigma solvers, self_assess) in every mode, and its 8-bit crops (host_input) go straight to its u8
-    stems."""
+    stems.  A solver built with lens= undistorts the keypoints and sigmas first, one more launch on the
+    solver's stream before the solve; run()'s poses then carry points_ideal, sigmas_ideal and lens_status."""
 
     def __init__(self, model: "DETR | RTDETR", solver: PoseSolver, batch: int, device="cuda", use_graph: bool = False,
                  self_assess: bool = True, overlap: bool = False, raw_frames=None, overlap_decode: bool = False,
@@ -151,11 +152,15 @@ class PosePipeline:
 
     def _solve(self, fo, stream=None, q_gt=None, t_gt=None, repro=None, clip=None):
         sig = fo.get("sigmas")
+        kw = {}
+        if sig is not None and getattr(self.solver, "lens", None) is not None:
+            # the lens maps the crop-normalised sigmas in pixels: the scale the covariance derives too
+            kw["sigma_scale"] = sigma_scale_of(self.clip_bbox if clip is None else clip, sig.device, stream)
         if self.per_image_th:
             poses = self.solver.solve_batch(fo["points_px"], fo["probs"], sig, stream=stream,
-                                            repro_per_image=self.repro if repro is None else repro)
+                                            repro_per_image=self.repro if repro is None else repro, **kw)
         else:
-            poses = self.solver.solve_batch(fo["points_px"], fo["probs"], sig, stream=stream)
+            poses = self.solver.solve_batch(fo["points_px"], fo["probs"], sig, stream=stream, **kw)
         q_gt = self.q_gt if q_gt is None else q_gt
         t_gt = self.t_gt if t_gt is None else t_gt
         s_t, s_q = device_speed_score(poses["quat"], poses["tvec"], q_gt, t_gt, stream=stream)
@@ -299,7 +304,7 @@ class PosePipeline:
         # the ground truth is snapshotted on the caller's stream: a load() of the next batch may
         # overwrite q_gt / t_gt while this batch's score still runs on the solver stream
         q_gt, t_gt, repro = self.q_gt.clone(), self.t_gt.clone(), self.repro.clone()
-        clip = self.clip_bbox.clone() if self.pose_cov else None
+        clip = self.clip_bbox.clone() if self.pose_cov or getattr(self.solver, "lens", None) is not None else None
         s1.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(s1):
             for t in list(_tensors(fo)) + [q_gt, t_gt, repro] + ([clip] if clip is not None else []):
@@ -351,6 +356,10 @@ class PosePipeline:
             self.t_gt.copy_(t_gt, non_blocking=True)
 
     def run(self):
+        """One step.  With a lens solver, poses["points_ideal"], ["sigmas_ideal"] and ["lens_status"] are
+        the solver's own buffers (PoseSolver.undistort): the next run() overwrites them on the solver's
+        stream, also in the overlap modes, so clone them after wait(out) if they must outlive the next step.
+        Every other output is this step's own."""
         if not self.use_graph:
             self.out = self._body()
             return self.out

@@ -6,6 +6,10 @@ batched HIP solver kernel (csrc/pnp.hip) through spe_pnp_batch.
     quat, tvec = solver(points, logits)         # one image, numpy, like the reference
     poses = solver.solve_batch(points_px, probs) # whole batch on device (hot path)
 
+A camera with lens distortion: every solver class takes lens=LensModel(K, dist) (build_solver: args.dist)
+and then undistorts its keypoints, and their sigmas, on the device (spe_undistort_points) before the
+unchanged solver kernel runs on the ideal points.
+
 Failures raise exactly what the reference raises so SpeedEval.update maps them to a zero
 pose: IndexError when no foreground label survives, SolverError (the cv2.error stand-in)
 when OpenCV would assert (fewer than 4 correspondences) or leave its output undefined.
@@ -16,7 +20,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .config import Camera, world_points
+from .config import Camera, LensModel, world_points
 
 MODES = {"epnp": _lib.SPE_PNP_EPNP, "ransac_p3p_lm": _lib.SPE_PNP_RANSAC_P3P_LM,
          "epnp_ransac_sigma": _lib.SPE_PNP_EPNP_RANSAC_SIGMA, "epnp_lm": _lib.SPE_PNP_EPNP_LM,
@@ -27,10 +31,21 @@ class SolverError(RuntimeError):
     """Raised where the reference's cv2 call raises cv2.error."""
 
 
-class PoseSolver:
-    """Holds the 11 world landmarks (REV/utils/speed_eval.py:28-39) and camera K."""
+def sigma_scale_of(clip_bbox, device, stream=None):
+    """clip_bbox [B,4] (x1, y1, x2, y2) -> [B,2] fp32, the crop's width and height: the pixels per unit of
+    a crop-normalised sigma, per axis (the factor PostProcess applies to the points).  Made on the stream
+    the kernels read it on."""
+    with torch.cuda.stream(stream if stream is not None else torch.cuda.current_stream()):
+        cb = clip_bbox.to(device=device, dtype=torch.float32)
+        return torch.stack((cb[:, 2] - cb[:, 0], cb[:, 3] - cb[:, 1]), 1).contiguous()
 
-    def __init__(self, mode=_lib.SPE_PNP_RANSAC_P3P_LM, repro=20.0, ransac_iters=100, confidence=0.99):
+
+class PoseSolver:
+    """Holds the 11 world landmarks (REV/utils/speed_eval.py:28-39) and camera K.  lens (a
+    spe.config.LensModel, None: a pinhole camera): its K replaces Camera.K, and solve_batch first maps
+    the points and sigmas to the ideal image (undistort)."""
+
+    def __init__(self, mode=_lib.SPE_PNP_RANSAC_P3P_LM, repro=20.0, ransac_iters=100, confidence=0.99, lens=None):
         self.W_Pt = world_points()
         self.K = Camera.K.copy()
         self.mode = mode
@@ -38,6 +53,53 @@ class PoseSolver:
         self.ransac_iters = int(ransac_iters)
         self.confidence = float(confidence)
         self._dev = {}
+        self.lens = None
+        if lens is not None:
+            self.set_lens(lens)
+
+    def set_lens(self, lens):
+        """Installs a LensModel: the ideal points are pixels of its K, which the solver then uses."""
+        self.lens = lens
+        self.K = np.array(lens.K)
+        self._dev = {}
+        self._lens_dist = {}
+        self._lens_buf = {}
+
+    def undistort(self, points_px, sigmas=None, sigma_scale=None, stream=None):
+        """The lens step (include/spe.h spe_undistort_points), one launch: points_px [N,Q,2] distorted
+        pixels (+ sigmas [N,Q,2], sigma_scale [N,2] pixels per sigma unit, None: the sigmas are pixels)
+        -> dict of device tensors points_ideal [N,Q,2], sigmas_ideal [N,Q,2] (None without sigmas) and
+        lens_status [N,Q] u8 (1: the iteration left the model's domain, the point and its sigma are
+        returned unchanged).  The outputs are buffers the solver keeps per (device, shape): the next call
+        with the same shape overwrites them, clone what must outlive it."""
+        N, Q = points_px.shape[0], points_px.shape[1]
+        dev = points_px.device
+        Kd, _ = self._consts(dev)
+        if str(dev) not in self._lens_dist:
+            self._lens_dist[str(dev)] = torch.tensor(self.lens.dist.tolist(), dtype=torch.float64, device=dev)
+        key = (str(dev), N, Q, sigmas is not None)
+        if key not in self._lens_buf:
+            self._lens_buf[key] = dict(points_ideal=torch.empty(N, Q, 2, device=dev),
+                                       sigmas_ideal=torch.empty(N, Q, 2, device=dev) if sigmas is not None else None,
+                                       lens_status=torch.empty(N, Q, dtype=torch.uint8, device=dev))
+        o = dict(self._lens_buf[key])
+        ins = [t.float().contiguous() if t is not None else None for t in (points_px, sigmas, sigma_scale)]
+        _lib.check(_lib.lib().spe_undistort_points(
+            _lib.stream_ptr(stream), _lib.ptr(ins[0]), _lib.ptr(ins[1]), _lib.ptr(ins[2]), N, Q, _lib.ptr(Kd),
+            _lib.ptr(self._lens_dist[str(dev)]), self.lens.iters, _lib.ptr(o["points_ideal"]),
+            _lib.ptr(o["sigmas_ideal"]), _lib.ptr(o["lens_status"])), "spe_undistort_points")
+        if stream is not None:
+            # a converted copy was made on the current stream and is dropped here, while the kernel reads it
+            # on `stream`
+            for t, src in zip(ins, (points_px, sigmas, sigma_scale)):
+                if t is not None and t is not src:
+                    t.record_stream(stream)
+        return o
+
+    def _lens_step(self, points_px, sigmas, sigma_scale, stream):
+        """solve_batch's prologue with a lens: (points, sigmas) to solve on and what `out` gains."""
+        o = self.undistort(points_px, sigmas, sigma_scale, stream)
+        return o["points_ideal"], o["sigmas_ideal"], {k: v for k, v in o.items() if v is not None}
 
     def _consts(self, device):
         key = str(device)
@@ -46,14 +108,23 @@ class PoseSolver:
                               torch.as_tensor(self.W_Pt, dtype=torch.float64, device=device).contiguous())
         return self._dev[key]
 
-    def solve_batch(self, points_px, probs, sigmas=None, stream=None, out=None, repro_per_image=None):
+    def solve_batch(self, points_px, probs, sigmas=None, stream=None, out=None, repro_per_image=None,
+                    sigma_scale=None, undistorted=False):
         """points_px [B,Q,2], probs [B,Q,C] (+ sigmas [B,Q,2]) device fp32 -> dict of device
         tensors quat [B,4] f32, tvec [B,3] f64, rvec, status, n_corr, corr_label [B,16],
         inlier_mask [B].  repro_per_image: device fp32 [B] thresholds replacing
-        reprojectionError image by image (EPnPCeresSolver)."""
+        reprojectionError image by image (EPnPCeresSolver).
+
+        With a lens the points and sigmas first go through undistort() and the solver runs on its
+        buffers; the result also carries points_ideal, sigmas_ideal (with sigmas) and lens_status.
+        sigma_scale [B,2]: the pixels per sigma unit (sigma_scale_of(clip_bbox) for a model's
+        crop-normalised sigmas; None: they are pixels).  undistorted: the points are ideal already."""
         B, Q, C = probs.shape
         dev = probs.device
         Kd, Wd = self._consts(dev)
+        ideal = {}
+        if self.lens is not None and not undistorted and B > 0:
+            points_px, sigmas, ideal = self._lens_step(points_px, sigmas, sigma_scale, stream)
         if out is None:
             out = dict(quat=torch.empty(B, 4, device=dev), tvec=torch.empty(B, 3, dtype=torch.float64, device=dev),
                        rvec=torch.empty(B, 3, dtype=torch.float64, device=dev),
@@ -68,6 +139,7 @@ class PoseSolver:
             _lib.ptr(out["tvec"]), _lib.ptr(out["rvec"]), _lib.ptr(out["status"]), _lib.ptr(out["n_corr"]),
             _lib.ptr(out["corr_label"]), _lib.ptr(out["inlier_mask"]),
             _lib.ptr(repro_per_image.float().contiguous() if repro_per_image is not None else None)), "spe_pnp_batch")
+        out.update(ideal)
         return out
 
     def self_assess(self, probs, sigmas, poses, score_th=0.5, sigma_th=5.0, min_inliers=4, stream=None):
@@ -95,8 +167,10 @@ class PoseSolver:
         applies to the points; None: they are in pixels.  Returns device tensors pose_cov [B,6,6] f64
         (state order: rotation rad, translation m), sigma_rot [B] f32, sigma_t [B,3] f64, pred_score [B]
         f32 and cov_status [B] i32 (0 ok, 1 no pose, 2 fewer than 3 inliers, 3 bad sigma, 4 singular;
-        the numeric outputs of a non-zero status are 0)."""
+        the numeric outputs of a non-zero status are 0).  Poses solved through a lens carry
+        sigmas_ideal, the sigmas in the image the pose was solved in: those are used."""
         B, Q, C = probs.shape
+        sigmas = poses.get("sigmas_ideal", sigmas)
         dev = probs.device
         Kd, Wd = self._consts(dev)
         if C - 1 > Wd.shape[0]:
@@ -109,9 +183,7 @@ class PoseSolver:
         scale = None
         if clip_bbox is not None:
             # made on the stream the kernel reads it on
-            with torch.cuda.stream(stream if stream is not None else torch.cuda.current_stream()):
-                cb = clip_bbox.to(device=dev, dtype=torch.float32)
-                scale = torch.stack((cb[:, 2] - cb[:, 0], cb[:, 3] - cb[:, 1]), 1).contiguous()
+            scale = sigma_scale_of(clip_bbox, dev, stream)
         _lib.check(_lib.lib().spe_pose_covariance(
             _lib.stream_ptr(stream), _lib.ptr(probs.contiguous()), _lib.ptr(sigmas.contiguous()), _lib.ptr(scale),
             _lib.ptr(poses["status"]), _lib.ptr(poses["corr_label"]), _lib.ptr(poses["inlier_mask"]),
@@ -123,7 +195,7 @@ class PoseSolver:
     def find_index(self, logits):
         return logits.argmax(1), logits.max(1)
 
-    def __call__(self, points, logits, sigmas=None, device=None):
+    def __call__(self, points, logits, sigmas=None, device=None, undistorted=False):
         """One image, numpy in / numpy out (REV/utils/speed_eval.py:164-242)."""
         points = np.asarray(points, dtype=np.float32)
         logits = np.asarray(logits, dtype=np.float32)
@@ -132,7 +204,7 @@ class PoseSolver:
         p = torch.from_numpy(points[None].copy()).to(dev)
         l = torch.from_numpy(logits[None].copy()).to(dev)
         s = torch.from_numpy(np.asarray(sigmas, np.float32)[None].copy()).to(dev) if sigmas is not None else None
-        o = self.solve_batch(p, l, s)
+        o = self.solve_batch(p, l, s, undistorted=True) if undistorted else self.solve_batch(p, l, s)
         st = int(o["status"][0].item())
         if st == _lib.SPE_PNP_NO_FG:
             raise IndexError("no foreground keypoint")
@@ -145,15 +217,16 @@ class SimplePoseSolver(PoseSolver):
     """cv2.solvePnPRansac(P3P, reprojectionError=args.repro) + solvePnPGeneric(ITERATIVE)
     (REV/utils/speed_eval.py:143-242)."""
 
-    def __init__(self, args=None):
-        super().__init__(_lib.SPE_PNP_RANSAC_P3P_LM, getattr(args, "repro", 20) if args is not None else 20)
+    def __init__(self, args=None, lens=None):
+        super().__init__(_lib.SPE_PNP_RANSAC_P3P_LM, getattr(args, "repro", 20) if args is not None else 20,
+                         lens=lens)
 
 
 class SimplePoseSolverSigma(PoseSolver):
     """EPnP-RANSAC (reprojection 25) + sigma-weighted Huber LM (UNC/utils/speed_eval.py:322-420)."""
 
-    def __init__(self, args=None):
-        super().__init__(_lib.SPE_PNP_EPNP_RANSAC_SIGMA, 25.0)
+    def __init__(self, args=None, lens=None):
+        super().__init__(_lib.SPE_PNP_EPNP_RANSAC_SIGMA, 25.0, lens=lens)
 
 
 class EPnPSolver(PoseSolver):
@@ -161,8 +234,8 @@ class EPnPSolver(PoseSolver):
     BASELINE config 2 ("EPnP only, no RANSAC").  inlier_mask: epnp_init's set, reprojection error
     < reprojectionError."""
 
-    def __init__(self, args=None, refine=False):
-        super().__init__(_lib.SPE_PNP_EPNP_LM if refine else _lib.SPE_PNP_EPNP, 20.0)
+    def __init__(self, args=None, refine=False, lens=None):
+        super().__init__(_lib.SPE_PNP_EPNP_LM if refine else _lib.SPE_PNP_EPNP, 20.0, lens=lens)
 
 
 class EPnPCeresSolver(PoseSolver):
@@ -171,8 +244,8 @@ class EPnPCeresSolver(PoseSolver):
     sigma-weighted Huber(0.001) LM on the inliers, and the EPnP pose kept when the refined error
     sum over all points is larger.  A batch carries one threshold per image."""
 
-    def __init__(self, input_size=256):
-        super().__init__(_lib.SPE_PNP_EPNP_CERES, 20.0)
+    def __init__(self, input_size=256, lens=None):
+        super().__init__(_lib.SPE_PNP_EPNP_CERES, 20.0, lens=lens)
         self.input_size = input_size
 
     def repro_th(self, area):
@@ -187,7 +260,8 @@ class EPnPCeresSolver(PoseSolver):
         self.reprojectionError = self.repro_th(area)
         return self.reprojectionError
 
-    def solve_batch(self, points_px, probs, sigmas=None, stream=None, out=None, repro_per_image=None, area=None):
+    def solve_batch(self, points_px, probs, sigmas=None, stream=None, out=None, repro_per_image=None, area=None,
+                    sigma_scale=None, undistorted=False):
         """As PoseSolver.solve_batch with one threshold per image: `area` (B box areas) or
         `repro_per_image` (device fp32 [B]) is required -- the reference has no batch-wide
         threshold for this solver (get_repro_th runs per image, :90)."""
@@ -198,7 +272,8 @@ class EPnPCeresSolver(PoseSolver):
             repro_per_image = torch.tensor([self.repro_th(float(a)) for a in area], dtype=torch.float32,
                                            device=probs.device)
         repro_per_image = repro_per_image.float().contiguous()
-        o = super().solve_batch(points_px, probs, sigmas, stream=stream, out=out, repro_per_image=repro_per_image)
+        o = super().solve_batch(points_px, probs, sigmas, stream=stream, out=out, repro_per_image=repro_per_image,
+                                sigma_scale=sigma_scale, undistorted=undistorted)
         # the kernel may still read the thresholds on `stream` after this returns
         if stream is not None:
             repro_per_image.record_stream(stream)
@@ -219,18 +294,19 @@ class ExhaustivePoseSolver(PoseSolver):
     revert-if-worse; the candidate with the smallest error sum wins.  Draws no samples: the result is a
     function of the correspondences alone.  What is unpinned: include/spe.h, SPE_PNP_EXHAUSTIVE."""
 
-    def __init__(self, topk=10, input_size=256, repro=20.0):
+    def __init__(self, topk=10, input_size=256, repro=20.0, lens=None):
         topk = int(topk)
         if not 1 <= topk <= 64:
             raise ValueError(f"topk must be in [1, 64], got {topk}")
-        super().__init__(_lib.SPE_PNP_EXHAUSTIVE, repro)
+        super().__init__(_lib.SPE_PNP_EXHAUSTIVE, repro, lens=lens)
         self.topk = topk
         self.input_size = input_size
 
     repro_th = EPnPCeresSolver.repro_th
     get_repro_th = EPnPCeresSolver.get_repro_th
 
-    def solve_batch(self, points_px, probs, sigmas=None, stream=None, out=None, repro_per_image=None, area=None):
+    def solve_batch(self, points_px, probs, sigmas=None, stream=None, out=None, repro_per_image=None, area=None,
+                    sigma_scale=None, undistorted=False):
         """As PoseSolver.solve_batch plus cand_index [B] i32 (the winner's subset index, -1 without a
         pose) and repro_final [B] f32 (the threshold after growth).  `area` (B box areas, get_repro_th
         each) or `repro_per_image` (device fp32 [B]) gives one threshold per image; with neither the
@@ -238,6 +314,9 @@ class ExhaustivePoseSolver(PoseSolver):
         B, Q, C = probs.shape
         dev = probs.device
         Kd, Wd = self._consts(dev)
+        ideal = {}
+        if self.lens is not None and not undistorted and B > 0:
+            points_px, sigmas, ideal = self._lens_step(points_px, sigmas, sigma_scale, stream)
         if repro_per_image is None and area is not None:
             repro_per_image = torch.tensor([self.repro_th(float(a)) for a in area], dtype=torch.float32, device=dev)
         if repro_per_image is not None:
@@ -259,6 +338,7 @@ class ExhaustivePoseSolver(PoseSolver):
             _lib.ptr(out["status"]), _lib.ptr(out["n_corr"]), _lib.ptr(out["corr_label"]),
             _lib.ptr(out["inlier_mask"]), _lib.ptr(repro_per_image), _lib.ptr(out["cand_index"]),
             _lib.ptr(out["repro_final"])), "spe_pnp_exhaustive")
+        out.update(ideal)
         if repro_per_image is not None:
             # the kernel may still read the thresholds on `stream` after this returns
             if stream is not None:
@@ -275,16 +355,22 @@ class ExhaustivePoseSolver(PoseSolver):
 class Multi_Mean_PoseSolver(PoseSolver):
     """Multi-checkpoint ensemble (REV/utils/speed_eval.py:42-140): the M models' keypoints are
     fused per label (mean after a 3-sigma filter, first-seen label order) on the device
-    (spe_ensemble_fuse) and solved like SimplePoseSolver (P3P-RANSAC + LM)."""
+    (spe_ensemble_fuse) and solved like SimplePoseSolver (P3P-RANSAC + LM).  With a lens every model's
+    points are undistorted before the fusion, in one launch over [M * B, Q]."""
 
-    def __init__(self, args=None):
-        super().__init__(_lib.SPE_PNP_RANSAC_P3P_LM, getattr(args, "repro", 25) if args is not None else 25)
+    def __init__(self, args=None, lens=None):
+        super().__init__(_lib.SPE_PNP_RANSAC_P3P_LM, getattr(args, "repro", 25) if args is not None else 25,
+                         lens=lens)
 
     def fuse_batch(self, multi_points_px, multi_probs, stream=None):
         """lists of M device tensors [B,Q,2] / [B,Q,C] -> fused points [B,C-1,2], probs [B,C-1,C]."""
         pts = torch.stack(list(multi_points_px)).float().contiguous()
         prb = torch.stack(list(multi_probs)).float().contiguous()
         M, B, Q, C = prb.shape
+        if self.lens is not None and B > 0:
+            if stream is not None:
+                pts.record_stream(stream)      # the stacked copy is read on `stream` and dropped here
+            pts = self.undistort(pts.view(M * B, Q, 2), stream=stream)["points_ideal"].view(M, B, Q, 2)
         fp = torch.empty(B, C - 1, 2, device=prb.device)
         fr = torch.empty(B, C - 1, C, device=prb.device)
         _lib.check(_lib.lib().spe_ensemble_fuse(_lib.stream_ptr(stream), _lib.ptr(pts), _lib.ptr(prb), M, B, Q, C,
@@ -293,7 +379,7 @@ class Multi_Mean_PoseSolver(PoseSolver):
 
     def solve_batch_multi(self, multi_points_px, multi_probs, stream=None):
         fp, fr = self.fuse_batch(multi_points_px, multi_probs, stream=stream)
-        return self.solve_batch(fp, fr, stream=stream)
+        return self.solve_batch(fp, fr, stream=stream, undistorted=True)
 
     def __call__(self, multi_points, multi_logits, device=None):
         """One image, numpy lists in / numpy out, the reference's call (gen_submission)."""
@@ -303,7 +389,7 @@ class Multi_Mean_PoseSolver(PoseSolver):
         mp = [torch.from_numpy(np.asarray(p, np.float32)[None].copy()).to(dev) for p in multi_points]
         ml = [torch.from_numpy(np.asarray(l, np.float32)[None].copy()).to(dev) for l in multi_logits]
         fp, fr = self.fuse_batch(mp, ml)
-        return PoseSolver.__call__(self, fp[0].cpu().numpy(), fr[0].cpu().numpy(), device=dev)
+        return PoseSolver.__call__(self, fp[0].cpu().numpy(), fr[0].cpu().numpy(), device=dev, undistorted=True)
 
 
 class SigmaEnsemblePoseSolver:
@@ -312,12 +398,20 @@ class SigmaEnsemblePoseSolver:
     reference counterpart, is defined in include/spe.h), then solved by `backend` -- any solver object of
     this module, SimplePoseSolverSigma by default -- with the fused sigma.  The fused arrays have
     solve_batch's layout, so the backend's self_assess and pose_covariance take them as they take one
-    model's."""
+    model's.  With a lens every model's points and sigmas are undistorted before the fusion, in one launch
+    over [M * B, Q], and the fused arrays are ideal.  The lens is the backend's.  lens=: NOTE that it is
+    installed ON THE BACKEND OBJECT passed in (set_lens: its K is replaced and it undistorts from then on,
+    also when called directly); a backend that already holds another lens is refused."""
 
-    def __init__(self, backend=None, gate=3.0, sigma_floor=1e-3):
+    def __init__(self, backend=None, gate=3.0, sigma_floor=1e-3, lens=None):
         self.backend = backend if backend is not None else SimplePoseSolverSigma()
         if not hasattr(self.backend, "solve_batch"):
             raise ValueError("SigmaEnsemblePoseSolver: the backend must be a solver object (solve_batch)")
+        if lens is not None:
+            if getattr(self.backend, "lens", None) not in (None, lens):
+                raise ValueError("SigmaEnsemblePoseSolver: the backend already holds a different lens")
+            if self.backend.lens is None:
+                self.backend.set_lens(lens)
         self.gate = float(gate)
         self.sigma_floor = float(sigma_floor)
         if not self.gate > 0:
@@ -329,11 +423,16 @@ class SigmaEnsemblePoseSolver:
     def mode(self):
         return self.backend.mode
 
+    @property
+    def lens(self):
+        return getattr(self.backend, "lens", None)
+
     def fuse_batch(self, multi_points_px, multi_probs, multi_sigmas, clip_bbox=None, stream=None):
         """lists of M device tensors [B,Q,2] / [B,Q,C] / [B,Q,2] -> dict of device tensors points
         [B,C-1,2], probs [B,C-1,C], sigmas [B,C-1,2] f32, n_pooled, n_kept [B,C-1] i32.  clip_bbox [B,4]
         (x1, y1, x2, y2): the sigmas are crop-normalised and weigh in pixels, by the crop's width and
-        height; the fused sigma is crop-normalised again.  None: they are in the points' unit."""
+        height; the fused sigma is crop-normalised again.  None: they are in the points' unit.  With a
+        lens also lens_status [M,B,Q] u8 (PoseSolver.undistort)."""
         if multi_sigmas is None:
             raise ValueError("SigmaEnsemblePoseSolver needs every model's sigmas (multi_sigmas)")
         with torch.cuda.stream(stream if stream is not None else torch.cuda.current_stream()):
@@ -346,12 +445,23 @@ class SigmaEnsemblePoseSolver:
             if clip_bbox is not None:
                 cb = clip_bbox.to(device=dev, dtype=torch.float32)
                 scale = torch.stack((cb[:, 2] - cb[:, 0], cb[:, 3] - cb[:, 1]), 1).contiguous()
+            lens_scale = scale.repeat(M, 1) if scale is not None and self.lens is not None else None
         if pts.shape != (M, B, Q, 2) or sig.shape != (M, B, Q, 2):
             raise ValueError(f"points {tuple(pts.shape)} / sigmas {tuple(sig.shape)} do not match probs {tuple(prb.shape)}")
+        lens_status = None
+        if self.lens is not None and B > 0:
+            u = self.backend.undistort(pts.view(M * B, Q, 2), sig.view(M * B, Q, 2), lens_scale, stream)
+            if stream is not None:
+                for t in (pts, sig) + ((lens_scale,) if lens_scale is not None else ()):
+                    t.record_stream(stream)
+            pts, sig = u["points_ideal"].view(M, B, Q, 2), u["sigmas_ideal"].view(M, B, Q, 2)
+            lens_status = u["lens_status"].view(M, B, Q)
         out = dict(points=torch.empty(B, C - 1, 2, device=dev), probs=torch.empty(B, C - 1, C, device=dev),
                    sigmas=torch.empty(B, C - 1, 2, device=dev),
                    n_pooled=torch.empty(B, C - 1, dtype=torch.int32, device=dev),
                    n_kept=torch.empty(B, C - 1, dtype=torch.int32, device=dev))
+        if lens_status is not None:
+            out["lens_status"] = lens_status
         if B == 0:
             return out
         _lib.check(_lib.lib().spe_ensemble_fuse_sigma(
@@ -371,6 +481,8 @@ class SigmaEnsemblePoseSolver:
         the backend's pose dict plus "fused", fuse_batch's dict."""
         fused = self.fuse_batch(multi_points_px, multi_probs, multi_sigmas, clip_bbox=clip_bbox, stream=stream)
         kw = {}
+        if self.lens is not None:
+            kw["undistorted"] = True           # fuse_batch undistorted every model's points and sigmas
         if area is not None:
             kw["area"] = area
         if repro_per_image is not None:
@@ -389,8 +501,10 @@ class SigmaEnsemblePoseSolver:
 def build_solver(args=None):
     """REV/utils/speed_eval.py:21-22 (SimplePoseSolver); `args.solver` selects the variant.
     "ensemble_sigma" wraps the solver `args.backend` names (epnp_ransac_sigma by default) in a
-    SigmaEnsemblePoseSolver with `args.gate` / `args.sigma_floor`."""
+    SigmaEnsemblePoseSolver with `args.gate` / `args.sigma_floor`.  `args.dist` (4 or 5 OpenCV distortion
+    coefficients), when present, gives the solver a lens (LensModel.from_args)."""
     name = getattr(args, "solver", "ransac_p3p_lm") if args is not None else "ransac_p3p_lm"
+    lens = LensModel.from_args(args) if getattr(args, "dist", None) is not None else None
     if name == "ensemble_sigma":
         import argparse
         backend = getattr(args, "backend", "epnp_ransac_sigma")
@@ -400,14 +514,14 @@ def build_solver(args=None):
         return SigmaEnsemblePoseSolver(build_solver(inner), getattr(args, "gate", 3.0),
                                        getattr(args, "sigma_floor", 1e-3))
     if name == "ransac_p3p_lm":
-        return SimplePoseSolver(args)
+        return SimplePoseSolver(args, lens=lens)
     if name == "epnp_ransac_sigma":
-        return SimplePoseSolverSigma(args)
+        return SimplePoseSolverSigma(args, lens=lens)
     if name in ("epnp", "epnp_lm"):
-        return EPnPSolver(args, refine=name == "epnp_lm")
+        return EPnPSolver(args, refine=name == "epnp_lm", lens=lens)
     if name == "epnp_ceres":
-        return EPnPCeresSolver(getattr(args, "input_size", 256) if args is not None else 256)
+        return EPnPCeresSolver(getattr(args, "input_size", 256) if args is not None else 256, lens=lens)
     if name == "exhaustive":
         return ExhaustivePoseSolver(getattr(args, "topk", 10), getattr(args, "input_size", 256),
-                                    getattr(args, "repro", 20.0))
+                                    getattr(args, "repro", 20.0), lens=lens)
     raise ValueError(f"unknown solver {name}")
