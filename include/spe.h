@@ -614,6 +614,59 @@ int spe_pose_covariance(void* stream, const float* probs, const float* sigmas,
                         float* sigma_rot, double* sigma_t, float* pred_score,
                         int32_t* cov_status);
 
+/* Calibration records: what a predicted sigma, covariance and score are compared with when the ground
+ * truth pose is known.  No reference code exists (the reference's self-assessment is commented out); this
+ * comment is the definition, all of it in fp64.  Inputs are those of spe_pose_covariance (device pointers,
+ * the same K and world, corr_label [B,16]) plus points_px [B,Q,2] in the image the pose was solved in, the
+ * ground truth q_gt [B,4] / t_gt [B,3], and spe_pose_covariance's cov [B,6,6] / cov_status [B].
+ *
+ * sigma_gain (finite and > 0, else SPE_E_ARG) is the calibration factor under test: it multiplies the
+ * sigma before the floor, effective sigma = max(sigma * scale * gain, sigma_floor), and the covariance is
+ * read as cov * gain^2.  cov is therefore the covariance at gain 1.
+ *
+ * Ground-truth rotation.  R_gt is the rotation whose quaternion (w, x, y, z), as spe_pnp_batch emits it
+ * (Blender's mat3_to_quat of the camera-from-body R), is q_gt / |q_gt|:
+ *     R_gt = [[1-2(yy+zz), 2(xy-zw), 2(xz+yw)], [2(xy+zw), 1-2(xx+zz), 2(yz-xw)], [2(xz-yw), 2(yz+xw), 1-2(xx+yy)]]
+ * so a pose whose emitted quaternion equals q_gt has no rotation error; spe_speed_score pairs the two
+ * quaternions component by component, the same convention.
+ *
+ * Pose error, in spe_pose_covariance's perturbation convention R_pr = exp([dw]x) R_gt, t_pr = t_gt + dt:
+ * with q_pr = (cos(|r|/2), sin(|r|/2) r/|r|) of rvec and q_rel = q_pr (x) conj(q_gt / |q_gt|) = (w, v), sign
+ * chosen so that w >= 0,  dw = 2 atan2(|v|, w) v/|v|  (0 where |v| = 0; never acos, so that a small angle
+ * keeps its digits) and dt = tvec - t_gt.  delta [B,6] = (dw, dt).  |dw| is spe_speed_score's s_q of the pair.
+ *
+ * NEES.  nees [B,3] = (delta^T S^-1 delta, dw^T S_ww^-1 dw, dt^T S_tt^-1 dt) with S = cov * gain^2 and its two
+ * marginal 3x3 blocks: 6, 3 and 3 degrees of freedom.  Each is one Cholesky solve of the Jacobi-scaled
+ * matrix D^-1/2 S D^-1/2, D = diag S; no inverse is formed.
+ *
+ * Keypoint z-scores.  For landmark l (0 <= l < L = num_classes - 1) the query is the one the solver's
+ * selection gives the label (highest score, the first on ties; the same code as spe_self_assess and
+ * spe_pose_covariance).  z [B,L,2] = (p_sel - pi(R_gt X_l + t_gt)) / effective sigma, per axis, with pi the
+ * pinhole projection (fx x/z + cx, fy y/z + cy).  kp_flags [B,L]: bit 0 valid -- some query carries the
+ * label, the ground-truth point has z > 0, and the point, the sigma * scale * gain product and the z-score are
+ * finite; bit 1 taking-part inlier -- the solver has a pose (status 0 or 3), a correspondence with this
+ * label has its bit set in inlier_mask, and some query carries the label (spe_pose_covariance's rule).  The
+ * bits are independent; where bit 0 is clear z = 0.
+ *
+ * calib_status [B], the first that applies:
+ *     0 ok
+ *     1 ground truth unusable: |q_gt| zero or not finite, or t_gt not finite
+ *     2 no pose (solver status not 0 or 3)
+ *     3 no covariance (cov_status != 0)
+ *     4 singular: delta not finite, a diagonal of S not positive and finite, a pivot of a scaled matrix
+ *       <= 64 * DBL_EPSILON, or a NEES that is not finite
+ * delta is written for status 0, 3 and 4 (all zero where it is not finite), nees for status 0, z and
+ * kp_flags for every status but 1; everything else is 0, and no NaN leaves the kernel.  num_queries <= 64,
+ * 2 <= num_classes <= 17, batch >= 1, sigma_floor positive and finite, else SPE_E_ARG before any launch.
+ * One launch (one wave per image); no allocation, no scratch, no synchronisation. */
+int spe_calibration_records(void* stream, const float* points_px, const float* probs, const float* sigmas,
+                            const float* sigma_scale, float sigma_floor, const int32_t* status,
+                            const int32_t* corr_label, const uint32_t* inlier_mask, const double* rvec,
+                            const double* tvec, const double* q_gt, const double* t_gt, const double* cov,
+                            const int32_t* cov_status, int batch, int num_queries, int num_classes,
+                            const double* K, const double* world, double sigma_gain, double* delta, double* nees,
+                            double* z, uint8_t* kp_flags, int32_t* calib_status);
+
 /* speed_score per image (REV/utils/speed_eval.py:245-262), device pointers. */
 int spe_speed_score(void* stream, const float* quat, const double* tvec, const double* q_gt, const double* t_gt,
                     int batch, double* s_t, double* s_q);

@@ -1,7 +1,8 @@
 // C entry points of the native runtime outside the model's forward pass (include/spe.h): the set
-// criterion, ensemble fusion, pre- and post-processing, the batched solver, its self-assessment and the
-// SPEED score.  No allocation or synchronisation happens inside spe_pnp_batch / spe_pnp_exhaustive /
-// spe_speed_score once the per-stream scratch has its size, so a caller may capture them into a hipGraph.
+// criterion, ensemble fusion, pre- and post-processing, the batched solver, its self-assessment, the pose
+// covariance, the calibration records and the SPEED score.  No allocation or synchronisation happens
+// inside spe_pnp_batch / spe_pnp_exhaustive / spe_speed_score once the per-stream scratch has its size,
+// so a caller may capture them into a hipGraph.
 #include <hip/hip_runtime.h>
 
 #include <map>
@@ -256,6 +257,25 @@ int spe_pose_covariance(void* stream, const float* probs, const float* sigmas, c
   PoseCovArgs a{probs, sigmas, sigma_scale, status, corr_label, inlier_mask, rvec, tvec, B, Q, C, K, world,
                 sigma_floor, cov, sigma_rot, sigma_t, pred_score, cov_status};
   CK(spe_launch_pose_cov(a, (hipStream_t)stream));
+  return 0;
+}
+
+int spe_calibration_records(void* stream, const float* points_px, const float* probs, const float* sigmas,
+                            const float* sigma_scale, float sigma_floor, const int32_t* status,
+                            const int32_t* corr_label, const uint32_t* inlier_mask, const double* rvec,
+                            const double* tvec, const double* q_gt, const double* t_gt, const double* cov,
+                            const int32_t* cov_status, int B, int Q, int C, const double* K, const double* world,
+                            double sigma_gain, double* delta, double* nees, double* z, uint8_t* kp_flags,
+                            int32_t* calib_status) {
+  if (!points_px || !probs || !sigmas || !status || !corr_label || !inlier_mask || !rvec || !tvec || !q_gt || !t_gt ||
+      !cov || !cov_status || !K || !world || !delta || !nees || !z || !kp_flags || !calib_status || B < 1 || Q <= 0 ||
+      Q > 64 || C < 2 || C > 17)
+    return fail(SPE_E_ARG, "bad argument");
+  if (!(sigma_floor > 0) || !(sigma_floor < INFINITY)) return fail(SPE_E_ARG, "sigma_floor must be positive and finite");
+  if (!(sigma_gain > 0) || !(sigma_gain < (double)INFINITY)) return fail(SPE_E_ARG, "sigma_gain must be positive and finite");
+  CalibArgs a{points_px, probs, sigmas, sigma_scale, sigma_floor, status, corr_label, inlier_mask, rvec, tvec, q_gt,
+              t_gt, cov, cov_status, B, Q, C, K, world, sigma_gain, delta, nees, z, kp_flags, calib_status};
+  CK(spe_launch_calib_records(a, (hipStream_t)stream));
   return 0;
 }
 

@@ -136,20 +136,8 @@ __device__ void epnp_solve_wave(EpnpShared& sh, const cam_t* k, const float* img
   __syncthreads();
 }
 
-// The two rules of the correspondence selection (REV/utils/speed_eval.py:152-206) that the solver,
-// the self-assessment and the pose covariance share: a query's label is the argmax of its C class
-// probabilities (the lower class on ties), and a label's query is the one with the highest such
-// score (the earlier query on ties).
-SPE_DEV int argmax_class(const float* p, int C, float* score) {
-  int lab = 0;
-  float sc = p[0];
-  for (int c = 1; c < C; ++c)
-    if (p[c] > sc) { sc = p[c]; lab = c; }
-  *score = sc;
-  return lab;
-}
-// does a later query with score `sc` replace the label's best so far (best_q < 0: none yet)
-SPE_DEV bool takes_over(int best_q, float best_s, float sc) { return best_q < 0 || sc > best_s; }
+// (argmax_class / takes_over, the two rules of the selection, and the 6x6 Cholesky pair chol6_factor /
+// chol6_backsolve are in pnp_math.h: calib.hip shares them.)
 
 // Correspondence selection (REV/utils/speed_eval.py:152-206): lane-parallel argmax over the C
 // class probabilities, then (lane 0) first-seen label order with the best-score query per label.
@@ -209,47 +197,6 @@ struct LmShared {
   double red[48];            // reduced normal equations: H[36], g[6], cost
   double x[6];               // fallback step
 };
-
-// Cholesky factor L (lower) of symmetric S (lower triangle read); false at the first pivot that is
-// not above thr
-__device__ __forceinline__ bool chol6_factor(const double* S, double thr, double (*L)[6]) {
-#pragma unroll
-  for (int j = 0; j < 6; ++j) {
-    double s = S[j * 6 + j];
-#pragma unroll
-    for (int p = 0; p < j; ++p) s -= L[j][p] * L[j][p];
-    if (!(s > thr)) return false;
-    L[j][j] = sqrt(s);
-    const double inv = 1.0 / L[j][j];
-#pragma unroll
-    for (int i = j + 1; i < 6; ++i) {
-      double t = S[i * 6 + j];
-#pragma unroll
-      for (int p = 0; p < j; ++p) t -= L[i][p] * L[j][p];
-      L[i][j] = t * inv;
-    }
-  }
-  return true;
-}
-
-// L L^T x = b
-__device__ __forceinline__ void chol6_backsolve(const double (*L)[6], const double* b, double* x) {
-  double y[6];
-#pragma unroll
-  for (int i = 0; i < 6; ++i) {
-    double t = b[i];
-#pragma unroll
-    for (int p = 0; p < i; ++p) t -= L[i][p] * y[p];
-    y[i] = t / L[i][i];
-  }
-#pragma unroll
-  for (int i = 5; i >= 0; --i) {
-    double t = y[i];
-#pragma unroll
-    for (int p = i + 1; p < 6; ++p) t -= L[p][i] * x[p];
-    x[i] = t / L[i][i];
-  }
-}
 
 // S x = b for symmetric S (lower triangle read); false when S is not safely positive definite
 __device__ __forceinline__ bool chol6_solve(const double* S, const double* b, double* x) {

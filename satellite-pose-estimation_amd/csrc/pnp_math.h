@@ -1185,3 +1185,59 @@ PNP_FN void blender_quat(const double* Rd, float* q) {
   else { q[1] = 1.0f; q[0] = q[2] = q[3] = 0.0f; }
 }
 
+/* ------------------------------------------------------------------ shared by pnp.hip and calib.hip */
+// The two rules of the correspondence selection (REV/utils/speed_eval.py:152-206) that the solver,
+// the self-assessment, the pose covariance and the calibration records share: a query's label is the
+// argmax of its C class probabilities (the lower class on ties), and a label's query is the one with
+// the highest such score (the earlier query on ties).
+__device__ __forceinline__ int argmax_class(const float* p, int C, float* score) {
+  int lab = 0;
+  float sc = p[0];
+  for (int c = 1; c < C; ++c)
+    if (p[c] > sc) { sc = p[c]; lab = c; }
+  *score = sc;
+  return lab;
+}
+// does a later query with score `sc` replace the label's best so far (best_q < 0: none yet)
+__device__ __forceinline__ bool takes_over(int best_q, float best_s, float sc) { return best_q < 0 || sc > best_s; }
+
+// Cholesky factor L (lower) of symmetric S (lower triangle read); false at the first pivot that is
+// not above thr
+__device__ __forceinline__ bool chol6_factor(const double* S, double thr, double (*L)[6]) {
+#pragma unroll
+  for (int j = 0; j < 6; ++j) {
+    double s = S[j * 6 + j];
+#pragma unroll
+    for (int p = 0; p < j; ++p) s -= L[j][p] * L[j][p];
+    if (!(s > thr)) return false;
+    L[j][j] = sqrt(s);
+    const double inv = 1.0 / L[j][j];
+#pragma unroll
+    for (int i = j + 1; i < 6; ++i) {
+      double t = S[i * 6 + j];
+#pragma unroll
+      for (int p = 0; p < j; ++p) t -= L[i][p] * L[j][p];
+      L[i][j] = t * inv;
+    }
+  }
+  return true;
+}
+
+// L L^T x = b
+__device__ __forceinline__ void chol6_backsolve(const double (*L)[6], const double* b, double* x) {
+  double y[6];
+#pragma unroll
+  for (int i = 0; i < 6; ++i) {
+    double t = b[i];
+#pragma unroll
+    for (int p = 0; p < i; ++p) t -= L[i][p] * y[p];
+    y[i] = t / L[i][i];
+  }
+#pragma unroll
+  for (int i = 5; i >= 0; --i) {
+    double t = y[i];
+#pragma unroll
+    for (int p = i + 1; p < 6; ++p) t -= L[p][i] * x[p];
+    x[i] = t / L[i][i];
+  }
+}

@@ -84,5 +84,33 @@ struct PoseCovArgs {
   int32_t* cov_status;        // [B]
 };
 int spe_launch_pose_cov(const PoseCovArgs& a, hipStream_t s);
+
+// Calibration records against ground truth (include/spe.h spe_calibration_records; csrc/calib.hip)
+struct CalibArgs {
+  const float* points;        // [B][Q][2] px, the image the pose was solved in
+  const float* probs;         // [B][Q][C]
+  const float* sigmas;        // [B][Q][2]
+  const float* sigma_scale;   // [B][2] or null
+  float sigma_floor;
+  const int32_t* status;      // [B]     (solver outputs)
+  const int32_t* corr_label;  // [B][16]
+  const uint32_t* inlier_mask;// [B]
+  const double* rvec;         // [B][3]
+  const double* tvec;         // [B][3]
+  const double* q_gt;         // [B][4]
+  const double* t_gt;         // [B][3]
+  const double* cov;          // [B][6][6] (spe_pose_covariance)
+  const int32_t* cov_status;  // [B]
+  int B, Q, C;
+  const double* K;            // 3x3 row-major
+  const double* world;        // [C-1][3]
+  double sigma_gain;
+  double* delta;              // [B][6]
+  double* nees;               // [B][3]
+  double* z;                  // [B][C-1][2]
+  uint8_t* kp_flags;          // [B][C-1]
+  int32_t* calib_status;      // [B]
+};
+int spe_launch_calib_records(const CalibArgs& a, hipStream_t s);
 int spe_launch_score(const float* quat, const double* tvec, const double* q_gt, const double* t_gt, int B,
                      double* s_t, double* s_q, hipStream_t s);

@@ -47,8 +47,14 @@ def _log_losses(ld, weight_dict, device, log):
 
 
 @torch.no_grad()
-def evaluate(model, criterion, postprocessors, data_loader, gt_file, solver, device, output_dir=None):
+def evaluate(model, criterion, postprocessors, data_loader, gt_file, solver, device, output_dir=None,
+             calibration=False, sigma_gain=1.0):
+    """calibration (a model with a sigma head): the keypoint sigmas, the pose covariance and its predicted score are
+    compared with the ground truth over the whole set (spe.calibration.Calibration at sigma_gain); the returned
+    stats then carry the summary dict under "calibration" and evaluator.stats one more line.  With several ranks
+    the log is gathered but the calibration is not: each rank's summary and line cover the images it evaluated."""
     evaluator = SpeedEval(gt_file, solver)
+    cal = _new_calibration(calibration, solver, sigma_gain)
     ceres = getattr(solver, "mode", None) == _lib.SPE_PNP_EPNP_CERES
     if ceres:
         # EPnPCeresSolver's per-image thresholds come from the ground-truth box areas: refuse up front a
@@ -89,16 +95,23 @@ def evaluate(model, criterion, postprocessors, data_loader, gt_file, solver, dev
         sig = outputs.get("sigmas")
         assess = solver.self_assess(outputs["probs"], sig, poses) if sig is not None else None
         evaluator.update_batch(filenames, outputs["points_px"], outputs["probs"], poses, s_t, s_q, sig, assess)
+        if cal is not None:
+            if sig is None:
+                raise ValueError("evaluate: calibration needs a model with a sigma head")
+            cal.update(outputs["points_px"], outputs["probs"], sig, poses,
+                       solver.pose_covariance(outputs["probs"], sig, poses, clip_bbox=clip), q_gt, t_gt, s_t, s_q,
+                       clip_bbox=clip)
     evaluator.log = spe_dist.all_gather_log(evaluator.log)
     evaluator.summarize()
     stats = {k: s / max(n, 1) for k, (s, n) in meters.items()}
+    _finish_calibration(cal, stats, evaluator)
     stats["speed_eval_pose"] = evaluator.stats
     return stats, evaluator
 
 
 @torch.no_grad()
 def evaluate_rtdetr(model, criterion, postprocessors, data_loader, gt_file, solver, device, output_dir=None,
-                    pose_cov=False):
+                    pose_cov=False, sigma_gain=1.0, calibration=False):
     """The UNC RT-DETR evaluation loop (UNC/solver/speed_engine.py:123-202) with evaluate()'s
     interface.  Per batch: one device pass (RTDETR.forward with clip_bbox, so RTDETRPostProcessor
     runs fused; `postprocessors` is accepted for the reference's signature), the device criterion
@@ -111,8 +124,11 @@ def evaluate_rtdetr(model, criterion, postprocessors, data_loader, gt_file, solv
     "sigma" and "aux_points_0..2", the first three aux_outputs entries' pred_logits (the reference
     stores logits under that name) rounded to 2 decimals.  pose_cov: each entry also carries
     "pred_score", the pose covariance's first-order prediction of the image's score
-    (PoseSolver.pose_covariance; 0 where cov_status is not 0, which "cov_status" tells)."""
+    (PoseSolver.pose_covariance; 0 where cov_status is not 0, which "cov_status" tells), computed with
+    the sigmas times sigma_gain.  calibration: as for evaluate(); the covariance is computed for it whether
+    pose_cov is set or not, and the log entries are those of a run without it."""
     evaluator = SpeedEval(gt_file, solver)
+    cal = _new_calibration(calibration, solver, sigma_gain)
     meters = {}
 
     def log(k, v):
@@ -139,14 +155,43 @@ def evaluate_rtdetr(model, criterion, postprocessors, data_loader, gt_file, solv
         s_t, s_q = device_speed_score(poses["quat"], poses["tvec"], q_gt, t_gt)
         evaluator.update_batch(filenames, outputs["points_px"], outputs["probs"], poses, s_t, s_q, outputs["sigmas"],
                                aux_logits=[a["pred_logits"] for a in aux[:3]])
+        cov = None
         if pose_cov:
-            _log_pred_score(evaluator.log, filenames,
-                            solver.pose_covariance(outputs["probs"], outputs["sigmas"], poses, clip_bbox=clip))
+            cov = solver.pose_covariance(outputs["probs"], outputs["sigmas"], poses, clip_bbox=clip, **_gain_kw(sigma_gain))
+            _log_pred_score(evaluator.log, filenames, cov)
+        if cal is not None:
+            # the accumulator applies the gain itself, to the covariance at gain 1
+            if cov is None or float(sigma_gain) != 1.0:
+                cov = solver.pose_covariance(outputs["probs"], outputs["sigmas"], poses, clip_bbox=clip)
+            cal.update(outputs["points_px"], outputs["probs"], outputs["sigmas"], poses, cov, q_gt, t_gt, s_t, s_q,
+                       clip_bbox=clip)
     evaluator.log = spe_dist.all_gather_log(evaluator.log)
     evaluator.summarize()
     stats = {k: s / max(n, 1) for k, (s, n) in meters.items()}
+    _finish_calibration(cal, stats, evaluator)
     stats["speed_eval_pose"] = evaluator.stats
     return stats, evaluator
+
+
+def _gain_kw(sigma_gain):
+    """pose_covariance's sigma_gain keyword, left out at 1.0: a solver object without the keyword keeps working."""
+    return {} if float(sigma_gain) == 1.0 else {"sigma_gain": float(sigma_gain)}
+
+
+def _new_calibration(calibration, solver, sigma_gain):
+    """The evaluate loops' accumulator: None unless asked for."""
+    if not calibration:
+        return None
+    from .calibration import Calibration
+    return Calibration(sigma_gain=sigma_gain, solver=solver)
+
+
+def _finish_calibration(cal, stats, evaluator):
+    """The summary into the returned stats ("calibration") and one line onto the evaluator's."""
+    if cal is None:
+        return
+    stats["calibration"] = cal.summarize()
+    evaluator.stats += "; " + cal.stats_line(stats["calibration"])
 
 
 def _lens_kw(solver, sigmas, clip):
@@ -196,7 +241,7 @@ def _batch_frames(files, names, decoder, device):
 
 @torch.no_grad()
 def generate_submission(models, postprocessors, anns, read_file, solver, device, batch_size, input_size,
-                        decoder=None, transform=None, pose_cov=False):
+                        decoder=None, transform=None, pose_cov=False, sigma_gain=1.0):
     """The reference's gen_submission loop (REV/gen_submission_single.py:113-187; with a list of
     models, gen_prediction + gen_submission of gen_submission_multi.py:123-186) over SpeedSubmission
     (REV/datasets/speed.py:44-160), from the files' bytes on.
@@ -224,7 +269,8 @@ def generate_submission(models, postprocessors, anns, read_file, solver, device,
 
     pose_cov (a single model with a sigma head, or a list with a SigmaEnsemblePoseSolver, whose fused probs
     and sigmas it then reads): each record also carries "pred_score" and "cov_status"
-    (PoseSolver.pose_covariance on the crop-scaled sigmas); a status-1 crop's are 0 and 1, like its pose."""
+    (PoseSolver.pose_covariance on the crop-scaled sigmas, times sigma_gain, the calibration factor
+    spe.calibration measures); a status-1 crop's are 0 and 1, like its pose."""
     from .datasets import JpegDecoder, SpeedSubmissionTransform
     from .solver import SigmaEnsemblePoseSolver
     multi = isinstance(models, (list, tuple))
@@ -273,7 +319,7 @@ def generate_submission(models, postprocessors, anns, read_file, solver, device,
         if pose_cov:
             if o.get("sigmas") is None:
                 raise ValueError("generate_submission: pose_cov needs a model with a sigma head")
-            cov = solver.pose_covariance(o["probs"], o["sigmas"], poses, clip_bbox=t["clip_bbox"])
+            cov = solver.pose_covariance(o["probs"], o["sigmas"], poses, clip_bbox=t["clip_bbox"], **_gain_kw(sigma_gain))
             bad = t["status"] != 0
             cov["pred_score"] = cov["pred_score"].masked_fill(bad, 0.0)
             cov["cov_status"] = torch.where(bad & (cov["cov_status"] == 0), torch.ones_like(cov["cov_status"]),

@@ -54,13 +54,24 @@ class PosePipeline:
     def __init__(self, model: "DETR | RTDETR", solver: PoseSolver, batch: int, device="cuda", use_graph: bool = False,
                  self_assess: bool = True, overlap: bool = False, raw_frames=None, overlap_decode: bool = False,
                  jpeg_max_bytes: int = 0, overlap_backbone: bool = False, host_input: bool = False,
-                 pose_cov: bool = False):
+                 pose_cov: bool = False, sigma_gain: float = 1.0, calibration=None):
         self.model, self.solver, self.B = model, solver, batch
         self.self_assess = self_assess
         # pose_cov (models with a sigma head): one more launch on the solver's stream after the solve,
         # PoseSolver.pose_covariance; run()'s output then also carries pose_cov [B,6,6], pred_score,
         # sigma_t, sigma_rot and cov_status.  Off: no launch and no key is added.
-        self.pose_cov = pose_cov
+        # sigma_gain: the calibration factor on the sigmas the covariance reads (spe.calibration measures it);
+        # the solver is not touched.  1.0: every output as without it.
+        self.sigma_gain = float(sigma_gain)
+        # calibration (an spe.calibration.Calibration; implies pose_cov): every step appends its batch's
+        # calibration records against the loaded ground truth, one more launch on the solver's stream and no
+        # host synchronisation; run()'s output then carries them under "calibration".
+        # Not with use_graph: a replayed graph runs no Python, so the accumulator would hold the warm-up's and the
+        # capture's batch however many steps ran.
+        if calibration is not None and use_graph:
+            raise ValueError("calibration: eager execution only (a graph replay appends nothing to the accumulator)")
+        self.calibration = calibration
+        self.pose_cov = pose_cov or calibration is not None
         # overlap: the solver / score / self-assessment of batch i run on a second HIP stream
         # while the forward of batch i+1 runs on the caller's stream (the solver occupies one
         # wave per image, far from filling the chip, and its latency is fp64-bound).  Results of
@@ -172,7 +183,16 @@ class PosePipeline:
                 raise ValueError("pose_cov: the model has no sigma head")
             # the model's sigmas are crop-normalised like its points: to pixels by the crop's size
             out.update(self.solver.pose_covariance(fo["probs"], sig, poses, stream=stream,
-                                                   clip_bbox=self.clip_bbox if clip is None else clip))
+                                                   clip_bbox=self.clip_bbox if clip is None else clip,
+                                                   **({} if self.sigma_gain == 1.0 else {"sigma_gain": self.sigma_gain})))
+            if self.calibration is not None:
+                # the records of this batch, with this batch's boxes and ground truth, on the solver's stream;
+                # the accumulator applies its own gain to the covariance at gain 1
+                cov1 = out if self.sigma_gain == 1.0 else self.solver.pose_covariance(
+                    fo["probs"], sig, poses, stream=stream, clip_bbox=self.clip_bbox if clip is None else clip)
+                out["calibration"] = self.calibration.update(
+                    fo["points_px"], fo["probs"], sig, poses, cov1, q_gt, t_gt, s_t, s_q,
+                    clip_bbox=self.clip_bbox if clip is None else clip, stream=stream)
         return out
 
     def _decode(self):

@@ -159,7 +159,7 @@ class PoseSolver:
         out["reliable"] = out["reliable"].bool()
         return out
 
-    def pose_covariance(self, probs, sigmas, poses, clip_bbox=None, sigma_floor=1e-3, stream=None):
+    def pose_covariance(self, probs, sigmas, poses, clip_bbox=None, sigma_floor=1e-3, stream=None, sigma_gain=1.0):
         """First-order covariance of a solve_batch result's poses from the keypoint sigmas (definition:
         include/spe.h spe_pose_covariance).  `poses` is solve_batch's dict of any solver class (status,
         corr_label, inlier_mask, rvec, tvec).  clip_bbox [B,4] (x1, y1, x2, y2): the sigmas are
@@ -168,8 +168,13 @@ class PoseSolver:
         (state order: rotation rad, translation m), sigma_rot [B] f32, sigma_t [B,3] f64, pred_score [B]
         f32 and cov_status [B] i32 (0 ok, 1 no pose, 2 fewer than 3 inliers, 3 bad sigma, 4 singular;
         the numeric outputs of a non-zero status are 0).  Poses solved through a lens carry
-        sigmas_ideal, the sigmas in the image the pose was solved in: those are used."""
+        sigmas_ideal, the sigmas in the image the pose was solved in: those are used.  sigma_gain: a
+        calibration factor on every sigma (spe.calibration measures it), multiplied into the scale -- without
+        a clip_bbox a [B,2] scale of the gain is made; at 1.0 nothing changes, bit for bit."""
         B, Q, C = probs.shape
+        sigma_gain = float(sigma_gain)
+        if not 0 < sigma_gain < float("inf"):
+            raise ValueError(f"sigma_gain must be positive and finite, got {sigma_gain}")
         sigmas = poses.get("sigmas_ideal", sigmas)
         dev = probs.device
         Kd, Wd = self._consts(dev)
@@ -184,6 +189,9 @@ class PoseSolver:
         if clip_bbox is not None:
             # made on the stream the kernel reads it on
             scale = sigma_scale_of(clip_bbox, dev, stream)
+        if sigma_gain != 1.0:
+            with torch.cuda.stream(stream if stream is not None else torch.cuda.current_stream()):
+                scale = scale * sigma_gain if scale is not None else torch.full((B, 2), sigma_gain, device=dev)
         _lib.check(_lib.lib().spe_pose_covariance(
             _lib.stream_ptr(stream), _lib.ptr(probs.contiguous()), _lib.ptr(sigmas.contiguous()), _lib.ptr(scale),
             _lib.ptr(poses["status"]), _lib.ptr(poses["corr_label"]), _lib.ptr(poses["inlier_mask"]),
