@@ -667,6 +667,85 @@ int spe_calibration_records(void* stream, const float* points_px, const float* p
                             const double* K, const double* world, double sigma_gain, double* delta, double* nees,
                             double* z, uint8_t* kp_flags, int32_t* calib_status);
 
+/* Landmark reconstruction: the body-frame 3-D landmarks (the `world` table every entry above reads) from 2-D
+ * keypoint observations in views of known pose.  The paper obtains its table by multi-view triangulation;
+ * that code is not in the reference (it ships the result, all_result.json 'pt'), so this comment is the
+ * definition, all of it in fp64, every step rounded on its own.  All pointers are device memory.
+ *
+ * Observations.  N = num_views, L = num_landmarks (1 <= L <= 16).  obs_px [N,L,2] pixels; obs_sigma [N,L,2]
+ * pixels (nullable: every sigma is 1 px); obs_valid [N,L] u8 (0: no observation); q_gt [N,4] / t_gt [N,3] the
+ * view's pose, R_gt by spe_calibration_records' formula (camera-from-body, X_cam = R_gt X + t_gt); K 3x3
+ * row-major, read as fx = K[0], fy = K[4], cx = K[2], cy = K[5] (no skew).  An observation is skipped -- it
+ * enters no sum and no NaN propagates -- where obs_valid is 0, the view's |q_gt| is zero or not finite, t_gt
+ * is not finite, the point is not finite, or sigma * sigma_gain is not finite on either axis.  Effective sigma
+ * = max(sigma * sigma_gain, sigma_floor) per axis, spe_calibration_records' rule.
+ *
+ * Stage 0, the linear start (skipped when world_init [L,3] is given: that is the start point).  With
+ * u = (px - cx) / fx, v = (py - cy) / fy and r1, r2, r3 the rows of R_gt, a view gives the two rows
+ *     (r1 - u r3) . X = -(t1 - u t3)        weight (fx / sigma_x)^2
+ *     (r2 - v r3) . X = -(t2 - v t3)        weight (fy / sigma_y)^2
+ * summed over the landmark's views into the 3x3 normal matrix A = sum w a a^T and the vector sum w a b, solved
+ * by Cholesky of the Jacobi-scaled D^-1/2 A D^-1/2, D = diag A (chol3_factor / chol3_backsolve of pnp_math.h).
+ *
+ * Stage 1, the refinement: `iterations` Levenberg-Marquardt steps on r = ((px - pi_x) / sigma_x, (py - pi_y)
+ * / sigma_y), pi = (fx x/z + cx, fy y/z + cy) of (x, y, z) = R_gt X + t_gt.  An evaluation at a point X runs
+ * over the landmark's views that are not skipped and have z > z_min (and a finite |r|): the used views.  With
+ * h = huber and |r| the norm of the view's two components, in sigma units: weight w = 1 and rho = |r|^2, or,
+ * where h > 0 and |r| > h, w = h / |r| and rho = 2 h |r| - h^2.  J = d pi / d X over sigma, per axis (2x3):
+ *     Jx = (fx / z / sigma_x) (r1 - (x/z) r3),   Jy = (fy / z / sigma_y) (r2 - (y/z) r3)
+ * H = sum w J^T J, g = sum w J^T r, robust cost = sum rho, n = the number of used views, and sum of
+ * (px - pi_x)^2 + (py - pi_y)^2.  The start point is evaluated first: fewer than 2 used views there is status
+ * 1, otherwise it is the accepted point and lambda = 1e-3.  A step solves (H + lambda diag H) d = g at the
+ * accepted point (Cholesky of D^-1/2 H D^-1/2 + lambda I) and evaluates the candidate X + d: it is accepted,
+ * with lambda / 10, when its robust cost is lower and it uses no fewer views than the accepted point;
+ * otherwise the accepted point, its H and g are kept, with lambda * 10.  The step count is fixed; nothing is
+ * read back between steps.
+ *
+ * Summation.  Every sum over views is taken in one fixed order: view n is lane n % 64 of wave n / 64; a wave's
+ * lanes are joined by the xor butterfly 32, 16, 8, 4, 2, 1 (skipped and absent views contribute 0); the wave
+ * partials w, w + 64, w + 128, .. are added in that order by lane w % 64 of a second wave and joined by the
+ * same butterfly.  No atomics: two runs give the same bits.
+ *
+ * Outputs, at the accepted point: world [L,3]; cov [L,3,3] = H^-1 (Cholesky of the Jacobi-scaled H, unscaled
+ * afterwards, symmetric, fully written; not multiplied by chi2); chi2 [L] = the robust cost; n_used [L] i32;
+ * rms_px [L] = sqrt(sum((px - pi_x)^2 + (py - pi_y)^2) / n), unweighted; obs_flags [N,L] u8: bit 0 the
+ * observation is used at the final point, bit 1 it is beyond the Huber threshold there (h > 0 and |r| > h;
+ * only with bit 0).  lm_status [L], the first that applies:
+ *     0 ok
+ *     1 fewer than 2 usable views (stage 0: not skipped; the start point's evaluation: used)
+ *     2 degenerate: a diagonal of a matrix to factor that is not positive and finite, or a pivot of the
+ *       scaled matrix <= 64 * DBL_EPSILON (rays parallel, identical poses)
+ *     3 a start point, candidate or result that is not finite
+ * For a non-zero status the landmark's world, cov, chi2, n_used and rms_px are 0, its obs_flags are 0, and it
+ * takes no part in later launches: no NaN leaves the kernels.
+ *
+ * spe_landmarks_solve launches stage 0 (2 launches), iterations + 1 evaluate / update pairs and the flags
+ * kernel on `stream`; no allocation, no synchronisation; it works in `scratch`, caller-owned device memory,
+ * 8-byte aligned, of at least spe_landmarks_scratch_bytes(num_views, num_landmarks) bytes (0 for arguments
+ * out of range), whose contents mean nothing between calls.  SPE_E_ARG before any launch: a null required
+ * pointer, num_views < 1, num_landmarks outside [1, 16], iterations outside [0, 64], sigma_floor or sigma_gain
+ * not positive and finite; SPE_E_WORKSPACE: a scratch misaligned or too small.  huber <= 0 switches the
+ * robust weight off.
+ *
+ * spe_landmark_observations turns model output into the observation layout, one launch, one wave per image:
+ * for landmark l (0 <= l < L = num_classes - 1) the query is the one the solver's selection gives the label
+ * (highest score, the first on ties; the same code as spe_pnp_batch and spe_calibration_records).  Image b is
+ * written at row row_offset + b of obs_px / obs_sigma / obs_valid [rows,L,.]: obs_px = the query's point;
+ * obs_sigma (nullable) = sigmas * sigma_scale, the fp64 product, sigmas [B,Q,2] and sigma_scale [B,2] as
+ * spe_pose_covariance takes them (sigmas null: 1; sigma_scale null: the sigmas are pixels); obs_valid = 1.
+ * A label no query carries gives point 0, sigma 1, obs_valid 0.  num_queries <= 64, 2 <= num_classes <= 17,
+ * batch >= 1, row_offset >= 0, else SPE_E_ARG before any launch. */
+int spe_landmark_observations(void* stream, const float* points_px, const float* probs, const float* sigmas,
+                              const float* sigma_scale, int batch, int num_queries, int num_classes,
+                              int64_t row_offset, double* obs_px, double* obs_sigma, uint8_t* obs_valid);
+int64_t spe_landmarks_scratch_bytes(int num_views, int num_landmarks);
+int spe_landmarks_solve(void* stream, const double* obs_px, const double* obs_sigma, const uint8_t* obs_valid,
+                        const double* q_gt, const double* t_gt, int num_views, int num_landmarks, const double* K,
+                        const double* world_init, int iterations, double huber, double sigma_floor,
+                        double sigma_gain, double z_min, void* scratch, int64_t scratch_bytes, double* world,
+                        double* cov, double* chi2, int32_t* n_used, double* rms_px, uint8_t* obs_flags,
+                        int32_t* lm_status);
+
 /* speed_score per image (REV/utils/speed_eval.py:245-262), device pointers. */
 int spe_speed_score(void* stream, const float* quat, const double* tvec, const double* q_gt, const double* t_gt,
                     int batch, double* s_t, double* s_q);

@@ -1,6 +1,6 @@
 // C entry points of the native runtime outside the model's forward pass (include/spe.h): the set
 // criterion, ensemble fusion, pre- and post-processing, the batched solver, its self-assessment, the pose
-// covariance, the calibration records and the SPEED score.  No allocation or synchronisation happens
+// covariance, the calibration records, the landmark reconstruction and the SPEED score.  No allocation or synchronisation happens
 // inside spe_pnp_batch / spe_pnp_exhaustive / spe_speed_score once the per-stream scratch has its size,
 // so a caller may capture them into a hipGraph.
 #include <hip/hip_runtime.h>
@@ -276,6 +276,43 @@ int spe_calibration_records(void* stream, const float* points_px, const float* p
   CalibArgs a{points_px, probs, sigmas, sigma_scale, sigma_floor, status, corr_label, inlier_mask, rvec, tvec, q_gt,
               t_gt, cov, cov_status, B, Q, C, K, world, sigma_gain, delta, nees, z, kp_flags, calib_status};
   CK(spe_launch_calib_records(a, (hipStream_t)stream));
+  return 0;
+}
+
+int spe_landmark_observations(void* stream, const float* points_px, const float* probs, const float* sigmas,
+                              const float* sigma_scale, int batch, int num_queries, int num_classes,
+                              int64_t row_offset, double* obs_px, double* obs_sigma, uint8_t* obs_valid) {
+  if (!points_px || !probs || !obs_px || !obs_valid || batch < 1 || num_queries <= 0 || num_queries > 64 ||
+      num_classes < 2 || num_classes > 17 || row_offset < 0)
+    return fail(SPE_E_ARG, "bad argument");
+  LandmarkObsArgs a{points_px, probs, sigmas, sigma_scale, batch, num_queries, num_classes, (size_t)row_offset,
+                    obs_px, obs_sigma, obs_valid};
+  CK(spe_launch_landmark_observations(a, (hipStream_t)stream));
+  return 0;
+}
+
+int64_t spe_landmarks_scratch_bytes(int num_views, int num_landmarks) {
+  return (int64_t)spe_landmarks_scratch_size(num_views, num_landmarks);
+}
+
+int spe_landmarks_solve(void* stream, const double* obs_px, const double* obs_sigma, const uint8_t* obs_valid,
+                        const double* q_gt, const double* t_gt, int num_views, int num_landmarks, const double* K,
+                        const double* world_init, int iterations, double huber, double sigma_floor,
+                        double sigma_gain, double z_min, void* scratch, int64_t scratch_bytes, double* world,
+                        double* cov, double* chi2, int32_t* n_used, double* rms_px, uint8_t* obs_flags,
+                        int32_t* lm_status) {
+  if (!obs_px || !obs_valid || !q_gt || !t_gt || !K || !scratch || !world || !cov || !chi2 || !n_used || !rms_px ||
+      !obs_flags || !lm_status || num_views < 1 || num_landmarks < 1 || num_landmarks > 16)
+    return fail(SPE_E_ARG, "bad argument");
+  if (iterations < 0 || iterations > 64) return fail(SPE_E_ARG, "iterations must be in [0, 64]");
+  if (!(sigma_floor > 0) || !(sigma_floor < (double)INFINITY)) return fail(SPE_E_ARG, "sigma_floor must be positive and finite");
+  if (!(sigma_gain > 0) || !(sigma_gain < (double)INFINITY)) return fail(SPE_E_ARG, "sigma_gain must be positive and finite");
+  if (((uintptr_t)scratch & 7) != 0 || scratch_bytes < spe_landmarks_scratch_bytes(num_views, num_landmarks))
+    return fail(SPE_E_WORKSPACE, "scratch misaligned or below spe_landmarks_scratch_bytes");
+  LandmarkArgs a{obs_px, obs_sigma, obs_valid, q_gt, t_gt, num_views, num_landmarks, K, world_init, iterations,
+                 huber, sigma_floor, sigma_gain, z_min, scratch, world, cov, chi2, n_used, rms_px, obs_flags,
+                 lm_status};
+  CK(spe_launch_landmarks_solve(a, (hipStream_t)stream));
   return 0;
 }
 

@@ -1241,3 +1241,42 @@ __device__ __forceinline__ void chol6_backsolve(const double (*L)[6], const doub
     x[i] = t / L[i][i];
   }
 }
+
+// 3x3 analogue of chol6_factor / chol6_backsolve, built the same way (calib.hip, landmarks.hip)
+__device__ __forceinline__ bool chol3_factor(const double* S, double thr, double (*L)[3]) {
+#pragma unroll
+  for (int j = 0; j < 3; ++j) {
+    double s = S[j * 3 + j];
+#pragma unroll
+    for (int p = 0; p < j; ++p) s -= L[j][p] * L[j][p];
+    if (!(s > thr)) return false;
+    L[j][j] = sqrt(s);
+    const double inv = 1.0 / L[j][j];
+#pragma unroll
+    for (int i = j + 1; i < 3; ++i) {
+      double t = S[i * 3 + j];
+#pragma unroll
+      for (int p = 0; p < j; ++p) t -= L[i][p] * L[j][p];
+      L[i][j] = t * inv;
+    }
+  }
+  return true;
+}
+
+__device__ __forceinline__ void chol3_backsolve(const double (*L)[3], const double* b, double* x) {
+  double y[3];
+#pragma unroll
+  for (int i = 0; i < 3; ++i) {
+    double t = b[i];
+#pragma unroll
+    for (int p = 0; p < i; ++p) t -= L[i][p] * y[p];
+    y[i] = t / L[i][i];
+  }
+#pragma unroll
+  for (int i = 2; i >= 0; --i) {
+    double t = y[i];
+#pragma unroll
+    for (int p = i + 1; p < 3; ++p) t -= L[p][i] * x[p];
+    x[i] = t / L[i][i];
+  }
+}

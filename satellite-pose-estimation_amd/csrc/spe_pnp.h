@@ -112,5 +112,42 @@ struct CalibArgs {
   int32_t* calib_status;      // [B]
 };
 int spe_launch_calib_records(const CalibArgs& a, hipStream_t s);
+
+// Landmark reconstruction from posed observations (include/spe.h spe_landmarks_solve; csrc/landmarks.hip)
+struct LandmarkObsArgs {
+  const float* points;        // [B][Q][2] px
+  const float* probs;         // [B][Q][C]
+  const float* sigmas;        // [B][Q][2] or null
+  const float* sigma_scale;   // [B][2] or null
+  int B, Q, C;
+  size_t row_offset;          // image b is written at row row_offset + b
+  double* obs_px;             // [rows][C-1][2]
+  double* obs_sigma;          // [rows][C-1][2] or null
+  uint8_t* obs_valid;         // [rows][C-1]
+};
+int spe_launch_landmark_observations(const LandmarkObsArgs& a, hipStream_t s);
+
+struct LandmarkArgs {
+  const double* obs_px;       // [N][L][2]
+  const double* obs_sigma;    // [N][L][2] or null: 1 px
+  const uint8_t* obs_valid;   // [N][L]
+  const double* q_gt;         // [N][4]
+  const double* t_gt;         // [N][3]
+  int N, L;
+  const double* K;            // 3x3 row-major
+  const double* world_init;   // [L][3] or null
+  int iterations;
+  double huber, sigma_floor, sigma_gain, z_min;
+  void* scratch;              // spe_landmarks_scratch_bytes(N, L)
+  double* world;              // [L][3]
+  double* cov;                // [L][3][3]
+  double* chi2;               // [L]
+  int32_t* n_used;            // [L]
+  double* rms_px;             // [L]
+  uint8_t* obs_flags;         // [N][L]
+  int32_t* lm_status;         // [L]
+};
+size_t spe_landmarks_scratch_size(int N, int L);
+int spe_launch_landmarks_solve(const LandmarkArgs& a, hipStream_t s);
 int spe_launch_score(const float* quat, const double* tvec, const double* q_gt, const double* t_gt, int B,
                      double* s_t, double* s_q, hipStream_t s);

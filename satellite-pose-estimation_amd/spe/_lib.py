@@ -53,7 +53,7 @@ SPE_PNP_OK, SPE_PNP_NO_FG, SPE_PNP_CV_ERROR, SPE_PNP_RANSAC_FALLBACK, SPE_PNP_UN
 # every symbol include/spe.h declares (checked by tests/test_capi.py)
 EXPORTS = ["spe_abi_version", "spe_last_error", "spe_model_create", "spe_model_create_backbone", "spe_model_create_flags", "spe_model_destroy", "spe_model_set_param",
            "spe_model_num_params", "spe_model_param_name", "spe_model_finalize", "spe_model_workspace_bytes",
-           "spe_forward", "spe_forward_stages", "spe_forward_stages_u8", "spe_preprocess", "spe_preprocess_submission", "spe_criterion", "spe_criterion_sigma", "spe_ensemble_fuse", "spe_ensemble_fuse_sigma", "spe_undistort_points", "spe_distort_points", "spe_postprocess", "spe_pnp_batch", "spe_pnp_exhaustive", "spe_debug_pnp_exhaustive_stages", "spe_self_assess", "spe_pose_covariance", "spe_calibration_records", "spe_speed_score", "spe_model_profile_begin",
+           "spe_forward", "spe_forward_stages", "spe_forward_stages_u8", "spe_preprocess", "spe_preprocess_submission", "spe_criterion", "spe_criterion_sigma", "spe_ensemble_fuse", "spe_ensemble_fuse_sigma", "spe_undistort_points", "spe_distort_points", "spe_postprocess", "spe_pnp_batch", "spe_pnp_exhaustive", "spe_debug_pnp_exhaustive_stages", "spe_self_assess", "spe_pose_covariance", "spe_calibration_records", "spe_landmark_observations", "spe_landmarks_scratch_bytes", "spe_landmarks_solve", "spe_speed_score", "spe_model_profile_begin",
            "spe_model_profile_end", "spe_model_profile_get", "spe_debug_gemm", "spe_debug_gemm_path", "spe_debug_gemm_h3", "spe_debug_ffn_h3", "spe_debug_ffn_h3_perm", "spe_debug_gemm_planes", "spe_debug_attention",
            "spe_debug_layernorm", "spe_debug_ffn", "spe_debug_xattn", "spe_debug_xattn_h3", "spe_debug_upconv", "spe_debug_btail", "spe_debug_decsa", "spe_debug_decproj", "spe_debug_decxproj", "spe_debug_wfrag_pack", "spe_debug_decffn", "spe_debug_decq", "spe_debug_btail_perm", "spe_debug_btail_rows", "spe_debug_btail_row_perm", "spe_debug_btail_wide", "spe_debug_btail_wide_proj", "spe_debug_btail_wide_perm", "spe_debug_stempool", "spe_rtdetr_create", "spe_rtdetr_forward",
            "spe_rtdetr_forward_stages", "spe_rtdetr_forward_stages_u8",
@@ -145,6 +145,10 @@ def load(path: str):
     L.spe_self_assess.argtypes = [P, P, P, P, P, P, I, I, I, F, F, I, P, P, P]
     L.spe_pose_covariance.argtypes = [P] + [P] * 8 + [I, I, I, P, P, F] + [P] * 5
     L.spe_calibration_records.argtypes = [P] + [P] * 4 + [F] + [P] * 9 + [I, I, I, P, P, D] + [P] * 5
+    L.spe_landmark_observations.argtypes = [P] + [P] * 4 + [I, I, I, I64, P, P, P]
+    L.spe_landmarks_scratch_bytes.argtypes = [I, I]
+    L.spe_landmarks_scratch_bytes.restype = I64
+    L.spe_landmarks_solve.argtypes = [P] + [P] * 5 + [I, I, P, P, I, D, D, D, D, P, I64] + [P] * 7
     L.spe_model_profile_begin.argtypes = [P, ctypes.c_char_p]
     L.spe_model_profile_end.argtypes = [P]
     L.spe_model_profile_get.argtypes = [P, I, ctypes.c_char_p, I, ctypes.POINTER(D), ctypes.POINTER(D),

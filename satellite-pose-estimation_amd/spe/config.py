@@ -139,6 +139,21 @@ def world_points() -> np.ndarray:
         return np.asarray(json.load(f)["points"], dtype=np.float64)
 
 
+def load_world(world=None) -> np.ndarray:
+    """A landmark table [L,3] fp64, 1 <= L <= 16, from what a solver's world= takes: None (the packaged
+    world_points()), a path to a JSON file in world_points.json's layout ({"points": ...}), an array, or an
+    object with .points (spe.landmarks.LandmarkModel)."""
+    if world is None:
+        return world_points()
+    if isinstance(world, (str, os.PathLike)):
+        with open(world) as f:
+            world = json.load(f)["points"]
+    w = np.array(getattr(world, "points", world), dtype=np.float64)
+    if w.ndim != 2 or w.shape[1] != 3 or not 1 <= w.shape[0] <= 16 or not np.isfinite(w).all():
+        raise ValueError(f"a landmark table is [L,3] finite numbers with 1 <= L <= 16, got shape {w.shape}")
+    return w
+
+
 def quat_to_matrix(q) -> np.ndarray:
     """Rotation matrix of a (w, x, y, z) quaternion, `mathutils.Quaternion(q).to_matrix()`
     convention (used by REV/utils/utils.py:49-53 to project landmarks)."""

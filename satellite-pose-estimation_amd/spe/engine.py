@@ -48,8 +48,12 @@ def _log_losses(ld, weight_dict, device, log):
 
 @torch.no_grad()
 def evaluate(model, criterion, postprocessors, data_loader, gt_file, solver, device, output_dir=None,
-             calibration=False, sigma_gain=1.0):
-    """calibration (a model with a sigma head): the keypoint sigmas, the pose covariance and its predicted score are
+             calibration=False, sigma_gain=1.0, landmarks=None):
+    """landmarks (a spe.landmarks.LandmarkReconstruction, None: nothing changes): every batch's keypoints,
+    their sigmas and ground-truth poses are added to it (update(), one launch, no synchronisation); the caller
+    runs landmarks.solve() afterwards.
+
+    calibration (a model with a sigma head): the keypoint sigmas, the pose covariance and its predicted score are
     compared with the ground truth over the whole set (spe.calibration.Calibration at sigma_gain); the returned
     stats then carry the summary dict under "calibration" and evaluator.stats one more line.  With several ranks
     the log is gathered but the calibration is not: each rank's summary and line cover the images it evaluated."""
@@ -95,6 +99,8 @@ def evaluate(model, criterion, postprocessors, data_loader, gt_file, solver, dev
         sig = outputs.get("sigmas")
         assess = solver.self_assess(outputs["probs"], sig, poses) if sig is not None else None
         evaluator.update_batch(filenames, outputs["points_px"], outputs["probs"], poses, s_t, s_q, sig, assess)
+        if landmarks is not None:
+            _update_landmarks(landmarks, outputs, q_gt, t_gt, clip)
         if cal is not None:
             if sig is None:
                 raise ValueError("evaluate: calibration needs a model with a sigma head")
@@ -111,7 +117,7 @@ def evaluate(model, criterion, postprocessors, data_loader, gt_file, solver, dev
 
 @torch.no_grad()
 def evaluate_rtdetr(model, criterion, postprocessors, data_loader, gt_file, solver, device, output_dir=None,
-                    pose_cov=False, sigma_gain=1.0, calibration=False):
+                    pose_cov=False, sigma_gain=1.0, calibration=False, landmarks=None):
     """The UNC RT-DETR evaluation loop (UNC/solver/speed_engine.py:123-202) with evaluate()'s
     interface.  Per batch: one device pass (RTDETR.forward with clip_bbox, so RTDETRPostProcessor
     runs fused; `postprocessors` is accepted for the reference's signature), the device criterion
@@ -126,7 +132,7 @@ def evaluate_rtdetr(model, criterion, postprocessors, data_loader, gt_file, solv
     "pred_score", the pose covariance's first-order prediction of the image's score
     (PoseSolver.pose_covariance; 0 where cov_status is not 0, which "cov_status" tells), computed with
     the sigmas times sigma_gain.  calibration: as for evaluate(); the covariance is computed for it whether
-    pose_cov is set or not, and the log entries are those of a run without it."""
+    pose_cov is set or not, and the log entries are those of a run without it.  landmarks: as for evaluate()."""
     evaluator = SpeedEval(gt_file, solver)
     cal = _new_calibration(calibration, solver, sigma_gain)
     meters = {}
@@ -155,6 +161,8 @@ def evaluate_rtdetr(model, criterion, postprocessors, data_loader, gt_file, solv
         s_t, s_q = device_speed_score(poses["quat"], poses["tvec"], q_gt, t_gt)
         evaluator.update_batch(filenames, outputs["points_px"], outputs["probs"], poses, s_t, s_q, outputs["sigmas"],
                                aux_logits=[a["pred_logits"] for a in aux[:3]])
+        if landmarks is not None:
+            _update_landmarks(landmarks, outputs, q_gt, t_gt, clip)
         cov = None
         if pose_cov:
             cov = solver.pose_covariance(outputs["probs"], outputs["sigmas"], poses, clip_bbox=clip, **_gain_kw(sigma_gain))
@@ -176,6 +184,15 @@ def evaluate_rtdetr(model, criterion, postprocessors, data_loader, gt_file, solv
 def _gain_kw(sigma_gain):
     """pose_covariance's sigma_gain keyword, left out at 1.0: a solver object without the keyword keeps working."""
     return {} if float(sigma_gain) == 1.0 else {"sigma_gain": float(sigma_gain)}
+
+
+def _update_landmarks(rec, outputs, q_gt, t_gt, clip):
+    """One batch into a LandmarkReconstruction: the model's sigmas are crop-normalised, the crop's size is
+    their scale."""
+    from .solver import sigma_scale_of
+    sig = outputs.get("sigmas")
+    rec.update(outputs["points_px"], outputs["probs"], sig, q_gt, t_gt,
+               sigma_scale=sigma_scale_of(clip, clip.device) if sig is not None else None)
 
 
 def _new_calibration(calibration, solver, sigma_gain):

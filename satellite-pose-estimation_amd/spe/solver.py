@@ -20,7 +20,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .config import Camera, LensModel, world_points
+from .config import Camera, LensModel, load_world
 
 MODES = {"epnp": _lib.SPE_PNP_EPNP, "ransac_p3p_lm": _lib.SPE_PNP_RANSAC_P3P_LM,
          "epnp_ransac_sigma": _lib.SPE_PNP_EPNP_RANSAC_SIGMA, "epnp_lm": _lib.SPE_PNP_EPNP_LM,
@@ -43,10 +43,14 @@ def sigma_scale_of(clip_bbox, device, stream=None):
 class PoseSolver:
     """Holds the 11 world landmarks (REV/utils/speed_eval.py:28-39) and camera K.  lens (a
     spe.config.LensModel, None: a pinhole camera): its K replaces Camera.K, and solve_batch first maps
-    the points and sigmas to the ideal image (undistort)."""
+    the points and sigmas to the ideal image (undistort).  world (spe.config.load_world: an [L,3] array, a
+    world_points.json-style file or a spe.landmarks.LandmarkModel; None: the packaged SPEED table): the
+    landmarks every entry of this solver reads."""
 
-    def __init__(self, mode=_lib.SPE_PNP_RANSAC_P3P_LM, repro=20.0, ransac_iters=100, confidence=0.99, lens=None):
-        self.W_Pt = world_points()
+    def __init__(self, mode=_lib.SPE_PNP_RANSAC_P3P_LM, repro=20.0, ransac_iters=100, confidence=0.99, lens=None,
+                 world=None):
+        self.W_Pt = load_world(world)
+        self._own_world = world is not None
         self.K = Camera.K.copy()
         self.mode = mode
         self.reprojectionError = float(repro)
@@ -64,6 +68,18 @@ class PoseSolver:
         self._dev = {}
         self._lens_dist = {}
         self._lens_buf = {}
+
+    def set_world(self, world):
+        """Installs another landmark table (load_world); the device constants are made again."""
+        self.W_Pt = load_world(world)
+        self._own_world = world is not None
+        self._dev = {}
+
+    def _check_world(self, C):
+        """A table given by the caller must cover the model's landmark classes (the kernels read C - 1 rows)."""
+        if self._own_world and C - 1 > self.W_Pt.shape[0]:
+            raise ValueError(f"solve_batch: {C} classes need {C - 1} landmarks, the solver's table holds "
+                             f"{self.W_Pt.shape[0]}")
 
     def undistort(self, points_px, sigmas=None, sigma_scale=None, stream=None):
         """The lens step (include/spe.h spe_undistort_points), one launch: points_px [N,Q,2] distorted
@@ -122,6 +138,7 @@ class PoseSolver:
         B, Q, C = probs.shape
         dev = probs.device
         Kd, Wd = self._consts(dev)
+        self._check_world(C)
         ideal = {}
         if self.lens is not None and not undistorted and B > 0:
             points_px, sigmas, ideal = self._lens_step(points_px, sigmas, sigma_scale, stream)
@@ -225,16 +242,16 @@ class SimplePoseSolver(PoseSolver):
     """cv2.solvePnPRansac(P3P, reprojectionError=args.repro) + solvePnPGeneric(ITERATIVE)
     (REV/utils/speed_eval.py:143-242)."""
 
-    def __init__(self, args=None, lens=None):
+    def __init__(self, args=None, lens=None, world=None):
         super().__init__(_lib.SPE_PNP_RANSAC_P3P_LM, getattr(args, "repro", 20) if args is not None else 20,
-                         lens=lens)
+                         lens=lens, world=world)
 
 
 class SimplePoseSolverSigma(PoseSolver):
     """EPnP-RANSAC (reprojection 25) + sigma-weighted Huber LM (UNC/utils/speed_eval.py:322-420)."""
 
-    def __init__(self, args=None, lens=None):
-        super().__init__(_lib.SPE_PNP_EPNP_RANSAC_SIGMA, 25.0, lens=lens)
+    def __init__(self, args=None, lens=None, world=None):
+        super().__init__(_lib.SPE_PNP_EPNP_RANSAC_SIGMA, 25.0, lens=lens, world=world)
 
 
 class EPnPSolver(PoseSolver):
@@ -242,8 +259,8 @@ class EPnPSolver(PoseSolver):
     BASELINE config 2 ("EPnP only, no RANSAC").  inlier_mask: epnp_init's set, reprojection error
     < reprojectionError."""
 
-    def __init__(self, args=None, refine=False, lens=None):
-        super().__init__(_lib.SPE_PNP_EPNP_LM if refine else _lib.SPE_PNP_EPNP, 20.0, lens=lens)
+    def __init__(self, args=None, refine=False, lens=None, world=None):
+        super().__init__(_lib.SPE_PNP_EPNP_LM if refine else _lib.SPE_PNP_EPNP, 20.0, lens=lens, world=world)
 
 
 class EPnPCeresSolver(PoseSolver):
@@ -252,8 +269,8 @@ class EPnPCeresSolver(PoseSolver):
     sigma-weighted Huber(0.001) LM on the inliers, and the EPnP pose kept when the refined error
     sum over all points is larger.  A batch carries one threshold per image."""
 
-    def __init__(self, input_size=256, lens=None):
-        super().__init__(_lib.SPE_PNP_EPNP_CERES, 20.0, lens=lens)
+    def __init__(self, input_size=256, lens=None, world=None):
+        super().__init__(_lib.SPE_PNP_EPNP_CERES, 20.0, lens=lens, world=world)
         self.input_size = input_size
 
     def repro_th(self, area):
@@ -302,11 +319,11 @@ class ExhaustivePoseSolver(PoseSolver):
     revert-if-worse; the candidate with the smallest error sum wins.  Draws no samples: the result is a
     function of the correspondences alone.  What is unpinned: include/spe.h, SPE_PNP_EXHAUSTIVE."""
 
-    def __init__(self, topk=10, input_size=256, repro=20.0, lens=None):
+    def __init__(self, topk=10, input_size=256, repro=20.0, lens=None, world=None):
         topk = int(topk)
         if not 1 <= topk <= 64:
             raise ValueError(f"topk must be in [1, 64], got {topk}")
-        super().__init__(_lib.SPE_PNP_EXHAUSTIVE, repro, lens=lens)
+        super().__init__(_lib.SPE_PNP_EXHAUSTIVE, repro, lens=lens, world=world)
         self.topk = topk
         self.input_size = input_size
 
@@ -322,6 +339,7 @@ class ExhaustivePoseSolver(PoseSolver):
         B, Q, C = probs.shape
         dev = probs.device
         Kd, Wd = self._consts(dev)
+        self._check_world(C)
         ideal = {}
         if self.lens is not None and not undistorted and B > 0:
             points_px, sigmas, ideal = self._lens_step(points_px, sigmas, sigma_scale, stream)
@@ -366,9 +384,9 @@ class Multi_Mean_PoseSolver(PoseSolver):
     (spe_ensemble_fuse) and solved like SimplePoseSolver (P3P-RANSAC + LM).  With a lens every model's
     points are undistorted before the fusion, in one launch over [M * B, Q]."""
 
-    def __init__(self, args=None, lens=None):
+    def __init__(self, args=None, lens=None, world=None):
         super().__init__(_lib.SPE_PNP_RANSAC_P3P_LM, getattr(args, "repro", 25) if args is not None else 25,
-                         lens=lens)
+                         lens=lens, world=world)
 
     def fuse_batch(self, multi_points_px, multi_probs, stream=None):
         """lists of M device tensors [B,Q,2] / [B,Q,C] -> fused points [B,C-1,2], probs [B,C-1,C]."""
@@ -409,12 +427,15 @@ class SigmaEnsemblePoseSolver:
     model's.  With a lens every model's points and sigmas are undistorted before the fusion, in one launch
     over [M * B, Q], and the fused arrays are ideal.  The lens is the backend's.  lens=: NOTE that it is
     installed ON THE BACKEND OBJECT passed in (set_lens: its K is replaced and it undistorts from then on,
-    also when called directly); a backend that already holds another lens is refused."""
+    also when called directly); a backend that already holds another lens is refused.  world=: a landmark
+    table, installed on the backend object too (set_world)."""
 
-    def __init__(self, backend=None, gate=3.0, sigma_floor=1e-3, lens=None):
+    def __init__(self, backend=None, gate=3.0, sigma_floor=1e-3, lens=None, world=None):
         self.backend = backend if backend is not None else SimplePoseSolverSigma()
         if not hasattr(self.backend, "solve_batch"):
             raise ValueError("SigmaEnsemblePoseSolver: the backend must be a solver object (solve_batch)")
+        if world is not None:
+            self.backend.set_world(world)      # like lens=: installed on the backend object
         if lens is not None:
             if getattr(self.backend, "lens", None) not in (None, lens):
                 raise ValueError("SigmaEnsemblePoseSolver: the backend already holds a different lens")
@@ -499,6 +520,13 @@ class SigmaEnsemblePoseSolver:
         poses["fused"] = fused
         return poses
 
+    def set_world(self, world):
+        self.backend.set_world(world)
+
+    @property
+    def W_Pt(self):
+        return self.backend.W_Pt
+
     def self_assess(self, probs, sigmas, poses, **kw):
         return self.backend.self_assess(probs, sigmas, poses, **kw)
 
@@ -510,9 +538,11 @@ def build_solver(args=None):
     """REV/utils/speed_eval.py:21-22 (SimplePoseSolver); `args.solver` selects the variant.
     "ensemble_sigma" wraps the solver `args.backend` names (epnp_ransac_sigma by default) in a
     SigmaEnsemblePoseSolver with `args.gate` / `args.sigma_floor`.  `args.dist` (4 or 5 OpenCV distortion
-    coefficients), when present, gives the solver a lens (LensModel.from_args)."""
+    coefficients), when present, gives the solver a lens (LensModel.from_args); `args.world` (a path to a
+    world_points.json-style file, an [L,3] array or a LandmarkModel) its landmark table (load_world)."""
     name = getattr(args, "solver", "ransac_p3p_lm") if args is not None else "ransac_p3p_lm"
     lens = LensModel.from_args(args) if getattr(args, "dist", None) is not None else None
+    world = getattr(args, "world", None)
     if name == "ensemble_sigma":
         import argparse
         backend = getattr(args, "backend", "epnp_ransac_sigma")
@@ -522,14 +552,14 @@ def build_solver(args=None):
         return SigmaEnsemblePoseSolver(build_solver(inner), getattr(args, "gate", 3.0),
                                        getattr(args, "sigma_floor", 1e-3))
     if name == "ransac_p3p_lm":
-        return SimplePoseSolver(args, lens=lens)
+        return SimplePoseSolver(args, lens=lens, world=world)
     if name == "epnp_ransac_sigma":
-        return SimplePoseSolverSigma(args, lens=lens)
+        return SimplePoseSolverSigma(args, lens=lens, world=world)
     if name in ("epnp", "epnp_lm"):
-        return EPnPSolver(args, refine=name == "epnp_lm", lens=lens)
+        return EPnPSolver(args, refine=name == "epnp_lm", lens=lens, world=world)
     if name == "epnp_ceres":
-        return EPnPCeresSolver(getattr(args, "input_size", 256) if args is not None else 256, lens=lens)
+        return EPnPCeresSolver(getattr(args, "input_size", 256) if args is not None else 256, lens=lens, world=world)
     if name == "exhaustive":
         return ExhaustivePoseSolver(getattr(args, "topk", 10), getattr(args, "input_size", 256),
-                                    getattr(args, "repro", 20.0), lens=lens)
+                                    getattr(args, "repro", 20.0), lens=lens, world=world)
     raise ValueError(f"unknown solver {name}")
