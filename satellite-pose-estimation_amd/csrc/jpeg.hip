@@ -340,7 +340,9 @@ __global__ __launch_bounds__(64) void jpeg_unstuff_scan_kernel(const int64_t* __
   for (int i = last + 1; i < nt; ++i) tl[3 * i + 2] = -1;        // past the end: nothing to write
   im.ulen = kept;
   im.nseg = rst + 1;
-  if (rst + 1 > ws.max_seg) im.status = ST_CAPACITY;
+  // max_seg is nblocks + 1: a stream with more restart markers than blocks is corrupt like one
+  // with exactly as many (jpeg_segments_kernel), not a file too large for its slot
+  if (rst + 1 > ws.max_seg) im.status = ST_CORRUPT;
 }
 
 // pass 2: write the kept bytes and the restart positions (segment starts)
