@@ -13,8 +13,9 @@ same pieces, with spe.rtdetr.SetCriterion and the reference's extra log fields.
 generate_submission() is the reference's gen_submission loop (REV/gen_submission_single.py:113-187,
 gen_submission_multi.py:123-186) from the JPEG files' bytes to the {filename: pose} log.
 
-A camera with lens distortion comes with the solver (spe.solver, lens=): the three loops hand it the
-crop's size as the sigmas' scale and everything downstream reads the undistorted keypoints.
+What follows the model in the three loops is spe.poststage.PostStage.  A camera with lens distortion comes
+with the solver (spe.solver, lens=): the stage hands it the crop's size as the sigmas' scale and everything
+downstream reads the undistorted keypoints.
 """
 from __future__ import annotations
 
@@ -25,6 +26,7 @@ import torch
 
 from . import _lib
 from . import dist as spe_dist
+from .poststage import PostStage
 from .speed_eval import SpeedEval, device_speed_score
 
 
@@ -46,20 +48,18 @@ def _log_losses(ld, weight_dict, device, log):
     log("class_error", ld["class_error"])
 
 
-@torch.no_grad()
-def evaluate(model, criterion, postprocessors, data_loader, gt_file, solver, device, output_dir=None,
-             calibration=False, sigma_gain=1.0, landmarks=None):
-    """landmarks (a spe.landmarks.LandmarkReconstruction, None: nothing changes): every batch's keypoints,
-    their sigmas and ground-truth poses are added to it (update(), one launch, no synchronisation); the caller
-    runs landmarks.solve() afterwards.
-
-    calibration (a model with a sigma head): the keypoint sigmas, the pose covariance and its predicted score are
-    compared with the ground truth over the whole set (spe.calibration.Calibration at sigma_gain); the returned
-    stats then carry the summary dict under "calibration" and evaluator.stats one more line.  With several ranks
-    the log is gathered but the calibration is not: each rank's summary and line cover the images it evaluated."""
+def _evaluate(model, criterion, data_loader, gt_file, solver, device, calibration, sigma_gain, landmarks, *,
+              box_areas, self_assess, unc_log, pose_cov):
+    """The loop of evaluate() and evaluate_rtdetr().  What the two differ in: box_areas (the Ceres-style solver's
+    per-image thresholds from the ground-truth box areas, checked up front), self_assess (run it on a model with
+    sigmas), unc_log (the UNC log's three aux_outputs entries) and pose_cov (pred_score / cov_status per record)."""
     evaluator = SpeedEval(gt_file, solver)
-    cal = _new_calibration(calibration, solver, sigma_gain)
-    ceres = getattr(solver, "mode", None) == _lib.SPE_PNP_EPNP_CERES
+    cal = None
+    if calibration:
+        from .calibration import Calibration
+        cal = Calibration(sigma_gain=sigma_gain, solver=solver)
+    post = PostStage(solver, self_assess, pose_cov, sigma_gain, cal, landmarks, score=device_speed_score)
+    ceres = box_areas and getattr(solver, "mode", None) == _lib.SPE_PNP_EPNP_CERES
     if ceres:
         # EPnPCeresSolver's per-image thresholds come from the ground-truth box areas: refuse up front a
         # ground truth without them (load_ground_truth sets "area" only from bbox_xxyy).  The area-driven
@@ -81,38 +81,52 @@ def evaluate(model, criterion, postprocessors, data_loader, gt_file, solver, dev
         filenames = [t["filename"] for t in targets]
         clip = torch.stack([torch.as_tensor(t["clip_bbox"], dtype=torch.float32) for t in targets]).to(device)
         outputs = model(samples, clip_bbox=clip)
+        extra = {}
+        if unc_log:
+            aux = outputs.get("aux_outputs", [])
+            if len(aux) < 3:
+                raise ValueError(f"the UNC evaluation log needs three aux_outputs entries, the model returned {len(aux)}")
+            extra["aux_logits"] = [a["pred_logits"] for a in aux[:3]]
         if criterion is not None:
             ld = criterion(outputs, [{k: v.to(device) for k, v in t.items() if torch.is_tensor(v)} for t in targets])
             _log_losses(ld, criterion.weight_dict, device, log)
+        sig = outputs.get("sigmas")
+        if cal is not None and sig is None:
+            raise ValueError("evaluate: calibration needs a model with a sigma head")
         gt = [evaluator.ground_truth[f] for f in filenames]
-        if ceres:
-            # EPnPCeresSolver: one threshold per image from its ground-truth box area (UNC SpeedEval
-            # passes ground_truth[filename]["area"], src/data/speed/speed_dataset.py:396-399)
-            poses = solver.solve_batch(outputs["points_px"], outputs["probs"], outputs.get("sigmas"),
-                                       area=[g["area"] for g in gt], **_lens_kw(solver, outputs.get("sigmas"), clip))
-        else:
-            poses = solver.solve_batch(outputs["points_px"], outputs["probs"], outputs.get("sigmas"),
-                                       **_lens_kw(solver, outputs.get("sigmas"), clip))
         q_gt = torch.tensor([g["quat"] for g in gt], dtype=torch.float64, device=device)
         t_gt = torch.tensor([g["tvec"] for g in gt], dtype=torch.float64, device=device)
-        s_t, s_q = device_speed_score(poses["quat"], poses["tvec"], q_gt, t_gt)
-        sig = outputs.get("sigmas")
-        assess = solver.self_assess(outputs["probs"], sig, poses) if sig is not None else None
-        evaluator.update_batch(filenames, outputs["points_px"], outputs["probs"], poses, s_t, s_q, sig, assess)
-        if landmarks is not None:
-            _update_landmarks(landmarks, outputs, q_gt, t_gt, clip)
-        if cal is not None:
-            if sig is None:
-                raise ValueError("evaluate: calibration needs a model with a sigma head")
-            cal.update(outputs["points_px"], outputs["probs"], sig, poses,
-                       solver.pose_covariance(outputs["probs"], sig, poses, clip_bbox=clip), q_gt, t_gt, s_t, s_q,
-                       clip_bbox=clip)
+        # EPnPCeresSolver: one threshold per image from its ground-truth box area (UNC SpeedEval
+        # passes ground_truth[filename]["area"], src/data/speed/speed_dataset.py:396-399)
+        p = post(outputs, clip, q_gt, t_gt, area=[g["area"] for g in gt] if ceres else None)
+        evaluator.update_batch(filenames, outputs["points_px"], outputs["probs"], p.poses, p.s_t, p.s_q, sig, p.assess,
+                               **extra)
+        if p.cov is not None:
+            _log_pred_score(evaluator.log, filenames, p.cov)
     evaluator.log = spe_dist.all_gather_log(evaluator.log)
     evaluator.summarize()
     stats = {k: s / max(n, 1) for k, (s, n) in meters.items()}
-    _finish_calibration(cal, stats, evaluator)
+    if cal is not None:
+        # the summary into the returned stats and one line onto the evaluator's
+        stats["calibration"] = cal.summarize()
+        evaluator.stats += "; " + cal.stats_line(stats["calibration"])
     stats["speed_eval_pose"] = evaluator.stats
     return stats, evaluator
+
+
+@torch.no_grad()
+def evaluate(model, criterion, postprocessors, data_loader, gt_file, solver, device, output_dir=None,
+             calibration=False, sigma_gain=1.0, landmarks=None):
+    """landmarks (a spe.landmarks.LandmarkReconstruction, None: nothing changes): every batch's keypoints,
+    their sigmas and ground-truth poses are added to it (update(), one launch, no synchronisation); the caller
+    runs landmarks.solve() afterwards.
+
+    calibration (a model with a sigma head): the keypoint sigmas, the pose covariance and its predicted score are
+    compared with the ground truth over the whole set (spe.calibration.Calibration at sigma_gain); the returned
+    stats then carry the summary dict under "calibration" and evaluator.stats one more line.  With several ranks
+    the log is gathered but the calibration is not: each rank's summary and line cover the images it evaluated."""
+    return _evaluate(model, criterion, data_loader, gt_file, solver, device, calibration, sigma_gain, landmarks,
+                     box_areas=True, self_assess=True, unc_log=False, pose_cov=False)
 
 
 @torch.no_grad()
@@ -133,90 +147,8 @@ def evaluate_rtdetr(model, criterion, postprocessors, data_loader, gt_file, solv
     (PoseSolver.pose_covariance; 0 where cov_status is not 0, which "cov_status" tells), computed with
     the sigmas times sigma_gain.  calibration: as for evaluate(); the covariance is computed for it whether
     pose_cov is set or not, and the log entries are those of a run without it.  landmarks: as for evaluate()."""
-    evaluator = SpeedEval(gt_file, solver)
-    cal = _new_calibration(calibration, solver, sigma_gain)
-    meters = {}
-
-    def log(k, v):
-        s = meters.setdefault(k, [0.0, 0])
-        s[0] += float(v)
-        s[1] += 1
-
-    for samples, targets in data_loader:
-        samples = samples.to(device)
-        filenames = [t["filename"] for t in targets]
-        clip = torch.stack([torch.as_tensor(t["clip_bbox"], dtype=torch.float32) for t in targets]).to(device)
-        outputs = model(samples, clip_bbox=clip)
-        aux = outputs.get("aux_outputs", [])
-        if len(aux) < 3:
-            raise ValueError(f"the UNC evaluation log needs three aux_outputs entries, the model returned {len(aux)}")
-        if criterion is not None:
-            ld = criterion(outputs, [{k: v.to(device) for k, v in t.items() if torch.is_tensor(v)} for t in targets])
-            _log_losses(ld, criterion.weight_dict, device, log)
-        poses = solver.solve_batch(outputs["points_px"], outputs["probs"], outputs["sigmas"],
-                                   **_lens_kw(solver, outputs["sigmas"], clip))
-        gt = [evaluator.ground_truth[f] for f in filenames]
-        q_gt = torch.tensor([g["quat"] for g in gt], dtype=torch.float64, device=device)
-        t_gt = torch.tensor([g["tvec"] for g in gt], dtype=torch.float64, device=device)
-        s_t, s_q = device_speed_score(poses["quat"], poses["tvec"], q_gt, t_gt)
-        evaluator.update_batch(filenames, outputs["points_px"], outputs["probs"], poses, s_t, s_q, outputs["sigmas"],
-                               aux_logits=[a["pred_logits"] for a in aux[:3]])
-        if landmarks is not None:
-            _update_landmarks(landmarks, outputs, q_gt, t_gt, clip)
-        cov = None
-        if pose_cov:
-            cov = solver.pose_covariance(outputs["probs"], outputs["sigmas"], poses, clip_bbox=clip, **_gain_kw(sigma_gain))
-            _log_pred_score(evaluator.log, filenames, cov)
-        if cal is not None:
-            # the accumulator applies the gain itself, to the covariance at gain 1
-            if cov is None or float(sigma_gain) != 1.0:
-                cov = solver.pose_covariance(outputs["probs"], outputs["sigmas"], poses, clip_bbox=clip)
-            cal.update(outputs["points_px"], outputs["probs"], outputs["sigmas"], poses, cov, q_gt, t_gt, s_t, s_q,
-                       clip_bbox=clip)
-    evaluator.log = spe_dist.all_gather_log(evaluator.log)
-    evaluator.summarize()
-    stats = {k: s / max(n, 1) for k, (s, n) in meters.items()}
-    _finish_calibration(cal, stats, evaluator)
-    stats["speed_eval_pose"] = evaluator.stats
-    return stats, evaluator
-
-
-def _gain_kw(sigma_gain):
-    """pose_covariance's sigma_gain keyword, left out at 1.0: a solver object without the keyword keeps working."""
-    return {} if float(sigma_gain) == 1.0 else {"sigma_gain": float(sigma_gain)}
-
-
-def _update_landmarks(rec, outputs, q_gt, t_gt, clip):
-    """One batch into a LandmarkReconstruction: the model's sigmas are crop-normalised, the crop's size is
-    their scale."""
-    from .solver import sigma_scale_of
-    sig = outputs.get("sigmas")
-    rec.update(outputs["points_px"], outputs["probs"], sig, q_gt, t_gt,
-               sigma_scale=sigma_scale_of(clip, clip.device) if sig is not None else None)
-
-
-def _new_calibration(calibration, solver, sigma_gain):
-    """The evaluate loops' accumulator: None unless asked for."""
-    if not calibration:
-        return None
-    from .calibration import Calibration
-    return Calibration(sigma_gain=sigma_gain, solver=solver)
-
-
-def _finish_calibration(cal, stats, evaluator):
-    """The summary into the returned stats ("calibration") and one line onto the evaluator's."""
-    if cal is None:
-        return
-    stats["calibration"] = cal.summarize()
-    evaluator.stats += "; " + cal.stats_line(stats["calibration"])
-
-
-def _lens_kw(solver, sigmas, clip):
-    """solve_batch's sigma_scale for a solver with a lens: the crop's size, as the covariance takes it."""
-    if sigmas is None or getattr(solver, "lens", None) is None:
-        return {}
-    from .solver import sigma_scale_of
-    return {"sigma_scale": sigma_scale_of(clip, sigmas.device)}
+    return _evaluate(model, criterion, data_loader, gt_file, solver, device, calibration, sigma_gain, landmarks,
+                     box_areas=False, self_assess=False, unc_log=True, pose_cov=pose_cov)
 
 
 def _log_pred_score(log, filenames, cov):
@@ -303,6 +235,7 @@ def generate_submission(models, postprocessors, anns, read_file, solver, device,
                          "or a SigmaEnsemblePoseSolver")
     decoder = decoder if decoder is not None else JpegDecoder()
     transform = transform if transform is not None else SpeedSubmissionTransform(input_size)
+    post = PostStage(solver, pose_cov=pose_cov, sigma_gain=sigma_gain)
     names = list(anns)
     log = {}
     for i0 in range(0, len(names), int(batch_size)):
@@ -310,6 +243,7 @@ def generate_submission(models, postprocessors, anns, read_file, solver, device,
         bbox = np.asarray([anns[f][0][:4] for f in batch], np.float64)
         frames = _batch_frames([read_file(f) for f in batch], batch, decoder, device)
         t = transform(frames, bbox, crops=True, images=False)
+        poses = None
         if multi:
             outs = [m(t["crops"], clip_bbox=t["clip_bbox"]) for m in models]
             if sigma_multi:
@@ -317,27 +251,26 @@ def generate_submission(models, postprocessors, anns, read_file, solver, device,
                     raise ValueError("generate_submission: SigmaEnsemblePoseSolver needs models with a sigma head")
                 poses = solver.solve_batch_multi([o["points_px"] for o in outs], [o["probs"] for o in outs],
                                                  [o["sigmas"] for o in outs], clip_bbox=t["clip_bbox"])
-                # what pose_cov reads below: the fused keypoint set in one model's layout
+                # what pose_cov reads: the fused keypoint set in one model's layout
                 o = {"probs": poses["fused"]["probs"], "sigmas": poses["fused"]["sigmas"]}
             else:
                 poses = solver.solve_batch_multi([o["points_px"] for o in outs], [o["probs"] for o in outs])
+                o = {}
         else:
             o = models(t["crops"], clip_bbox=t["clip_bbox"])
-            poses = solver.solve_batch(o["points_px"], o["probs"], o.get("sigmas"),
-                                       **_lens_kw(solver, o.get("sigmas"), t["clip_bbox"]))
+        if pose_cov and o.get("sigmas") is None:
+            raise ValueError("generate_submission: pose_cov needs a model with a sigma head")
+        p = post(o, t["clip_bbox"], poses=poses)
         # failed images carry the zero pose, as in SpeedEval.update_batch: every solver status but OK
         # and RANSAC_FALLBACK, and here a status-1 crop too
-        st = poses["status"]
+        st = p.poses["status"]
         failed = ((st != _lib.SPE_PNP_OK) & (st != _lib.SPE_PNP_RANSAC_FALLBACK)) | (t["status"] != 0)
-        rec = torch.cat([poses["quat"].double(), poses["tvec"].double(), failed.double()[:, None]], 1).cpu().numpy()
+        rec = torch.cat([p.poses["quat"].double(), p.poses["tvec"].double(), failed.double()[:, None]], 1).cpu().numpy()
         for f, r in zip(batch, rec):
             quat, tvec = (np.zeros(4), np.zeros(3)) if r[7] else (r[0:4], r[4:7])
             log[f] = {"quat_pr": np.around(quat, decimals=6).tolist(), "tvec_pr": np.around(tvec, decimals=6).tolist()}
-        if pose_cov:
-            if o.get("sigmas") is None:
-                raise ValueError("generate_submission: pose_cov needs a model with a sigma head")
-            cov = solver.pose_covariance(o["probs"], o["sigmas"], poses, clip_bbox=t["clip_bbox"], **_gain_kw(sigma_gain))
-            bad = t["status"] != 0
+        if p.cov is not None:
+            bad, cov = t["status"] != 0, p.cov
             cov["pred_score"] = cov["pred_score"].masked_fill(bad, 0.0)
             cov["cov_status"] = torch.where(bad & (cov["cov_status"] == 0), torch.ones_like(cov["cov_status"]),
                                             cov["cov_status"])

@@ -14,16 +14,15 @@ from __future__ import annotations
 
 import ctypes
 
-import numpy as np
 import torch
 from torch import nn
 
 from . import _lib
 from .config import SpeConfig
-from .misc import NestedTensor, nested_tensor_from_tensor_list
+from ._hipmodel import HipModel
 
 
-class DETR(nn.Module):
+class DETR(HipModel):
     """Keypoint-set predictor (REV/models/detr_speed.py:32-100), HIP implementation.  cfg.backbone
     "resnet50s8": the stride-8 fusion neck (Backbone8s); "resnet50": ResNet-50 cut after layer3 with
     input_proj straight on the stride-16 map (Backbone, REV/models/backbone.py:57-102).  cfg.norm "group_bn":
@@ -40,6 +39,10 @@ class DETR(nn.Module):
     attn_dtype "fp16" (bf16 models): the encoder self-attention's q/k/V operands are stored
     and multiplied in fp16 (BASELINE config 5, "fp16 MFMA attention")."""
 
+    _NAME = "DETR"
+    _HOST_INPUT = "DETR (HIP) expects device tensors; call samples.to('cuda')"
+    _STAGES = "spe_forward_stages"
+
     def __init__(self, cfg: SpeConfig, dtype: str = "bf16", aux_loss: bool = False, attn_dtype: str = None):
         super().__init__()
         self.cfg = cfg
@@ -49,9 +52,6 @@ class DETR(nn.Module):
         if attn_dtype not in (None, dtype, "fp16") or (attn_dtype == "fp16" and dtype != "bf16"):
             raise ValueError(f"attn_dtype {attn_dtype!r}: None, the model dtype, or 'fp16' for bf16 models")
         self.attn_dtype = attn_dtype or dtype
-        self._pending = {}
-        self._handle = None
-        self._ws = {}          # (device, stream) -> (workspace, batch it was sized for)
         L = _lib.lib()
         c = _lib.ModelConfig(cfg.input_size, cfg.num_queries, cfg.enc_layers, cfg.dec_layers, cfg.hidden_dim,
                              cfg.nheads, cfg.dim_feedforward, int(cfg.sigma_head),
@@ -64,57 +64,7 @@ class DETR(nn.Module):
         flags = (_lib.SPE_MODEL_PRE_NORM if cfg.pre_norm else 0) | \
                 (_lib.SPE_MODEL_GROUP_NORM if cfg.norm == "group_bn" else 0)
         _lib.check(L.spe_model_create_flags(ctypes.byref(c), bb, flags, ctypes.byref(h)), "spe_model_create_flags")
-        self._h = h
-        self._keys = [L.spe_model_param_name(h, i).decode() for i in range(L.spe_model_num_params(h))]
-
-    # ---------------------------------------------------------------- parameters
-    def param_keys(self):
-        return list(self._keys)
-
-    def load_state_dict(self, state_dict, strict: bool = True):
-        """Accepts the reference's state_dict (torch tensors or numpy arrays).  Keys outside the
-        inference path (none for REV) are reported as unexpected, like nn.Module."""
-        L = _lib.lib()
-        unexpected = []
-        for k, v in state_dict.items():
-            if k.endswith("num_batches_tracked"):       # FrozenBatchNorm2d drops it (backbone.py:36-42)
-                continue
-            if k not in self._keys:
-                unexpected.append(k)
-                continue
-            a = np.ascontiguousarray(v.detach().cpu().numpy() if torch.is_tensor(v) else v, dtype=np.float32)
-            _lib.check(L.spe_model_set_param(self._h, k.encode(), a.ctypes.data_as(ctypes.c_void_p), a.size),
-                       f"set_param({k})")
-            self._pending[k] = True
-        missing = [k for k in self._keys if k not in self._pending]
-        if strict and (missing or unexpected):
-            raise RuntimeError(f"load_state_dict: missing={missing[:5]}... unexpected={unexpected[:5]}...")
-        self._finalize()
-        return missing, unexpected
-
-    def _finalize(self):
-        if self._handle is None and len(self._pending) == len(self._keys):
-            _lib.check(_lib.lib().spe_model_finalize(self._h), "spe_model_finalize")
-            self._handle = self._h
-
-    def workspace(self, B, device, stream=None):
-        """The default workspace of forward() on `stream` (the current stream if None): one per
-        (device, stream), so forwards issued on different streams never share intermediates;
-        forwards on one stream are ordered by it.  Allocated from torch's caching allocator on
-        that stream, so a regrown workspace's old block is only reused in stream order."""
-        device = torch.device(device)
-        s = stream if stream is not None else torch.cuda.current_stream(device)
-        key = (device.index if device.index is not None else torch.cuda.current_device(), s.cuda_stream)
-        ws = self._ws.get(key)
-        if ws is None or ws[1] < B:
-            nbytes = _lib.lib().spe_model_workspace_bytes(self._h, B)
-            with torch.cuda.stream(s):
-                self._ws[key] = ws = (torch.empty(int(nbytes), dtype=torch.uint8, device=device), B)
-        return ws[0]
-
-    def new_workspace(self, B, device):
-        """A separate workspace for another in-flight batch (encode/decode overlap)."""
-        return torch.empty(int(_lib.lib().spe_model_workspace_bytes(self._h, B)), dtype=torch.uint8, device=device)
+        self._adopt(h)
 
     # ---------------------------------------------------------------- forward
     def _outputs(self, B, dev, clip_bbox, return_hs):
@@ -145,72 +95,27 @@ class DETR(nn.Module):
         encoder layers over the src a backbone part left in `ws` (images may be None, B given)."""
         stage = {None: _lib.SPE_STAGE_ENCODE, "backbone": _lib.SPE_STAGE_BACKBONE,
                  "transformer": _lib.SPE_STAGE_TRANSFORMER}[part]
-        B = images.shape[0] if images is not None else int(B)
-        if images is not None and images.dtype == torch.uint8:
-            ch = self._crop_channels(images)
-            _lib.check(_lib.lib().spe_forward_stages_u8(self._h, _lib.stream_ptr(stream), _lib.ptr(images), ch, B,
-                                                        _lib.ptr(ws), ws.numel(), None, stage), "spe_forward_stages_u8")
-            return
-        _lib.check(_lib.lib().spe_forward_stages(self._h, _lib.stream_ptr(stream), _lib.ptr(images), B, _lib.ptr(ws),
-                                                 ws.numel(), None, stage), "spe_forward_stages")
-
-    def _crop_channels(self, crops):
-        """8-bit crops [B,S,S] (grayscale) or [B,S,S,3] (RGB), contiguous on the device -> channels."""
-        S = self.cfg.input_size
-        if not crops.is_cuda or not crops.is_contiguous():
-            raise ValueError("u8 crops: a contiguous device tensor")
-        if crops.dim() == 3 and tuple(crops.shape[1:]) == (S, S):
-            return 1
-        if crops.dim() == 4 and tuple(crops.shape[1:]) == (S, S, 3):
-            return 3
-        raise ValueError(f"u8 crops: expected [B,{S},{S}] or [B,{S},{S},3], got {tuple(crops.shape)}")
+        self._run(images, images.shape[0] if images is not None else int(B), ws, stream, None, stage)
 
     def decode(self, B, ws, clip_bbox=None, stream=None, return_hs=False):
         """Decode stage (decoder, heads, fused PostProcess) of the memory an encode() left in `ws`."""
-        dev = ws.device
-        if clip_bbox is not None:
-            clip_bbox = clip_bbox.to(device=dev, dtype=torch.float32).contiguous()
-        out, o = self._outputs(B, dev, clip_bbox, return_hs)
-        _lib.check(_lib.lib().spe_forward_stages(self._h, _lib.stream_ptr(stream), None, B, _lib.ptr(ws), ws.numel(),
-                                                 ctypes.byref(o), _lib.SPE_STAGE_DECODE), "spe_forward_stages")
+        out, o = self._outputs(B, ws.device, self._clip(clip_bbox, ws.device), return_hs)
+        self._run(None, B, ws, stream, o, _lib.SPE_STAGE_DECODE)
         return out
 
     def forward(self, samples, clip_bbox=None, stream=None, return_hs=False):
         """REV/models/detr_speed.py:59-92.  Returns pred_logits [B,Q,12], pred_points [B,Q,2]
         (+ pred_sigmas as log-sigma when the sigma head is configured).  Passing `clip_bbox`
         ([B,4] device fp32) also runs the fused PostProcess and adds `probs` / `points_px`."""
-        if self._handle is None:
-            raise RuntimeError("DETR: load_state_dict() with every parameter before forward()")
-        if isinstance(samples, (list, tuple)):            # REV/models/detr_speed.py:74-75
-            samples = nested_tensor_from_tensor_list(list(samples))
-        images = samples.tensors if isinstance(samples, NestedTensor) else samples
-        if not images.is_cuda:
-            raise RuntimeError("DETR (HIP) expects device tensors; call samples.to('cuda')")
-        if images.dtype == torch.uint8:
-            # the 8-bit crops to_tensor + Normalize would make the batch from (spe_forward_stages_u8)
-            ch = self._crop_channels(images)
-            B, dev = images.shape[0], images.device
-            if clip_bbox is not None:
-                clip_bbox = clip_bbox.to(device=dev, dtype=torch.float32).contiguous()
-            out, o = self._outputs(B, dev, clip_bbox, return_hs)
-            ws = self.workspace(B, dev, stream)
-            _lib.check(_lib.lib().spe_forward_stages_u8(self._h, _lib.stream_ptr(stream), _lib.ptr(images), ch, B,
-                                                        _lib.ptr(ws), ws.numel(), ctypes.byref(o),
-                                                        _lib.SPE_STAGE_ENCODE | _lib.SPE_STAGE_DECODE),
-                       "spe_forward_stages_u8")
-            return out
-        images = images.contiguous().float()
-        B, C, H, W = images.shape
-        S = self.cfg.input_size
-        if C != 3 or H != S or W != S:
-            raise ValueError(f"expected [B,3,{S},{S}] input, got {tuple(images.shape)}")
-        dev = images.device
-        if clip_bbox is not None:
-            clip_bbox = clip_bbox.to(device=dev, dtype=torch.float32).contiguous()
-        out, o = self._outputs(B, dev, clip_bbox, return_hs)
-        ws = self.workspace(B, dev, stream)
-        _lib.check(_lib.lib().spe_forward(self._h, _lib.stream_ptr(stream), _lib.ptr(images), B, _lib.ptr(ws),
-                                          ws.numel(), ctypes.byref(o)), "spe_forward")
+        self._require_ready("forward")
+        images = self._unwrap(samples)
+        if images.is_cuda and images.dtype == torch.uint8:
+            self._crop_channels(images)       # the 8-bit crops to_tensor + Normalize would make the batch from
+        else:
+            images = self._fp32_batch(images)
+        B, dev = images.shape[0], images.device
+        out, o = self._outputs(B, dev, self._clip(clip_bbox, dev), return_hs)
+        self._run(images, B, self.workspace(B, dev, stream), stream, o, _lib.SPE_STAGE_ENCODE | _lib.SPE_STAGE_DECODE)
         return out
 
     def forward_with_attention(self, images, enc_layer=-1, dec_layer=-2, clip_bbox=None, *, stream=None, maps=None):
@@ -220,19 +125,10 @@ class DETR(nn.Module):
         Returns (outputs, maps); `outputs` is forward()'s dict, bit for bit.  Model dtypes bf16 and fp32.
         `maps` (optional): {"enc": tensor or None, "dec": tensor or None} of caller buffers to fill; None
         skips that tap (spe_forward_attention's NULL map)."""
-        if self._handle is None:
-            raise RuntimeError("DETR: load_state_dict() with every parameter before forward_with_attention()")
-        if not images.is_cuda:
-            raise RuntimeError("DETR (HIP) expects device tensors; call samples.to('cuda')")
-        images = images.contiguous().float()
-        B, C, H, W = images.shape
-        S = self.cfg.input_size
-        if C != 3 or H != S or W != S:
-            raise ValueError(f"expected [B,3,{S},{S}] input, got {tuple(images.shape)}")
-        dev = images.device
-        if clip_bbox is not None:
-            clip_bbox = clip_bbox.to(device=dev, dtype=torch.float32).contiguous()
-        out, o = self._outputs(B, dev, clip_bbox, False)
+        self._require_ready("forward_with_attention")
+        images = self._fp32_batch(images)
+        B, dev = images.shape[0], images.device
+        out, o = self._outputs(B, dev, self._clip(clip_bbox, dev), False)
         T = self.cfg.tokens
         shapes = {"enc": (B, T, T), "dec": (B, self.cfg.num_queries, T)}
         if maps is None:
@@ -251,14 +147,6 @@ class DETR(nn.Module):
                                            ws.numel(), ctypes.byref(o), int(enc_layer), int(dec_layer),
                                            _lib.ptr(maps["enc"]), _lib.ptr(maps["dec"])), "spe_forward_attention")
         return out, {k: t for k, t in maps.items() if t is not None}
-
-    def __del__(self):
-        try:
-            if getattr(self, "_h", None):
-                _lib.lib().spe_model_destroy(self._h)
-                self._h = None
-        except Exception:
-            pass
 
 
 class SetCriterion(nn.Module):

@@ -12,8 +12,8 @@ import torch
 
 from . import _lib
 from .models import DETR
-from .solver import PoseSolver, sigma_scale_of
-from .speed_eval import device_speed_score
+from .poststage import PostStage
+from .solver import PoseSolver
 
 
 _STREAMS = {}
@@ -56,13 +56,11 @@ class PosePipeline:
                  jpeg_max_bytes: int = 0, overlap_backbone: bool = False, host_input: bool = False,
                  pose_cov: bool = False, sigma_gain: float = 1.0, calibration=None):
         self.model, self.solver, self.B = model, solver, batch
-        self.self_assess = self_assess
         # pose_cov (models with a sigma head): one more launch on the solver's stream after the solve,
         # PoseSolver.pose_covariance; run()'s output then also carries pose_cov [B,6,6], pred_score,
         # sigma_t, sigma_rot and cov_status.  Off: no launch and no key is added.
         # sigma_gain: the calibration factor on the sigmas the covariance reads (spe.calibration measures it);
         # the solver is not touched.  1.0: every output as without it.
-        self.sigma_gain = float(sigma_gain)
         # calibration (an spe.calibration.Calibration; implies pose_cov): every step appends its batch's
         # calibration records against the loaded ground truth, one more launch on the solver's stream and no
         # host synchronisation; run()'s output then carries them under "calibration".
@@ -70,8 +68,8 @@ class PosePipeline:
         # capture's batch however many steps ran.
         if calibration is not None and use_graph:
             raise ValueError("calibration: eager execution only (a graph replay appends nothing to the accumulator)")
-        self.calibration = calibration
         self.pose_cov = pose_cov or calibration is not None
+        self.post = PostStage(solver, self_assess, self.pose_cov, sigma_gain, calibration)
         # overlap: the solver / score / self-assessment of batch i run on a second HIP stream
         # while the forward of batch i+1 runs on the caller's stream (the solver occupies one
         # wave per image, far from filling the chip, and its latency is fp64-bound).  Results of
@@ -162,37 +160,20 @@ class PosePipeline:
         _ = Q
 
     def _solve(self, fo, stream=None, q_gt=None, t_gt=None, repro=None, clip=None):
-        sig = fo.get("sigmas")
-        kw = {}
-        if sig is not None and getattr(self.solver, "lens", None) is not None:
-            # the lens maps the crop-normalised sigmas in pixels: the scale the covariance derives too
-            kw["sigma_scale"] = sigma_scale_of(self.clip_bbox if clip is None else clip, sig.device, stream)
-        if self.per_image_th:
-            poses = self.solver.solve_batch(fo["points_px"], fo["probs"], sig, stream=stream,
-                                            repro_per_image=self.repro if repro is None else repro, **kw)
-        else:
-            poses = self.solver.solve_batch(fo["points_px"], fo["probs"], sig, stream=stream, **kw)
-        q_gt = self.q_gt if q_gt is None else q_gt
-        t_gt = self.t_gt if t_gt is None else t_gt
-        s_t, s_q = device_speed_score(poses["quat"], poses["tvec"], q_gt, t_gt, stream=stream)
-        out = {"forward": fo, "poses": poses, "s_t": s_t, "s_q": s_q}
-        if sig is not None and self.self_assess:
-            out["assess"] = self.solver.self_assess(fo["probs"], sig, poses, stream=stream)   # config-4 filter
-        if self.pose_cov:
-            if sig is None:
-                raise ValueError("pose_cov: the model has no sigma head")
-            # the model's sigmas are crop-normalised like its points: to pixels by the crop's size
-            out.update(self.solver.pose_covariance(fo["probs"], sig, poses, stream=stream,
-                                                   clip_bbox=self.clip_bbox if clip is None else clip,
-                                                   **({} if self.sigma_gain == 1.0 else {"sigma_gain": self.sigma_gain})))
-            if self.calibration is not None:
-                # the records of this batch, with this batch's boxes and ground truth, on the solver's stream;
-                # the accumulator applies its own gain to the covariance at gain 1
-                cov1 = out if self.sigma_gain == 1.0 else self.solver.pose_covariance(
-                    fo["probs"], sig, poses, stream=stream, clip_bbox=self.clip_bbox if clip is None else clip)
-                out["calibration"] = self.calibration.update(
-                    fo["points_px"], fo["probs"], sig, poses, cov1, q_gt, t_gt, s_t, s_q,
-                    clip_bbox=self.clip_bbox if clip is None else clip, stream=stream)
+        """The post-model stage on this batch's boxes, ground truth and thresholds (the staging buffers, or the
+        snapshots an overlap mode took of them) -> run()'s flat dict."""
+        if self.pose_cov and fo.get("sigmas") is None:
+            raise ValueError("pose_cov: the model has no sigma head")
+        post = self.post(fo, self.clip_bbox if clip is None else clip, self.q_gt if q_gt is None else q_gt,
+                         self.t_gt if t_gt is None else t_gt, stream=stream,
+                         repro_per_image=(self.repro if repro is None else repro) if self.per_image_th else None)
+        out = {"forward": fo, "poses": post.poses, "s_t": post.s_t, "s_q": post.s_q}
+        if post.assess is not None:
+            out["assess"] = post.assess   # config-4 filter
+        if post.cov is not None:
+            out.update(post.cov)
+        if post.records is not None:
+            out["calibration"] = post.records
         return out
 
     def _decode(self):

@@ -15,113 +15,44 @@ from __future__ import annotations
 
 import ctypes
 
-import numpy as np
 import torch
 from torch import nn
 
 from . import _lib
-from .misc import NestedTensor, nested_tensor_from_tensor_list
+from ._hipmodel import HipModel
 from .rtdetr_spec import RtdetrConfig, rtdetr_param_shapes, random_rtdetr_weights  # noqa: F401
 
 
-class RTDETR(nn.Module):
+class RTDETR(HipModel):
     """RTDETR(PResNet-vd | MobileNetV3_Large | MobileNetV3_Small | GhostNetV2, HybridEncoder, RTDETRTransformer)
     with the sigma head, eval forward; cfg.backbone picks the backbone ("mobilenetv3_large", "MobileNetV3_Small",
     "ghostnetv2": input_size 256 only).
     dtype "bf16": bf16 storage / MFMA with fp32 accumulation, LayerNorm, softmax and heads;
     "fp32": exact-f32 MFMA everywhere (parity path)."""
 
+    _NAME = "RTDETR"
+    _HOST_INPUT = "RTDETR (HIP) expects device tensors"
+    _STAGES = "spe_rtdetr_forward_stages"
+
     def __init__(self, cfg: RtdetrConfig, dtype: str = "bf16", aux_outputs: bool = True):
         super().__init__()
         self.cfg, self.dtype, self.aux_outputs = cfg, dtype, aux_outputs
         self.num_queries = cfg.num_queries
-        self._pending = {}
-        self._ready = False
-        self._ws = {}
         selector = {"mobilenetv3_large": _lib.SPE_RTDETR_MBV3_LARGE, "MobileNetV3_Small": _lib.SPE_RTDETR_MBV3_SMALL,
                     "ghostnetv2": _lib.SPE_RTDETR_GHOSTNETV2}.get(cfg.backbone, cfg.depth)
         c = _lib.RtdetrConfig(selector, cfg.input_size, cfg.num_queries, cfg.dec_layers, cfg.enc_ff, cfg.dec_ff,
                               cfg.csp_hidden, cfg.num_classes,
                               _lib.SPE_DTYPE_BF16 if dtype == "bf16" else _lib.SPE_DTYPE_F32)
         h = ctypes.c_void_p()
-        L = _lib.lib()
-        _lib.check(L.spe_rtdetr_create(ctypes.byref(c), ctypes.byref(h)), "spe_rtdetr_create")
-        self._h = h
-        self._keys = [L.spe_model_param_name(h, i).decode() for i in range(L.spe_model_num_params(h))]
-
-    def param_keys(self):
-        return list(self._keys)
-
-    def load_state_dict(self, state_dict, strict: bool = True):
-        """The reference's state_dict (torch tensors or numpy); BatchNorm num_batches_tracked
-        buffers are ignored.  Returns (missing, unexpected) like nn.Module."""
-        L = _lib.lib()
-        unexpected = []
-        for k, v in state_dict.items():
-            if k.endswith("num_batches_tracked"):
-                continue
-            if k not in self._keys:
-                unexpected.append(k)
-                continue
-            a = np.ascontiguousarray(v.detach().cpu().numpy() if torch.is_tensor(v) else v, dtype=np.float32)
-            _lib.check(L.spe_model_set_param(self._h, k.encode(), a.ctypes.data_as(ctypes.c_void_p), a.size),
-                       f"set_param({k})")
-            self._pending[k] = True
-        missing = [k for k in self._keys if k not in self._pending]
-        if strict and (missing or unexpected):
-            raise RuntimeError(f"load_state_dict: missing={missing[:5]}... unexpected={unexpected[:5]}...")
-        if not self._ready and len(self._pending) == len(self._keys):
-            _lib.check(L.spe_model_finalize(self._h), "spe_model_finalize")
-            self._ready = True
-        return missing, unexpected
-
-    def workspace(self, B, device, stream=None):
-        """Per-(device, stream) workspace, like DETR.workspace."""
-        device = torch.device(device)
-        s = stream if stream is not None else torch.cuda.current_stream(device)
-        key = (device.index if device.index is not None else torch.cuda.current_device(), s.cuda_stream)
-        ws = self._ws.get(key)
-        if ws is None or ws[1] < B:
-            nbytes = _lib.lib().spe_model_workspace_bytes(self._h, B)
-            with torch.cuda.stream(s):
-                self._ws[key] = ws = (torch.empty(int(nbytes), dtype=torch.uint8, device=device), B)
-        return ws[0]
-
-    def new_workspace(self, B, device):
-        """A separate workspace for another in-flight batch (staged overlap), like DETR.new_workspace."""
-        return torch.empty(int(_lib.lib().spe_model_workspace_bytes(self._h, B)), dtype=torch.uint8, device=device)
-
-    def _crop_channels(self, crops):
-        """8-bit crops [B,S,S] (grayscale) or [B,S,S,3] (RGB), contiguous on the device -> channels."""
-        S = self.cfg.input_size
-        if not crops.is_cuda or not crops.is_contiguous():
-            raise ValueError("u8 crops: a contiguous device tensor")
-        if crops.dim() == 3 and tuple(crops.shape[1:]) == (S, S):
-            return 1
-        if crops.dim() == 4 and tuple(crops.shape[1:]) == (S, S, 3):
-            return 3
-        raise ValueError(f"u8 crops: expected [B,{S},{S}] or [B,{S},{S},3], got {tuple(crops.shape)}")
-
-    def _run(self, images, B, ws, stream, o, stages):
-        """The stages of one forward over `ws`: fp32 images, 8-bit crops, or None without a backbone stage."""
-        L = _lib.lib()
-        out = ctypes.byref(o) if o is not None else None
-        if images is not None and images.dtype == torch.uint8:
-            ch = self._crop_channels(images)
-            _lib.check(L.spe_rtdetr_forward_stages_u8(self._h, _lib.stream_ptr(stream), _lib.ptr(images), ch, B,
-                                                      _lib.ptr(ws), ws.numel(), out, stages),
-                       "spe_rtdetr_forward_stages_u8")
-            return
-        _lib.check(L.spe_rtdetr_forward_stages(self._h, _lib.stream_ptr(stream), _lib.ptr(images), B, _lib.ptr(ws),
-                                               ws.numel(), out, stages), "spe_rtdetr_forward_stages")
+        _lib.check(_lib.lib().spe_rtdetr_create(ctypes.byref(c), ctypes.byref(h)), "spe_rtdetr_create")
+        self._adopt(h)
 
     def encode(self, images, ws, stream=None, part=None, B=None):
         """Encode stage (backbone + HybridEncoder): images -> the three level outputs kept in `ws`.
         part="backbone": the backbone alone (images -> the stride 8 / 16 / 32 maps in `ws`);
         part="transformer": the HybridEncoder over the maps a backbone part left in `ws` (images may be
         None, B given).  images: the fp32 batch [B,3,S,S] or 8-bit crops (forward's forms), on the device."""
-        if not self._ready:
-            raise RuntimeError("RTDETR: load_state_dict() with every parameter before encode()")
+        self._require_ready("encode")
         stage = {None: _lib.SPE_STAGE_ENCODE, "backbone": _lib.SPE_STAGE_BACKBONE,
                  "transformer": _lib.SPE_STAGE_TRANSFORMER}[part]
         B = images.shape[0] if images is not None else int(B)
@@ -130,12 +61,9 @@ class RTDETR(nn.Module):
     def decode(self, B, ws, clip_bbox=None, stream=None, aux=None, return_hs=False):
         """Decode stage (RTDETRTransformer, heads, fused RTDETRPostProcessor) of the level outputs an
         encode() left in `ws`; returns forward's dict."""
-        if not self._ready:
-            raise RuntimeError("RTDETR: load_state_dict() with every parameter before decode()")
-        dev = ws.device
-        if clip_bbox is not None:
-            clip_bbox = clip_bbox.to(device=dev, dtype=torch.float32).contiguous()
-        out, o = self._outputs(B, dev, clip_bbox, self.aux_outputs if aux is None else aux, return_hs)
+        self._require_ready("decode")
+        out, o = self._outputs(B, ws.device, self._clip(clip_bbox, ws.device), self.aux_outputs if aux is None else aux,
+                               return_hs)
         self._run(None, B, ws, stream, o, _lib.SPE_STAGE_DECODE)
         return out
 
@@ -178,26 +106,14 @@ class RTDETR(nn.Module):
         bit-identical to the fp32 batch normalised that way."""
         if torch.is_tensor(samples) and samples.dtype == torch.uint8:
             self._crop_channels(samples)              # (a malformed crop batch is refused whatever the model's state)
-        if not self._ready:
-            raise RuntimeError("RTDETR: load_state_dict() with every parameter before forward()")
-        aux = self.aux_outputs if aux is None else aux
-        if isinstance(samples, (list, tuple)):
-            samples = nested_tensor_from_tensor_list(list(samples))
-        images = samples.tensors if isinstance(samples, NestedTensor) else samples
+        self._require_ready("forward")
+        images = self._unwrap(samples)
         if images.dtype != torch.uint8:
-            if not images.is_cuda:
-                raise RuntimeError("RTDETR (HIP) expects device tensors")
-            images = images.contiguous().float()
-            B, C3, H, W = images.shape
-            S = self.cfg.input_size
-            if C3 != 3 or H != S or W != S:
-                raise ValueError(f"expected [B,3,{S},{S}] input, got {tuple(images.shape)}")
+            images = self._fp32_batch(images)
         else:
             self._crop_channels(images)
         B, dev = images.shape[0], images.device
-        if clip_bbox is not None:
-            clip_bbox = clip_bbox.to(device=dev, dtype=torch.float32).contiguous()
-        out, o = self._outputs(B, dev, clip_bbox, aux, return_hs)
+        out, o = self._outputs(B, dev, self._clip(clip_bbox, dev), self.aux_outputs if aux is None else aux, return_hs)
         self._run(images, B, self.workspace(B, dev, stream), stream, o, _lib.SPE_STAGE_ENCODE | _lib.SPE_STAGE_DECODE)
         return out
 
@@ -214,22 +130,10 @@ class RTDETR(nn.Module):
           "dec_weights" [B,Q,8,3,4] their softmaxed weights; points=False skips both
         and "level_sizes", the side of each level's map.  Negative dec_layer counts from the end.  fp32 batches
         only (the u8 crop form is forward()'s)."""
-        if not self._ready:
-            raise RuntimeError("RTDETR: load_state_dict() with every parameter before forward_with_attention()")
-        if isinstance(samples, (list, tuple)):
-            samples = nested_tensor_from_tensor_list(list(samples))
-        images = samples.tensors if isinstance(samples, NestedTensor) else samples
-        if not images.is_cuda:
-            raise RuntimeError("RTDETR (HIP) expects device tensors")
-        images = images.contiguous().float()
-        B, C3, H, W = images.shape
-        S = self.cfg.input_size
-        if C3 != 3 or H != S or W != S:
-            raise ValueError(f"expected [B,3,{S},{S}] input, got {tuple(images.shape)}")
-        dev = images.device
-        if clip_bbox is not None:
-            clip_bbox = clip_bbox.to(device=dev, dtype=torch.float32).contiguous()
-        out, o = self._outputs(B, dev, clip_bbox, self.aux_outputs, False)
+        self._require_ready("forward_with_attention")
+        images = self._fp32_batch(self._unwrap(samples))
+        B, dev = images.shape[0], images.device
+        out, o = self._outputs(B, dev, self._clip(clip_bbox, dev), self.aux_outputs, False)
         sizes = list(self.cfg.level_sizes)
         Q, T5, L = self.cfg.num_queries, sizes[-1] ** 2, sum(s * s for s in sizes)
         maps = {"dec_map": torch.empty(B, Q, L, device=dev)}
@@ -248,8 +152,7 @@ class RTDETR(nn.Module):
 
     def backbone_features(self, images, stream=None):
         """The backbone stage alone (spe_debug_rtdetr_backbone): the stride 8 / 16 / 32 maps as fp32 NCHW."""
-        if not self._ready:
-            raise RuntimeError("RTDETR: load_state_dict() with every parameter before backbone_features()")
+        self._require_ready("backbone_features")
         images = images.contiguous().float()
         B, dev = images.shape[0], images.device
         feats = [torch.empty(B, ch, s, s, device=dev) for ch, s in zip(self.cfg.backbone_channels, self.cfg.level_sizes)]
@@ -258,14 +161,6 @@ class RTDETR(nn.Module):
                                                         ws.numel(), *[_lib.ptr(f) for f in feats]),
                    "spe_debug_rtdetr_backbone")
         return feats
-
-    def __del__(self):
-        try:
-            if getattr(self, "_h", None):
-                _lib.lib().spe_model_destroy(self._h)
-                self._h = None
-        except Exception:
-            pass
 
 
 class RTDETRPostProcessor(nn.Module):

@@ -112,10 +112,27 @@ class PoseSolver:
                     t.record_stream(stream)
         return o
 
-    def _lens_step(self, points_px, sigmas, sigma_scale, stream):
-        """solve_batch's prologue with a lens: (points, sigmas) to solve on and what `out` gains."""
-        o = self.undistort(points_px, sigmas, sigma_scale, stream)
-        return o["points_ideal"], o["sigmas_ideal"], {k: v for k, v in o.items() if v is not None}
+    def _prologue(self, points_px, probs, sigmas, sigma_scale, undistorted, stream):
+        """Every solve_batch's start: the device constants, the world check and, with a lens, the undistortion.
+        -> K, the landmarks, the (points, sigmas) to solve on and what `out` gains."""
+        B, Q, C = probs.shape
+        Kd, Wd = self._consts(probs.device)
+        self._check_world(C)
+        ideal = {}
+        if self.lens is not None and not undistorted and B > 0:
+            o = self.undistort(points_px, sigmas, sigma_scale, stream)
+            points_px, sigmas, ideal = o["points_ideal"], o["sigmas_ideal"], {k: v for k, v in o.items() if v is not None}
+        return Kd, Wd, points_px, sigmas, ideal
+
+    @staticmethod
+    def _pose_tensors(B, dev):
+        """The seven outputs every solver kernel fills."""
+        return dict(quat=torch.empty(B, 4, device=dev), tvec=torch.empty(B, 3, dtype=torch.float64, device=dev),
+                    rvec=torch.empty(B, 3, dtype=torch.float64, device=dev),
+                    status=torch.empty(B, dtype=torch.int32, device=dev),
+                    n_corr=torch.empty(B, dtype=torch.int32, device=dev),
+                    corr_label=torch.empty(B, 16, dtype=torch.int32, device=dev),
+                    inlier_mask=torch.empty(B, dtype=torch.int32, device=dev))
 
     def _consts(self, device):
         key = str(device)
@@ -136,19 +153,9 @@ class PoseSolver:
         sigma_scale [B,2]: the pixels per sigma unit (sigma_scale_of(clip_bbox) for a model's
         crop-normalised sigmas; None: they are pixels).  undistorted: the points are ideal already."""
         B, Q, C = probs.shape
-        dev = probs.device
-        Kd, Wd = self._consts(dev)
-        self._check_world(C)
-        ideal = {}
-        if self.lens is not None and not undistorted and B > 0:
-            points_px, sigmas, ideal = self._lens_step(points_px, sigmas, sigma_scale, stream)
+        Kd, Wd, points_px, sigmas, ideal = self._prologue(points_px, probs, sigmas, sigma_scale, undistorted, stream)
         if out is None:
-            out = dict(quat=torch.empty(B, 4, device=dev), tvec=torch.empty(B, 3, dtype=torch.float64, device=dev),
-                       rvec=torch.empty(B, 3, dtype=torch.float64, device=dev),
-                       status=torch.empty(B, dtype=torch.int32, device=dev),
-                       n_corr=torch.empty(B, dtype=torch.int32, device=dev),
-                       corr_label=torch.empty(B, 16, dtype=torch.int32, device=dev),
-                       inlier_mask=torch.empty(B, dtype=torch.int32, device=dev))
+            out = self._pose_tensors(B, probs.device)
         _lib.check(_lib.lib().spe_pnp_batch(
             _lib.stream_ptr(stream), _lib.ptr(points_px.contiguous()), _lib.ptr(probs.contiguous()),
             _lib.ptr(sigmas.contiguous() if sigmas is not None else None), B, Q, C, _lib.ptr(Kd), _lib.ptr(Wd),
@@ -285,23 +292,29 @@ class EPnPCeresSolver(PoseSolver):
         self.reprojectionError = self.repro_th(area)
         return self.reprojectionError
 
+    def _thresholds(self, repro_per_image, area, dev, stream):
+        """`repro_per_image`, or `area` (B box areas, repro_th each) -> the device fp32 [B] thresholds, kept for
+        `stream` (the kernel may still read them there after solve_batch returns); None with neither."""
+        if repro_per_image is None:
+            if area is None:
+                return None
+            repro_per_image = torch.tensor([self.repro_th(float(a)) for a in area], dtype=torch.float32, device=dev)
+        repro_per_image = repro_per_image.float().contiguous()
+        if stream is not None:
+            repro_per_image.record_stream(stream)
+        return repro_per_image
+
     def solve_batch(self, points_px, probs, sigmas=None, stream=None, out=None, repro_per_image=None, area=None,
                     sigma_scale=None, undistorted=False):
         """As PoseSolver.solve_batch with one threshold per image: `area` (B box areas) or
         `repro_per_image` (device fp32 [B]) is required -- the reference has no batch-wide
         threshold for this solver (get_repro_th runs per image, :90)."""
+        repro_per_image = self._thresholds(repro_per_image, area, probs.device, stream)
         if repro_per_image is None:
-            if area is None:
-                raise ValueError("EPnPCeresSolver.solve_batch needs the per-image box areas (area=) or thresholds "
-                                 "(repro_per_image=): the reference derives every image's threshold from its area")
-            repro_per_image = torch.tensor([self.repro_th(float(a)) for a in area], dtype=torch.float32,
-                                           device=probs.device)
-        repro_per_image = repro_per_image.float().contiguous()
+            raise ValueError("EPnPCeresSolver.solve_batch needs the per-image box areas (area=) or thresholds "
+                             "(repro_per_image=): the reference derives every image's threshold from its area")
         o = super().solve_batch(points_px, probs, sigmas, stream=stream, out=out, repro_per_image=repro_per_image,
                                 sigma_scale=sigma_scale, undistorted=undistorted)
-        # the kernel may still read the thresholds on `stream` after this returns
-        if stream is not None:
-            repro_per_image.record_stream(stream)
         o["repro_per_image"] = repro_per_image
         return o
 
@@ -329,6 +342,7 @@ class ExhaustivePoseSolver(PoseSolver):
 
     repro_th = EPnPCeresSolver.repro_th
     get_repro_th = EPnPCeresSolver.get_repro_th
+    _thresholds = EPnPCeresSolver._thresholds
 
     def solve_batch(self, points_px, probs, sigmas=None, stream=None, out=None, repro_per_image=None, area=None,
                     sigma_scale=None, undistorted=False):
@@ -338,22 +352,10 @@ class ExhaustivePoseSolver(PoseSolver):
         batch-wide reprojectionError is used."""
         B, Q, C = probs.shape
         dev = probs.device
-        Kd, Wd = self._consts(dev)
-        self._check_world(C)
-        ideal = {}
-        if self.lens is not None and not undistorted and B > 0:
-            points_px, sigmas, ideal = self._lens_step(points_px, sigmas, sigma_scale, stream)
-        if repro_per_image is None and area is not None:
-            repro_per_image = torch.tensor([self.repro_th(float(a)) for a in area], dtype=torch.float32, device=dev)
-        if repro_per_image is not None:
-            repro_per_image = repro_per_image.float().contiguous()
+        Kd, Wd, points_px, sigmas, ideal = self._prologue(points_px, probs, sigmas, sigma_scale, undistorted, stream)
+        repro_per_image = self._thresholds(repro_per_image, area, dev, stream)
         if out is None:
-            out = dict(quat=torch.empty(B, 4, device=dev), tvec=torch.empty(B, 3, dtype=torch.float64, device=dev),
-                       rvec=torch.empty(B, 3, dtype=torch.float64, device=dev),
-                       status=torch.empty(B, dtype=torch.int32, device=dev),
-                       n_corr=torch.empty(B, dtype=torch.int32, device=dev),
-                       corr_label=torch.empty(B, 16, dtype=torch.int32, device=dev),
-                       inlier_mask=torch.empty(B, dtype=torch.int32, device=dev))
+            out = self._pose_tensors(B, dev)
         for k, dt in (("cand_index", torch.int32), ("repro_final", torch.float32)):
             if k not in out:
                 out[k] = torch.empty(B, dtype=dt, device=dev)
@@ -366,9 +368,6 @@ class ExhaustivePoseSolver(PoseSolver):
             _lib.ptr(out["repro_final"])), "spe_pnp_exhaustive")
         out.update(ideal)
         if repro_per_image is not None:
-            # the kernel may still read the thresholds on `stream` after this returns
-            if stream is not None:
-                repro_per_image.record_stream(stream)
             out["repro_per_image"] = repro_per_image
         return out
 
@@ -470,10 +469,7 @@ class SigmaEnsemblePoseSolver:
             sig = torch.stack(list(multi_sigmas)).float().contiguous()
             M, B, Q, C = prb.shape
             dev = prb.device
-            scale = None
-            if clip_bbox is not None:
-                cb = clip_bbox.to(device=dev, dtype=torch.float32)
-                scale = torch.stack((cb[:, 2] - cb[:, 0], cb[:, 3] - cb[:, 1]), 1).contiguous()
+            scale = sigma_scale_of(clip_bbox, dev, stream) if clip_bbox is not None else None
             lens_scale = scale.repeat(M, 1) if scale is not None and self.lens is not None else None
         if pts.shape != (M, B, Q, 2) or sig.shape != (M, B, Q, 2):
             raise ValueError(f"points {tuple(pts.shape)} / sigmas {tuple(sig.shape)} do not match probs {tuple(prb.shape)}")
